@@ -9,13 +9,16 @@ C ABI -- row normaliser, beam decode, traceback, int64 SparseTensor components
 packed on the device and materialised on the host ("logits
 already resident on device, output SparseTensor components materialised on
 host") -- plus, for N>1, the RCCL gather of every rank's outputs to rank 0.
-Weak scaling: the global batch is 256*N.  Extras beside `value`: the same call
-with the components left in HBM (`device_outputs`) and with host logits in
-(`host_io`, PCIe both ways).
+Weak scaling: the global batch is 256*N.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement), with
-a roofline object for the dominant kernel (ctcx_beam_decode, timed with HIP
-events on the stream it runs on) and a cpu_baseline object (the oracle's
+A plain run sets up, warms up, times --steps steps, writes the last timed
+step's outputs if --dump-outputs DIR is given, and prints ONE JSON result line
+on rank 0.  --full adds to that line, after the timed
+steps, everything else: the outputs' digest against the oracle's fixture, a
+roofline object for the dominant kernel (ctcx_beam_decode, timed with HIP
+events on the stream it runs on), the same call with the components left in
+HBM (`device_outputs`) and with host logits in (`host_io`, PCIe both ways),
+the strong-scaling extra and a cpu_baseline object (the oracle's
 reference-cost mode on a bounded sample, N=1 only).
 """
 import argparse
@@ -127,6 +130,42 @@ def output_digest(out, P):
     lp = out[6]
     feed(lp, lp.dtype if isinstance(lp, np.ndarray) else str(lp.dtype).replace("torch.", ""))
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 60 << 20   # --dump-outputs: all the .npy payloads together stay under 64 MB
+
+
+def dump_outputs(out, P, dirname):
+    """--dump-outputs: one decode call's outputs as DIR/<field>_<path>.npy and
+    DIR/log_probability.npy.  The int64 SparseTensor components are written as
+    float64 (exact below 2**53), log_probability ([B, P]) in the input dtype.
+    If everything together would pass DUMP_LIMIT_BYTES, each array keeps the
+    same fraction of its rows, chosen by default_rng(0) from the array's
+    length alone (so two builds that agree on the sizes sample the same rows);
+    the full row count is then the first thing to differ."""
+    os.makedirs(dirname, exist_ok=True)
+
+    def host(a):
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        return np.asarray(a)
+    arrays = {}
+    for name, field in zip(out._fields[:6], out[:6]):
+        for p in range(P):
+            arrays["%s_%d" % (name, p)] = host(field[p]).astype(np.float64)
+    lp = host(out[6])
+    arrays["log_probability"] = lp if lp.dtype in (np.float32, np.float64) else lp.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, DUMP_LIMIT_BYTES / max(total, 1))
+    written = 0
+    for name, a in arrays.items():
+        n = a.shape[0] if a.ndim else 0
+        if frac < 1.0 and n > 16:   # (the shapes and small arrays stay whole)
+            rows = np.sort(np.random.default_rng(0).choice(n, size=max(1, int(n * frac)), replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        written += a.nbytes
+    return {"dir": dirname, "arrays": len(arrays), "bytes": written, "sampled_fraction": frac}
 
 
 def expected_digest(config, rank, B, T):
@@ -285,7 +324,17 @@ def main():
     ap.add_argument("--no-strong", action="store_true",
                     help="skip the strong-scaling extra (N=1: the per-GPU latency at the B=256/N shards; "
                          "N>1: the measured global-B=256 split)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also: the outputs' digest against the oracle's fixture, the "
+                         "roofline object, device_outputs, host_io, strong scaling and the CPU baseline "
+                         "(each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64 for the int64 "
+                         "components, log_probability in its own dtype; a seeded row sample past %d MB)"
+                         % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -367,12 +416,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # the parity gate on the timed workload: the last timed step's outputs
-    # against the oracle's for these exact inputs (outside the timed region)
-    digest = output_digest(out, P)
-    # (the ring flags change no output; the bigram scorer does: no fixture)
-    want = expected_digest(args.config, rank, B, T) if args.scorer == "base" else None
-    match = None if want is None else digest == want
+    digest, match = None, None
+    if args.full:
+        # the parity gate on the timed workload: the last timed step's outputs
+        # against the oracle's for these exact inputs (outside the timed region)
+        digest = output_digest(out, P)
+        # (the ring flags change no output; the bigram scorer does: no fixture)
+        want = expected_digest(args.config, rank, B, T) if args.scorer == "base" else None
+        match = None if want is None else digest == want
     redecodes = red
     if world > 1:   # every rank's verdict: -1 no fixture, 0 mismatch, 1 match
         m = torch.tensor([-1 if match is None else int(match), redecodes], dtype=torch.int64, device=dev)
@@ -384,20 +435,6 @@ def main():
     frames_per_step = int(sl_np.sum()) * world
     value = frames_per_step * args.steps / elapsed
     ms = 1e3 * elapsed / args.steps
-    kavg = float(np.mean(kms))
-    abytes = algorithmic_bytes(sl_np, C, P, out)
-    achieved = abytes / (kavg * 1e-3) / 1e9
-    # HBM bytes per launch from this build's PMC passes (tools/pmc_summary.py);
-    # a file stamped with another library build is stale and not used
-    traffic, traffic_src = None, "no PMC file for this config"
-    pmc = os.path.join(ROOT, "profiles", "pmc_%s.json" % args.config)
-    if os.path.exists(pmc):
-        pj = json.load(open(pmc))
-        if pj.get("lib_sha16") == lib_hash() and pj.get("seq_len", T) == T:
-            traffic, traffic_src = pj.get("hbm_bytes_per_launch"), os.path.relpath(pmc, ROOT)
-        else:
-            traffic_src = "stale: %s is of build %s, this is %s" % (os.path.relpath(pmc, ROOT),
-                                                                   pj.get("lib_sha16"), lib_hash())
     metric = "decoded frames/sec at B=256, T=1500, C=29, beam_width=128; 1/2/4/8 GPUs"   # BASELINE.json
     if args.config != "cfg3" or args.seq_len or args.batch_per_gpu or args.scorer != "base":   # diagnostics
         metric = "decoded frames/sec at B=%d, T=%d, C=%d, beam_width=%d (%s%s, not the BASELINE metric)" % (
@@ -413,6 +450,51 @@ def main():
                    "merge_repeated": merge, "parallelism": "batch-shard x%d" % world,
                    "gather": world > 1 and not args.no_gather,
                    "backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None},
+        "literal_frames_per_step": lit / max(args.steps, 1),
+        # a helper-wave timeout re-decodes with the one-wave kernels: never silent
+        "helper_redecodes": redecodes,
+        "what": ("one decode call: device logits in, int64 SparseTensor components materialised on the host"
+                 if world == 1 else "one decode call per rank (device outputs) + %s gather to rank 0"
+                 % ("RCCL" if backend == "nccl" else backend)),
+        "full": args.full,
+    }
+    if args.dump_outputs and rank == 0:
+        # what the timed path returned in its last step (N>1: rank 0's own shard)
+        res["dumped_outputs"] = dump_outputs(out, P, args.dump_outputs)
+    if args.full:
+        full_extras(args, res, cfg, world, rank, dev, dec, gather_to_root, step, x, x_np, sl_np, out, st,
+                    kms, pms, tms, digest, match)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_extras(args, res, cfg, world, rank, dev, dec, gather_to_root, step, x, x_np, sl_np, out, st,
+                kms, pms, tms, digest, match):
+    """--full: everything beside the headline figure, added to `res` after the
+    timed steps: the digest verdict, the roofline object (from the timed
+    steps' HIP-event kernel times), the library's stamp, and the extra runs
+    (device_outputs, host_io, strong scaling, the CPU baseline)."""
+    import torch
+    import ctcext_amd
+    B, T, C, W, P, merge, blank = cfg
+    value = res["value"]
+    kavg = float(np.mean(kms))
+    abytes = algorithmic_bytes(sl_np, C, P, out)
+    achieved = abytes / (kavg * 1e-3) / 1e9
+    # HBM bytes per launch from this build's PMC passes (tools/pmc_summary.py);
+    # a file stamped with another library build is stale and not used
+    traffic, traffic_src = None, "no PMC file for this config"
+    pmc = os.path.join(ROOT, "profiles", "pmc_%s.json" % args.config)
+    if os.path.exists(pmc):
+        pj = json.load(open(pmc))
+        if pj.get("lib_sha16") == lib_hash() and pj.get("seq_len", T) == T:
+            traffic, traffic_src = pj.get("hbm_bytes_per_launch"), os.path.relpath(pmc, ROOT)
+        else:
+            traffic_src = "stale: %s is of build %s, this is %s" % (os.path.relpath(pmc, ROOT),
+                                                                   pj.get("lib_sha16"), lib_hash())
+    res.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "ctcx_beam_decode", "kernel_ms": kavg,
@@ -425,19 +507,13 @@ def main():
                      # the other kernels of the call (HIP events): the row pre-pass
                      # (normaliser; large C also the row facts) and traceback + pack
                      "prepass_ms": float(np.mean(pms)), "traceback_ms": float(np.mean(tms))},
-        "literal_frames_per_step": lit / max(args.steps, 1),
         # tests/golden/bench_digests.json: the oracle's outputs for these
         # inputs (null: no fixture for this config, e.g. cfg5's device-drawn logits)
         "outputs_match_oracle": match, "outputs_sha256": digest,
-        # a helper-wave timeout re-decodes with the one-wave kernels: never silent
-        "helper_redecodes": redecodes,
         "lib_sha16": lib_hash(),
         # __graft_entry__.build()'s record: recompiled or reused, and the sha
         "build_info": _build_info(),
-        "what": ("one decode call: device logits in, int64 SparseTensor components materialised on the host"
-                 if world == 1 else "one decode call per rank (device outputs) + %s gather to rank 0"
-                 % ("RCCL" if backend == "nccl" else backend)),
-    }
+    })
     if world == 1 and not args.no_host_io:
         # the same call with the components left in HBM (no device->host copy)
         n_dev = max(1, min(args.steps, 3))
@@ -477,10 +553,6 @@ def main():
         res["cpu_baseline"]["calibration"]["gpu_over_reference_equivalent"] = (
             value / res["cpu_baseline"]["calibration"]["reference_equivalent_value"])
         res["cpu_baseline"]["host_cpus"] = info
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

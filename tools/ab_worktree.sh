@@ -11,7 +11,9 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 for r in $(seq $N); do
   REF=""
   for side in . abold; do
-    v=$(cd $R/$side && timeout -k 10 240 python bench.py --steps 3 --warmup 1 --no-cpu --no-host-io "$@" 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.0f %.2f %s" % (d["value"], d["roofline"]["kernel_ms"], d.get("outputs_sha256", "-")[:16]))') || exit 1
+    # (kernel_ms and the digest are in the --full line; an older bench.py has no such option)
+    full=""; grep -q -- '"--full"' $R/$side/bench.py && full=--full
+    v=$(cd $R/$side && timeout -k 10 240 python bench.py $full --steps 3 --warmup 1 --no-cpu --no-host-io "$@" 2>/dev/null | python3 -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%.0f %.2f %s" % (d["value"], d["roofline"]["kernel_ms"], d.get("outputs_sha256", "-")[:16]))') || exit 1
     read -r val kms sha <<< "$v"
     if [ "$sha" = "-" ]; then   # an older bench.py without the digest: hash with this tree's
       echo "$side: no outputs_sha256 in its line; timing withheld"

@@ -11,5 +11,5 @@ for cfg in cfg3 cfg4 cfg5; do echo "[$(date +%T)] ab $cfg" >> $O/steps.log; echo
 echo "[$(date +%T)] ab extbig" >> $O/steps.log; echo "== cfg4 rank extract at large C (extbig: CTCX_EXT_BIG=1; its traceback is the old kernel)" >> $O/summary.txt
 CFG=cfg4 bash tools/abv.sh 2 'cur||' 'extbig||abrun/libextbig.so|' >> $O/summary.txt 2>&1 || exit 15
 echo "[$(date +%T)] bench" >> $O/steps.log
-timeout -k 10 400 python bench.py > $O/bench_cfg3.json 2> $O/bench_cfg3.err || exit 14
+timeout -k 10 400 python bench.py --full > $O/bench_cfg3.json 2> $O/bench_cfg3.err || exit 14
 echo "[$(date +%T)] done" >> $O/steps.log

@@ -30,7 +30,7 @@ REC_BYTES=${REC_BYTES:-4} python3 $R/tools/pmc_summary.py $(cc $O/fetch_cfg3) $(
 cp $O/pmc_cfg3.json $R/profiles/pmc_cfg3.json
 step bench-cfg3
 cd $R
-timeout -k 10 300 python3 bench.py > $O/bench_cfg3.json 2> $O/bench_cfg3.err || exit 17
+timeout -k 10 300 python3 bench.py --full > $O/bench_cfg3.json 2> $O/bench_cfg3.err || exit 17
 if [ "$QUICK" != 1 ]; then
   cd /tmp
   step stats-cfg4
