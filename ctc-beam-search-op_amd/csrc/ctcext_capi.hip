@@ -30,12 +30,14 @@ int use_helper_kernel(const DecodeParams<T>& p, int hk);
 template <typename T>
 int helper_kind(const DecodeParams<T>& p, int mode);
 template <typename T>
-hipError_t launch_row_norm(const T* x, const int32_t* sl, T* norm, int64_t T_, int64_t B, int64_t C,
-                           int64_t xstride, hipStream_t s);
+hipError_t launch_row_norm(const void* x, int xfmt, const int32_t* sl, T* norm, int64_t T_, int64_t B, int64_t C,
+                           int64_t xst_t, int64_t xst_b, hipStream_t s);
 hipError_t launch_traceback(const TraceParams& tp, hipStream_t s);
 template <typename T>
-hipError_t launch_row_prep(const T* x, const int32_t* sl, char* prep, T* norm, int64_t T_, int64_t B, int64_t C,
-                           int64_t xstride, int blank, hipStream_t s);
+hipError_t launch_row_prep(const void* x, int xfmt, const int32_t* sl, char* prep, T* norm, int64_t T_, int64_t B,
+                           int64_t C, int64_t xst_t, int64_t xst_b, int blank, hipStream_t s);
+hipError_t launch_widen_rows(const void* x, int xfmt, float* out, int64_t T_, int64_t B, int64_t C, int64_t xst_t,
+                             int64_t xst_b, hipStream_t s);
 hipError_t launch_scan(const int32_t* len, int64_t* off, int64_t* res, int64_t B, int P, hipStream_t s);
 hipError_t launch_pack(const PackParams& pp, hipStream_t s);
 }  // namespace ctcx
@@ -123,7 +125,7 @@ struct Dev {
   hipStream_t own_stream = nullptr;
   hipStream_t s = nullptr;   // stream of the current call
   hipEvent_t ev[4] = {};
-  DevBuf x, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
+  DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   int64_t lo = 0, nb = 0;    // this call's shard [lo, lo + nb)
   int ring = 0;              // this call's record-ring frames (ctcx::ring_frames)
   int rec_bytes = 8;         // this call's record size (8, 16 or 4 bytes)
@@ -150,7 +152,7 @@ struct ctcext_decoder {
 static void release_dev(Dev& d) {
   (void)hipSetDevice(d.device);
   if (d.own_stream) (void)hipStreamSynchronize(d.own_stream);
-  DevBuf* bufs[] = {&d.x, &d.sl, &d.norm, &d.prep, &d.rec, &d.foff, &d.item, &d.top_pos, &d.top_kind, &d.logp,
+  DevBuf* bufs[] = {&d.x, &d.xw, &d.sl, &d.norm, &d.prep, &d.rec, &d.foff, &d.item, &d.top_pos, &d.top_kind, &d.logp,
                     &d.seq, &d.len, &d.phase, &d.sctab, &d.gstate};
   for (DevBuf* b : bufs) b->release();
   for (auto& ev : d.ev)
@@ -259,11 +261,12 @@ extern "C" int ctcext_row_facts(ctcext_decoder* d, const void* x, int32_t dtype,
   HIP_OR_FAIL(hipSetDevice(r.device));
   const hipStream_t st = r.own_stream;
   if (dtype == CTCEXT_F64)
-    HIP_OR_FAIL(ctcx::launch_row_prep<double>((const double*)x, seq_len, (char*)prep, (double*)norm, max_time, batch,
-                                              num_classes, batch, blank_index, st));
+    HIP_OR_FAIL(ctcx::launch_row_prep<double>(x, ctcx::kInNative, seq_len, (char*)prep, (double*)norm, max_time,
+                                              batch, num_classes, batch * num_classes, num_classes, blank_index,
+                                              st));
   else
-    HIP_OR_FAIL(ctcx::launch_row_prep<float>((const float*)x, seq_len, (char*)prep, (float*)norm, max_time, batch,
-                                             num_classes, batch, blank_index, st));
+    HIP_OR_FAIL(ctcx::launch_row_prep<float>(x, ctcx::kInNative, seq_len, (char*)prep, (float*)norm, max_time, batch,
+                                             num_classes, batch * num_classes, num_classes, blank_index, st));
   HIP_OR_FAIL(hipStreamSynchronize(st));
   return CTCEXT_OK;
 }
@@ -361,6 +364,25 @@ static int check_limits(const ctcext_decode_args* a) {
   return CTCEXT_OK;
 }
 
+// The ABI-7 fields: the element format and the strides of inputs (after every
+// check above, so the reference's errors and their order stay as they were).
+static int check_layout(const ctcext_decode_args* a) {
+  const int f = a->inputs_format;
+  if (f != CTCEXT_IN_NATIVE && f != CTCEXT_IN_F16 && f != CTCEXT_IN_BF16)
+    return fail(CTCEXT_INVALID_ARGUMENT, "inputs_format must be CTCEXT_IN_NATIVE, CTCEXT_IN_F16 or CTCEXT_IN_BF16");
+  if (f != CTCEXT_IN_NATIVE && a->dtype != CTCEXT_F32)
+    return fail(CTCEXT_INVALID_ARGUMENT, "half-precision inputs need dtype float32");
+  if ((a->inputs_stride_t == 0) != (a->inputs_stride_b == 0))
+    return fail(CTCEXT_INVALID_ARGUMENT, "inputs_stride_t and inputs_stride_b must be given together");
+  if (a->inputs_stride_t != 0) {
+    if (a->max_time > 1 && a->inputs_stride_t < a->num_classes)
+      return fail(CTCEXT_INVALID_ARGUMENT, "inputs_stride_t is below num_classes");
+    if (a->batch_size > 1 && a->inputs_stride_b < a->num_classes)
+      return fail(CTCEXT_INVALID_ARGUMENT, "inputs_stride_b is below num_classes");
+  }
+  return CTCEXT_OK;
+}
+
 extern "C" int ctcext_validate(const ctcext_decode_args* a) {
   int rc = validate_shapes(a);
   if (rc != CTCEXT_OK) return rc;
@@ -370,6 +392,7 @@ extern "C" int ctcext_validate(const ctcext_decode_args* a) {
   }
   rc = check_limits(a);
   if (rc == CTCEXT_OK && !a->inputs_on_device) rc = check_table(a, a->scorer_table);
+  if (rc == CTCEXT_OK) rc = check_layout(a);
   if (rc == CTCEXT_OK) g_err.clear();
   return rc;
 }
@@ -402,10 +425,11 @@ static void shard_bounds(const std::vector<int32_t>& hsl, int n, std::vector<int
 }
 
 // Enqueues norm + decode + traceback of one shard on its device's stream.
-// x/sl point at the shard's first item; xstride is items per frame in x.
+// x/sl point at the shard's first item; x holds elements of xfmt
+// (CTCEXT_IN_*), row (t, b) of the shard xst_t * t + xst_b * b elements in.
 template <typename T>
-static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_decode_args* a, const T* x,
-                         int64_t xstride, const int32_t* sl, int helper_mode) {
+static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_decode_args* a, const void* x, int xfmt,
+                         int64_t xst_t, int64_t xst_b, const int32_t* sl, int helper_mode) {
   const int64_t T_ = a->max_time, C = a->num_classes, B = d->B, Bs = v.nb;
   const int W = a->beam_width, P = a->top_paths;
   const bool prof = (a->flags & CTCEXT_FLAG_PROFILE) != 0;
@@ -431,21 +455,33 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   }
 
   if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[0], s));
+  if (gs && xfmt != CTCEXT_IN_NATIVE && Bs > 0) {
+    // the global-state tier reads its rows in place, as T: a half shard is
+    // widened into workspace first (the slow catch-all tier; its kernels
+    // stay as they are)
+    HIP_OR_FAIL(v.xw.ensure(4 * (size_t)(T_ * Bs * C) + 16));
+    HIP_OR_FAIL(ctcx::launch_widen_rows(x, xfmt, (float*)v.xw.p, T_, Bs, C, xst_t, xst_b, s));
+    x = v.xw.p;
+    xfmt = CTCEXT_IN_NATIVE;
+    xst_t = Bs * C;
+    xst_b = C;
+  }
   if (!gs && C > 64) {
     // large C: the normaliser and the row facts the decode kernel reads per
     // frame, one parallel pre-pass
-    HIP_OR_FAIL(ctcx::launch_row_prep<T>(x, sl, (char*)v.prep.p, (T*)v.norm.p, T_, Bs, C, xstride,
+    HIP_OR_FAIL(ctcx::launch_row_prep<T>(x, xfmt, sl, (char*)v.prep.p, (T*)v.norm.p, T_, Bs, C, xst_t, xst_b,
                                          a->blank_index, s));
   } else {
-    HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, sl, (T*)v.norm.p, T_, Bs, C, xstride, s));
+    HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, xfmt, sl, (T*)v.norm.p, T_, Bs, C, xst_t, xst_b, s));
   }
   if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[1], s));
 
   ctcx::DecodeParams<T> p{};
-  p.x = x;
+  p.x = (const T*)x;
+  p.xfmt = xfmt;
   p.norm = (const T*)v.norm.p;
   p.seq_len = sl;
-  p.Tmax = T_; p.B = Bs; p.C = C; p.xstride = xstride;
+  p.Tmax = T_; p.B = Bs; p.C = C; p.xst_t = xst_t; p.xst_b = xst_b;
   p.W = W; p.P = P; p.blank = a->blank_index; p.blank_label = a->blank_label;
   // num_classes == 1 (the blank alone): no label is ever offered, and the
   // fast paths' offer arithmetic divides by C - 1, so every frame takes the
@@ -526,6 +562,15 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
   const int64_t T_ = a->max_time, B = a->batch_size, C = a->num_classes;
   const int P = a->top_paths;
   const int ts = (int)sizeof(T);
+  // the inputs' element size and element strides (both 0: the dense
+  // reference layout); the stride of a dimension of extent 1 addresses
+  // nothing, and takes the value a dense tensor would have
+  const size_t es = a->inputs_format == CTCEXT_IN_NATIVE ? (size_t)ts : 2;
+  int64_t st_t = a->inputs_stride_t ? a->inputs_stride_t : B * C;
+  int64_t st_b = a->inputs_stride_b ? a->inputs_stride_b : C;
+  if (T_ <= 1 && B <= 1) st_t = st_b = C;
+  else if (T_ <= 1) st_t = st_b * B;
+  else if (B <= 1) st_b = st_t * T_;
   const int nd = (int)d->devs.size();
   Dev& root = d->devs[0];
   std::vector<int64_t> lo;
@@ -539,38 +584,53 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
     v.s = (i == 0) ? root_stream : v.own_stream;
     if (v.nb == 0 && i > 0) continue;
     HIP_OR_FAIL(hipSetDevice(v.device));
-    const T* x;
+    const void* x;
     const int32_t* sl;
-    int64_t xstride;
-    if (i == 0 && a->inputs_on_device) {   // the root's shard is read in place
-      x = (const T*)a->inputs;
-      xstride = B;
+    int64_t xst_t = st_t, xst_b = st_b;
+    if (i == 0 && a->inputs_on_device) {   // the root's shard is read in place, through its strides
+      x = a->inputs;
       sl = a->sequence_length;
     } else if (v.nb == 0) {
       // an empty root shard (B < n_devices, no frames anywhere): nothing to
       // copy; enqueue_shard only sizes the root's whole-batch buffers and
       // launches no kernel over zero items
       x = nullptr;
-      xstride = 0;
+      xst_t = xst_b = 0;
       sl = nullptr;
     } else {
-      const size_t row = (size_t)v.nb * (size_t)C * ts;
-      HIP_OR_FAIL(v.x.ensure(row * (size_t)T_ + 16));
+      // the shard's items as a dense tensor on its device, in the inputs' own
+      // element type (halves stay 2 bytes on the way) and their own dimension
+      // order: [T][nb][C] from a time-major tensor, [nb][T][C] from a
+      // batch-major one, so that the copy is as few pieces as the strides allow
+      const size_t cb = (size_t)C * es;
+      HIP_OR_FAIL(v.x.ensure(cb * (size_t)v.nb * (size_t)T_ + 16));
       HIP_OR_FAIL(v.sl.ensure(4 * (size_t)v.nb + 16));
-      const char* src = (const char*)a->inputs + (size_t)v.lo * (size_t)C * ts;
-      if (v.nb == B) {
-        HIP_OR_FAIL(hipMemcpyAsync(v.x.p, src, row * (size_t)T_, hipMemcpyDefault, v.s));
+      const char* src = (const char*)a->inputs + (size_t)v.lo * (size_t)st_b * es;
+      const bool bmajor = st_t < st_b;
+      // outer dimension (extent no, source stride so) over inner (ni, si)
+      const int64_t no = bmajor ? v.nb : T_, ni = bmajor ? T_ : v.nb;
+      const int64_t so = bmajor ? st_b : st_t, si = bmajor ? st_t : st_b;
+      const size_t slab = cb * (size_t)ni;   // one outer index of the shard
+      if (si == C && (so == ni * C || no == 1)) {   // wholly contiguous
+        HIP_OR_FAIL(hipMemcpyAsync(v.x.p, src, slab * (size_t)no, hipMemcpyDefault, v.s));
+      } else if (si == C && so >= ni * C) {
+        // contiguous slabs (a [T][nb][C] window of a [T][B][C] tensor; the
+        // items of a batch-major tensor with padded frames): one pitched copy
+        HIP_OR_FAIL(hipMemcpy2DAsync(v.x.p, slab, src, (size_t)so * es, slab, (size_t)no, hipMemcpyDefault, v.s));
       } else {
-        // a [T][nb][C] window of the [T][B][C] tensor: T rows of nb*C values
-        HIP_OR_FAIL(hipMemcpy2DAsync(v.x.p, row, src, (size_t)B * (size_t)C * ts, row, (size_t)T_,
-                                     hipMemcpyDefault, v.s));
+        // rows apart in both dimensions (a vocabulary slice): one pitched
+        // copy of ni rows per outer index
+        for (int64_t o = 0; o < no; ++o)
+          HIP_OR_FAIL(hipMemcpy2DAsync((char*)v.x.p + (size_t)o * slab, cb, src + (size_t)o * (size_t)so * es,
+                                       (size_t)si * es, cb, (size_t)ni, hipMemcpyDefault, v.s));
       }
       HIP_OR_FAIL(hipMemcpyAsync(v.sl.p, hsl.data() + v.lo, 4 * (size_t)v.nb, hipMemcpyHostToDevice, v.s));
-      x = (const T*)v.x.p;
-      xstride = v.nb;
+      x = v.x.p;
+      xst_t = bmajor ? C : v.nb * C;
+      xst_b = bmajor ? T_ * C : C;
       sl = (const int32_t*)v.sl.p;
     }
-    int rc = enqueue_shard<T>(d, v, i == 0, a, x, xstride, sl, helper_mode);
+    int rc = enqueue_shard<T>(d, v, i == 0, a, x, a->inputs_format, xst_t, xst_b, sl, helper_mode);
     if (rc != CTCEXT_OK) return rc;
   }
 
@@ -692,6 +752,7 @@ extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args
       rc = check_table(a, a->scorer_table);
     }
   }
+  if (rc == CTCEXT_OK) rc = check_layout(a);
   if (rc != CTCEXT_OK) return rc;
 
   const int P = a->top_paths;

@@ -250,6 +250,87 @@ template <> struct __attribute__((aligned(16))) HE<double> { double v; int s; in
 typedef unsigned u32x2 __attribute__((ext_vector_type(2), may_alias));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4), may_alias));
 
+// Half-precision inputs (DecodeParams::xfmt): 2-byte elements in memory,
+// widened to float where a kernel reads them -- exact for both formats, so
+// everything downstream sees the values of the widened float tensor.
+//   fp16: the hardware convert (v_cvt_f32_f16; f16 denormals are never
+//         flushed, subnormals widen to their exact float value)
+//   bf16: the bits, 16 to the left
+struct F16 { uint16_t u; };
+struct BF16 { uint16_t u; };
+__device__ __forceinline__ float widen_f16(unsigned h) {
+  return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
+}
+__device__ __forceinline__ float widen_bf16(unsigned h) { return __uint_as_float(h << 16); }
+// element j of a row of E, as T (E = T: the element itself)
+template <typename T, typename E>
+__device__ __forceinline__ T ldw(const E* p, int64_t j) {
+  if constexpr (std::is_same<E, F16>::value) return widen_f16(p[j].u);
+  else if constexpr (std::is_same<E, BF16>::value) return widen_bf16(p[j].u);
+  else return p[j];
+}
+// a 32-bit word holding halves 2i (low) and 2i + 1 (high), as two floats' bits
+template <typename E>
+__device__ __forceinline__ void widen2(unsigned w, unsigned& lo, unsigned& hi) {
+  if constexpr (std::is_same<E, F16>::value) {
+    lo = __float_as_uint(widen_f16(w & 0xffffu));
+    hi = __float_as_uint(widen_f16(w >> 16));
+  } else {
+    lo = w << 16;
+    hi = w & 0xffff0000u;
+  }
+}
+
+// The decode kernel's row stage for half-precision rows: C 2-byte elements
+// at xr, widened into the LDS row (C float bit patterns, 16-byte aligned).
+// Rows of whole 16-byte pieces (C % 8 == 0, xr 16-byte aligned: the base and
+// both byte strides are then multiples of 16) move as 8 halves per load, a
+// batch of loads in flight per thread before the first LDS write; any other
+// row (an odd C leaves every other row start 2-byte aligned) element by element.
+// NT threads (the block) share the row.
+template <typename E>
+__device__ __forceinline__ void stage_row_half_t(CTCX_LDS unsigned* row, const uint16_t* xr, int C, int tid,
+                                                 int NT) {
+  if ((C & 7) == 0 && ((((uintptr_t)xr) | (uintptr_t)row) & 15) == 0) {
+    const u32x4* x8 = (const u32x4*)xr;
+    CTCX_LDS u32x4* r4 = (CTCX_LDS u32x4*)row;
+    const int C8 = C >> 3;
+    constexpr int kRB = 4;
+    for (int q0 = 0; q0 < C8; q0 += kRB * NT) {
+      u32x4 v[kRB];
+#pragma unroll
+      for (int u = 0; u < kRB; ++u) {
+        const int q = q0 + u * NT + tid;
+        if (q < C8) v[u] = x8[q];
+      }
+#pragma unroll
+      for (int u = 0; u < kRB; ++u) {
+        const int q = q0 + u * NT + tid;
+        if (q < C8) {
+          u32x4 a, b;
+          unsigned l, h;
+          widen2<E>(v[u][0], l, h); a[0] = l; a[1] = h;
+          widen2<E>(v[u][1], l, h); a[2] = l; a[3] = h;
+          widen2<E>(v[u][2], l, h); b[0] = l; b[1] = h;
+          widen2<E>(v[u][3], l, h); b[2] = l; b[3] = h;
+          r4[2 * q] = a;
+          r4[2 * q + 1] = b;
+        }
+      }
+    }
+  } else {
+    for (int j = tid; j < C; j += NT) row[j] = __float_as_uint(ldw<float>((const E*)xr, j));
+  }
+}
+// One out-of-line function for every decode kernel, as literal_step is: the
+// kernels' float path keeps its code (a uniform branch and a call are all the
+// frame loop gains), and the instantiations do not each carry a copy.
+__device__ __attribute__((noinline)) void stage_row_half(CTCX_LDS unsigned* row, const uint16_t* xr, int C,
+                                                         bool f16, int tid, int NT) {
+  if (f16) stage_row_half_t<F16>(row, xr, C, tid, NT);
+  else stage_row_half_t<BF16>(row, xr, C, tid, NT);
+}
+
 // Heap element loads/stores as single 8-byte (float) / 16-byte (double) LDS
 // accesses; a pair of siblings is one 16-byte (two for double) access.
 // (vector elements are copied to scalars before __builtin_bit_cast: clang
@@ -5061,11 +5142,17 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
 #endif
   for (int t = 0; t < sl; ++t) {
     uint64_t t0 = prof ? __builtin_amdgcn_s_memtime() : 0;
-    const T* xr = prm.x + ((int64_t)t * prm.xstride + b) * C;
+    // the row stage: the only read of x.  Row (t, b) starts xoff elements
+    // into x (elements of prm.xfmt); everything below works on the LDS copy
+    const int64_t xoff = (int64_t)t * prm.xst_t + (int64_t)b * prm.xst_b;
+    const T* xr = prm.x + xoff;
 #ifdef CTCX_GSTATE
-    cx.row = const_cast<T*>(xr);
+    cx.row = const_cast<T*>(xr);   // (read in place: the host hands this tier rows of T)
 #else
-    if constexpr (BIG && sizeof(T) == 4) {
+    if (sizeof(T) == 4 && prm.xfmt != kInNative) {   // uniform: half-precision rows, widened into the LDS row
+      if constexpr (sizeof(T) == 4)
+        stage_row_half((CTCX_LDS unsigned*)cx.row, (const uint16_t*)prm.x + xoff, C, prm.xfmt == kInF16, tid, NT);
+    } else if constexpr (BIG && sizeof(T) == 4) {
       // a large row: 16-byte loads, a batch of them in flight per thread
       // before the first LDS write (a load-store pair per element waited out
       // one global latency each: 16k cycles per cfg5 frame)
@@ -5495,10 +5582,12 @@ constexpr int kNormTile = CTCX_NORM_TILE;
 constexpr int kNormRPL = 64 / kNormTile;   // tile rows per load instruction
 constexpr int kNormNL = 64 / kNormRPL;     // load instructions per tile
 
-template <typename T>
-__global__ __launch_bounds__(64) void ctcx_row_norm(const T* __restrict__ x, const int32_t* seq_len,
+// E: the element type of x in memory (T itself, or F16 / BF16 with T = float:
+// widened as loaded, the arithmetic below is on the widened values)
+template <typename T, typename E = T>
+__global__ __launch_bounds__(64) void ctcx_row_norm(const E* __restrict__ x, const int32_t* seq_len,
                                                    T* __restrict__ norm, int64_t Tmax, int64_t B, int64_t C,
-                                                   int64_t xstride, const char* __restrict__ prep) {
+                                                   int64_t xst_t, int64_t xst_b, const char* __restrict__ prep) {
   __shared__ T tile[64][kNormTile + 1];   // [row in wave][class in tile], padded: conflict-free row reads
   __shared__ uint64_t etab[32];           // expf's 2^(i/32) table: the lanes' indices diverge
   const int lane = threadIdx.x;
@@ -5511,7 +5600,7 @@ __global__ __launch_bounds__(64) void ctcx_row_norm(const T* __restrict__ x, con
   if (row < rows) {
     const int64_t t = row / B, b = row - t * B;
     valid = t < seq_len[b];
-    if (valid) off = (t * xstride + b) * C;
+    if (valid) off = t * xst_t + b * xst_b;
   }
   const uint64_t vmask = __ballot(valid);
   if (vmask == 0) return;
@@ -5546,7 +5635,7 @@ __global__ __launch_bounds__(64) void ctcx_row_norm(const T* __restrict__ x, con
         const int64_t b0 = row_base(2 * q), b1 = row_base(2 * q + 1);
         base = sub ? b1 : b0;
       }
-      v[q] = x[base + cc];
+      v[q] = ldw<T>(x, base + cc);
     }
   };
   T v[kNormNL];
@@ -5599,12 +5688,14 @@ __global__ __launch_bounds__(64) void ctcx_row_norm(const T* __restrict__ x, con
 // aligned): the same 32-class tiles and class-order sums, moved as 16-byte
 // pieces -- a load instruction covers 8 rows (8 lanes x 16 B each), so 8 loads,
 // 8 LDS writes and 8 LDS reads per lane per tile instead of 32 of each, and
-// each lane's 8 row bases are fetched once, not per tile.
+// each lane's 8 row bases are fetched once, not per tile.  E = F16 / BF16:
+// the four classes of a piece are 8 bytes in memory (rows 8-byte aligned),
+// widened to the same float4.
 constexpr int kNormTileW4 = kNormTile + 4;   // 16-byte rows; 36 words apart, b128 row reads conflict-free
-template <int DUMMY = 0>
-__global__ __launch_bounds__(64) void ctcx_row_norm_v4(const float* __restrict__ x, const int32_t* seq_len,
+template <typename E = float>
+__global__ __launch_bounds__(64) void ctcx_row_norm_v4(const E* __restrict__ x, const int32_t* seq_len,
                                                       float* __restrict__ norm, int64_t Tmax, int64_t B, int64_t C,
-                                                      int64_t xstride, const char* __restrict__ prep) {
+                                                      int64_t xst_t, int64_t xst_b, const char* __restrict__ prep) {
   static_assert(kNormTile == 32, "8 lanes of 16 bytes per tile row");
   __shared__ __attribute__((aligned(16))) float tile[64][kNormTileW4];
   __shared__ uint64_t etab[32];
@@ -5617,7 +5708,7 @@ __global__ __launch_bounds__(64) void ctcx_row_norm_v4(const float* __restrict__
   if (row < rows) {
     const int64_t t = row / B, b = row - t * B;
     valid = t < seq_len[b];
-    if (valid) off = (t * xstride + b) * C;
+    if (valid) off = t * xst_t + b * xst_b;
   }
   if (__ballot(valid) == 0ull) return;
   float m = 0.f, s = 0.f;
@@ -5632,7 +5723,7 @@ __global__ __launch_bounds__(64) void ctcx_row_norm_v4(const float* __restrict__
   const bool le0 = __ballot(valid && !(known && m > -__builtin_inff())) == 0ull;
   // load q covers tile rows 8 q + sub, classes c4 .. c4 + 3 of the tile
   const int sub = lane >> 3, c4 = (lane & 7) * 4;
-  const float* base[8];
+  const E* base[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int src = 8 * q + sub;
@@ -5643,7 +5734,17 @@ __global__ __launch_bounds__(64) void ctcx_row_norm_v4(const float* __restrict__
   auto load = [&](float4 (&v)[8], int64_t c0) {
     const bool in = c4 < C - c0;   // (C - c0 is a multiple of 4)
 #pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = in ? *(const float4*)(base[q] + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = 0; q < 8; ++q) {
+      if constexpr (std::is_same<E, float>::value) {
+        v[q] = in ? *(const float4*)(base[q] + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        const u32x2 w = in ? *(const u32x2*)(base[q] + c0) : u32x2{0u, 0u};
+        unsigned f0, f1, f2, f3;
+        widen2<E>(w[0], f0, f1);
+        widen2<E>(w[1], f2, f3);
+        v[q] = make_float4(__uint_as_float(f0), __uint_as_float(f1), __uint_as_float(f2), __uint_as_float(f3));
+      }
+    }
   };
   float4 v[8];
   for (int pass = pass0 ? 0 : 1; pass < 2; ++pass) {
@@ -5759,10 +5860,10 @@ __device__ __forceinline__ unsigned fkey_sx(float v) {
   return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
 }
 
-template <typename T, bool INLDS>
-__global__ __launch_bounds__(64) void ctcx_row_prep(const T* __restrict__ x, const int32_t* __restrict__ seq_len,
+template <typename T, bool INLDS, typename E = T>
+__global__ __launch_bounds__(64) void ctcx_row_prep(const E* __restrict__ x, const int32_t* __restrict__ seq_len,
                                                    char* __restrict__ prep, T* __restrict__ norm, int64_t B,
-                                                   int64_t C, int64_t xstride, int blank) {
+                                                   int64_t C, int64_t xst_t, int64_t xst_b, int blank) {
   // LDS: the expf table (32 x 8 bytes), the staged row, the compact key list
   extern __shared__ __attribute__((aligned(16))) char plds[];
   uint64_t* etab = (uint64_t*)plds;
@@ -5773,7 +5874,7 @@ __global__ __launch_bounds__(64) void ctcx_row_prep(const T* __restrict__ x, con
   if (t >= seq_len[b]) return;
   const T NI = ninf<T>();
   const int Ci = (int)C;
-  const T* xr = x + (t * xstride + b) * C;
+  const E* xr = x + (t * xst_t + b * xst_b);   // (E = F16 / BF16: widened by every read below)
   char* pr = prep + row * (int64_t)prep_row_bytes(C, (int)sizeof(T));
   T* bm = (T*)(pr + prep_bmax_offset((int)sizeof(T)));
   const int nblk = (Ci + 63) / 64;
@@ -5785,7 +5886,7 @@ __global__ __launch_bounds__(64) void ctcx_row_prep(const T* __restrict__ x, con
 #pragma unroll
       for (int u = 0; u < kPrepBatch; ++u) {
         const int j = j0 + 64 * u + lane;
-        v[u] = j < Ci ? xr[j] : T(0);
+        v[u] = j < Ci ? ldw<T>(xr, j) : T(0);
       }
 #pragma unroll
       for (int u = 0; u < kPrepBatch; ++u) {
@@ -5795,7 +5896,7 @@ __global__ __launch_bounds__(64) void ctcx_row_prep(const T* __restrict__ x, con
     }
     __syncthreads();
   }
-  auto xat = [&](int j) -> T { return inlds ? xs[j] : xr[j]; };
+  auto xat = [&](int j) -> T { return inlds ? xs[j] : ldw<T>(xr, j); };
   // maximum, NaN / +inf, block maxima (block k: classes [64k, 64k + 64)),
   // and (float) the lane's largest non-blank key
   T xmax = NI, bmv = NI;
@@ -5957,7 +6058,7 @@ __global__ __launch_bounds__(64) void ctcx_row_prep(const T* __restrict__ x, con
       for (; j < Ci; ++j) ssum += xs[j];
     }
   } else if (lane == 0) {
-    for (int j = 0; j < Ci; ++j) ssum += norm_exp(xr[j] - m);
+    for (int j = 0; j < Ci; ++j) ssum += norm_exp(ldw<T>(xr, j) - m);
   }
   if (lane == 0) norm[row] = m + norm_log(ssum);
 }
@@ -6080,10 +6181,12 @@ constexpr int facts_rows_per_wave() { return (FUSE && NV <= 4) ? 2 : 1; }
 template <int NV>
 constexpr bool kFuseNorm = NV <= 4;
 
-template <int NV, bool FUSE>
+// E = F16 / BF16: the row's 2-byte elements, four per lane and load (8 bytes,
+// rows 8-byte aligned), widened into the same registers; all else as for float.
+template <int NV, bool FUSE, typename E = float>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CTCX_FACTS_WPE, 8))) void ctcx_row_facts(
-    const float* __restrict__ x, const int32_t* __restrict__ seq_len, char* __restrict__ prep, int64_t rows,
-    int64_t B, int C, int64_t xstride, int blank, float* __restrict__ norm) {
+    const E* __restrict__ x, const int32_t* __restrict__ seq_len, char* __restrict__ prep, int64_t rows,
+    int64_t B, int C, int64_t xst_t, int64_t xst_b, int blank, float* __restrict__ norm) {
   // per wave: the compact list of (key, label index) in label order, with one
   // dummy slot per lane (its stores are unconditional), and the radix histogram
   // (NV <= 4, C <= 1024: 16 keys per lane, bisected in registers as cheaply
@@ -6133,16 +6236,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CTCX_FACTS_
     rxmax[r] = NI;
     xbv[r] = 0.f;
     if (live[r]) {
-      const float4* xr = (const float4*)(x + (t * xstride + b) * (int64_t)C);
-      if constexpr (FUSE) xbv[r] = ((const float*)xr)[blank];
+      const E* xr = x + (t * xst_t + b * xst_b);
+      if constexpr (FUSE) xbv[r] = ldw<float>(xr, blank);
       // buffer loads: one lane offset and a constant row offset per load, no
       // 64-bit address per load in flight (those took 40 VGPRs at NV = 20); past
       // the row they return 0, replaced by -inf below
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)xr, (short)0, C * 4, 0x00020000);
+      // (the extent is the row's bytes: C * sizeof(E), a whole number of loads
+      // per lane since C % 4 == 0, so a load lies wholly inside or outside it)
+      const __amdgpu_buffer_rsrc_t rs =
+          __builtin_amdgcn_make_buffer_rsrc((void*)xr, (short)0, C * (int)sizeof(E), 0x00020000);
 #pragma unroll
       for (int u = 0; u < NV; ++u) {
-        const auto f = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, u * 1024, 0);
-        kr[r][u][0] = f[0]; kr[r][u][1] = f[1]; kr[r][u][2] = f[2]; kr[r][u][3] = f[3];
+        if constexpr (std::is_same<E, float>::value) {
+          const auto f = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, u * 1024, 0);
+          kr[r][u][0] = f[0]; kr[r][u][1] = f[1]; kr[r][u][2] = f[2]; kr[r][u][3] = f[3];
+        } else {
+          const auto f = __builtin_amdgcn_raw_buffer_load_b64(rs, lane * 8, u * 512, 0);
+          widen2<E>(f[0], kr[r][u][0], kr[r][u][1]);
+          widen2<E>(f[1], kr[r][u][2], kr[r][u][3]);
+        }
       }
     }
   }
@@ -6449,14 +6561,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CTCX_FACTS_
       if (live[r] && rbad[r] && lane == 0) {
         // the reference's order for both: maxCoeff's loop, then the sum
         const int64_t row = rrow[r], t = row / B, b = row - t * B;
-        const float* xr1 = x + (t * xstride + b) * (int64_t)C;
-        float m = xr1[0];
+        const E* xr1 = x + (t * xst_t + b * xst_b);
+        float m = ldw<float>(xr1, 0);
         for (int j = 1; j < C; ++j) {
-          const float v = xr1[j];
+          const float v = ldw<float>(xr1, j);
           m = (v > m) ? v : m;
         }
         float s1 = 0.f;
-        for (int j = 0; j < C; ++j) s1 += gm::expf_t(xr1[j] - m, etab);
+        for (int j = 0; j < C; ++j) s1 += gm::expf_t(ldw<float>(xr1, j) - m, etab);
         norm[row] = m + gm::logf(s1);
       }
     }
@@ -7021,24 +7133,24 @@ int ring_frames(const DecodeParams<T>& p, int cus, int cap, int hk) {
 template int ring_frames<float>(const DecodeParams<float>&, int, int, int);
 template int ring_frames<double>(const DecodeParams<double>&, int, int, int);
 
-template <int NV>
-static hipError_t launch_row_facts(const float* x, const int32_t* sl, char* prep, float* norm, int64_t rows,
-                                   int64_t B, int C, int64_t xstride, int blank, bool& fuse, hipStream_t s) {
+template <int NV, typename E>
+static hipError_t launch_row_facts(const E* x, const int32_t* sl, char* prep, float* norm, int64_t rows, int64_t B,
+                                   int C, int64_t xst_t, int64_t xst_b, int blank, bool& fuse, hipStream_t s) {
   // the normaliser fused for rows of up to 1024 classes only: past them the
   // block's class-order chain (C dependent adds per four rows) costs more than
   // the second read it saves (cfg5: 19.4 ms fused, 8.5 + 8.7 split)
   if constexpr (kFuseNorm<NV>) {
     if (fuse) {
       constexpr int nr = 4 * facts_rows_per_wave<NV, true>();
-      hipLaunchKernelGGL((ctcx_row_facts<NV, true>), dim3((unsigned)((rows + nr - 1) / nr)), dim3(256), 0, s, x, sl,
-                         prep, rows, B, C, xstride, blank, norm);
+      hipLaunchKernelGGL((ctcx_row_facts<NV, true, E>), dim3((unsigned)((rows + nr - 1) / nr)), dim3(256), 0, s, x,
+                         sl, prep, rows, B, C, xst_t, xst_b, blank, norm);
       return hipGetLastError();
     }
   }
   fuse = false;
   constexpr int nr = 4 * facts_rows_per_wave<NV, false>();
-  hipLaunchKernelGGL((ctcx_row_facts<NV, false>), dim3((unsigned)((rows + nr - 1) / nr)), dim3(256), 0, s, x, sl,
-                     prep, rows, B, C, xstride, blank, (float*)nullptr);
+  hipLaunchKernelGGL((ctcx_row_facts<NV, false, E>), dim3((unsigned)((rows + nr - 1) / nr)), dim3(256), 0, s, x, sl,
+                     prep, rows, B, C, xst_t, xst_b, blank, (float*)nullptr);
   return hipGetLastError();
 }
 
@@ -7061,21 +7173,25 @@ static bool prep_split() {
   return v;
 }
 
-template <typename T>
-hipError_t launch_row_prep(const T* x, const int32_t* sl, char* prep, T* norm, int64_t T_, int64_t B, int64_t C,
-                           int64_t xstride, int blank, hipStream_t s) {
+// The pre-pass over rows of E in memory (T itself, or F16 / BF16 with T =
+// float), row (t, b) at x + t * xst_t + b * xst_b.
+template <typename T, typename E>
+static hipError_t launch_row_prep_e(const E* x, const int32_t* sl, char* prep, T* norm, int64_t T_, int64_t B,
+                                    int64_t C, int64_t xst_t, int64_t xst_b, int blank, hipStream_t s) {
   const int64_t rows = T_ * B;
   if (rows == 0 || C <= 64) return hipSuccess;
   if constexpr (sizeof(T) == 4) {
-    // float rows of whole float4s (16-byte aligned): the register-resident
-    // row facts, with the normaliser from the same registers (one read) where
-    // that pays, else followed by ctcx_row_norm
-    if (C % 4 == 0 && ((uintptr_t)x & 15) == 0 && C <= 256 * 32) {   // NV <= 32 float4 per lane
+    // float rows of whole four-class pieces, every row start aligned to a
+    // piece (16 bytes of float, 8 of a half format: the base and both
+    // strides): the register-resident row facts, with the normaliser from the
+    // same registers (one read) where that pays, else followed by ctcx_row_norm
+    const bool pieces = C % 4 == 0 && ((uintptr_t)x & (4 * sizeof(E) - 1)) == 0 && xst_t % 4 == 0 && xst_b % 4 == 0;
+    if (pieces && C <= 256 * 32) {   // NV <= 32 pieces per lane
       const int c4 = (int)(C / 4);
       bool fuse = !prep_split();   // (cleared by the launcher where it does not fuse)
       float* nf = (float*)norm;
       hipError_t e;
-#define CTCX_FACTS(NV) launch_row_facts<NV>(x, sl, prep, nf, rows, B, (int)C, xstride, blank, fuse, s)
+#define CTCX_FACTS(NV) launch_row_facts<NV, E>(x, sl, prep, nf, rows, B, (int)C, xst_t, xst_b, blank, fuse, s)
       if (c4 <= 64) e = CTCX_FACTS(1);
       else if (c4 <= 128) e = CTCX_FACTS(2);
       else if (c4 <= 256) e = CTCX_FACTS(4);
@@ -7088,49 +7204,104 @@ hipError_t launch_row_prep(const T* x, const int32_t* sl, char* prep, T* norm, i
 #undef CTCX_FACTS
       if (e != hipSuccess || fuse) return e;
       if (norm_v4())
-        hipLaunchKernelGGL(ctcx_row_norm_v4<>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, sl, nf, T_, B,
-                           C, xstride, (const char*)prep);
+        hipLaunchKernelGGL(ctcx_row_norm_v4<E>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, sl, nf, T_, B,
+                           C, xst_t, xst_b, (const char*)prep);
       else
-        hipLaunchKernelGGL(ctcx_row_norm<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, sl, norm, T_, B,
-                           C, xstride, (const char*)prep);
+        hipLaunchKernelGGL((ctcx_row_norm<T, E>), dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, sl, norm,
+                           T_, B, C, xst_t, xst_b, (const char*)prep);
       return hipGetLastError();
     }
   }
-  const size_t row_b = (size_t)C * sizeof(T);
+  const size_t row_b = (size_t)C * sizeof(T);   // (staged widened)
   // the expf table, the row, then the compact key list
   const size_t lds = kPrepTabBytes + ((row_b + 15) & ~(size_t)15) + 4 * kPrepCompact;
   if (row_b > kPrepLdsBytes) {   // the row is read from global memory
-    hipLaunchKernelGGL((ctcx_row_prep<T, false>), dim3((unsigned)rows), dim3(64), kPrepTabBytes + 4 * kPrepCompact,
-                       s, x, sl, prep, norm, B, C, xstride, blank);
+    hipLaunchKernelGGL((ctcx_row_prep<T, false, E>), dim3((unsigned)rows), dim3(64),
+                       kPrepTabBytes + 4 * kPrepCompact, s, x, sl, prep, norm, B, C, xst_t, xst_b, blank);
     return hipGetLastError();
   }
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)ctcx_row_prep<T, true>,
+    hipError_t e = hipFuncSetAttribute((const void*)ctcx_row_prep<T, true, E>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((ctcx_row_prep<T, true>), dim3((unsigned)rows), dim3(64), lds, s, x, sl, prep, norm, B, C,
-                     xstride, blank);
+  hipLaunchKernelGGL((ctcx_row_prep<T, true, E>), dim3((unsigned)rows), dim3(64), lds, s, x, sl, prep, norm, B, C,
+                     xst_t, xst_b, blank);
   return hipGetLastError();
 }
-template hipError_t launch_row_prep<float>(const float*, const int32_t*, char*, float*, int64_t, int64_t, int64_t,
-                                           int64_t, int, hipStream_t);
-template hipError_t launch_row_prep<double>(const double*, const int32_t*, char*, double*, int64_t, int64_t,
-                                            int64_t, int64_t, int, hipStream_t);
+
+// x holds elements of xfmt (kInNative: of T; the half formats with T = float only)
+template <typename T>
+hipError_t launch_row_prep(const void* x, int xfmt, const int32_t* sl, char* prep, T* norm, int64_t T_, int64_t B,
+                           int64_t C, int64_t xst_t, int64_t xst_b, int blank, hipStream_t s) {
+  if constexpr (sizeof(T) == 4) {
+    if (xfmt == kInF16)
+      return launch_row_prep_e<T, F16>((const F16*)x, sl, prep, norm, T_, B, C, xst_t, xst_b, blank, s);
+    if (xfmt == kInBF16)
+      return launch_row_prep_e<T, BF16>((const BF16*)x, sl, prep, norm, T_, B, C, xst_t, xst_b, blank, s);
+  }
+  if (xfmt != kInNative) return hipErrorInvalidValue;
+  return launch_row_prep_e<T, T>((const T*)x, sl, prep, norm, T_, B, C, xst_t, xst_b, blank, s);
+}
+template hipError_t launch_row_prep<float>(const void*, int, const int32_t*, char*, float*, int64_t, int64_t, int64_t,
+                                           int64_t, int64_t, int, hipStream_t);
+template hipError_t launch_row_prep<double>(const void*, int, const int32_t*, char*, double*, int64_t, int64_t,
+                                            int64_t, int64_t, int64_t, int, hipStream_t);
 
 template <typename T>
-hipError_t launch_row_norm(const T* x, const int32_t* sl, T* norm, int64_t T_, int64_t B, int64_t C,
-                           int64_t xstride, hipStream_t s) {
+hipError_t launch_row_norm(const void* x, int xfmt, const int32_t* sl, T* norm, int64_t T_, int64_t B, int64_t C,
+                           int64_t xst_t, int64_t xst_b, hipStream_t s) {
   const int64_t rows = T_ * B;
   if (rows == 0) return hipSuccess;
-  hipLaunchKernelGGL(ctcx_row_norm<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, sl, norm, T_, B, C,
-                     xstride, (const char*)nullptr);
+  const dim3 grid((unsigned)((rows + 63) / 64));
+  if (sizeof(T) == 4 && xfmt == kInF16) {
+    if constexpr (sizeof(T) == 4)
+      hipLaunchKernelGGL((ctcx_row_norm<T, F16>), grid, dim3(64), 0, s, (const F16*)x, sl, norm, T_, B, C, xst_t,
+                         xst_b, (const char*)nullptr);
+  } else if (sizeof(T) == 4 && xfmt == kInBF16) {
+    if constexpr (sizeof(T) == 4)
+      hipLaunchKernelGGL((ctcx_row_norm<T, BF16>), grid, dim3(64), 0, s, (const BF16*)x, sl, norm, T_, B, C, xst_t,
+                         xst_b, (const char*)nullptr);
+  } else if (xfmt != kInNative) {
+    return hipErrorInvalidValue;
+  } else {
+    hipLaunchKernelGGL((ctcx_row_norm<T, T>), grid, dim3(64), 0, s, (const T*)x, sl, norm, T_, B, C, xst_t, xst_b,
+                       (const char*)nullptr);
+  }
   return hipGetLastError();
 }
-template hipError_t launch_row_norm<float>(const float*, const int32_t*, float*, int64_t, int64_t, int64_t, int64_t,
-                                           hipStream_t);
-template hipError_t launch_row_norm<double>(const double*, const int32_t*, double*, int64_t, int64_t, int64_t,
-                                            int64_t, hipStream_t);
+template hipError_t launch_row_norm<float>(const void*, int, const int32_t*, float*, int64_t, int64_t, int64_t,
+                                           int64_t, int64_t, hipStream_t);
+template hipError_t launch_row_norm<double>(const void*, int, const int32_t*, double*, int64_t, int64_t, int64_t,
+                                            int64_t, int64_t, hipStream_t);
+
+// Half-precision rows (t, b) at x + t * xst_t + b * xst_b, widened into the
+// dense float tensor out[T_][B][C]: the global-state tier reads its rows in
+// place, as floats, so the host widens a half shard into workspace first.
+template <typename E>
+__global__ __launch_bounds__(256) void ctcx_widen_rows(const E* __restrict__ x, float* __restrict__ out, int64_t B,
+                                                      int64_t C, int64_t xst_t, int64_t xst_b) {
+  const int64_t row = blockIdx.x;
+  const int64_t t = row / B, b = row - t * B;
+  const E* xr = x + (t * xst_t + b * xst_b);
+  float* o = out + row * C;
+  for (int64_t j = threadIdx.x; j < C; j += 256) o[j] = ldw<float>(xr, j);
+}
+hipError_t launch_widen_rows(const void* x, int xfmt, float* out, int64_t T_, int64_t B, int64_t C, int64_t xst_t,
+                             int64_t xst_b, hipStream_t s) {
+  const int64_t rows = T_ * B;
+  if (rows == 0 || C == 0) return hipSuccess;
+  if (rows > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (xfmt == kInF16)
+    hipLaunchKernelGGL(ctcx_widen_rows<F16>, dim3((unsigned)rows), dim3(256), 0, s, (const F16*)x, out, B, C, xst_t,
+                       xst_b);
+  else if (xfmt == kInBF16)
+    hipLaunchKernelGGL(ctcx_widen_rows<BF16>, dim3((unsigned)rows), dim3(256), 0, s, (const BF16*)x, out, B, C,
+                       xst_t, xst_b);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 
 hipError_t launch_traceback(const TraceParams& tp, hipStream_t s) {
   const int64_t n = tp.B * tp.P * 2;

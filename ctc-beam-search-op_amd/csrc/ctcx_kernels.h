@@ -119,11 +119,11 @@ __host__ __device__ inline size_t prep_top_offset(int64_t C, int tsize) {
 
 template <typename T>
 struct DecodeParams {
-  const T* x;               // row (t, b) at x + (t * xstride + b) * C
+  const T* x;               // row (t, b) at element t * xst_t + b * xst_b (elements of xfmt: 2 bytes for the halves)
   const T* norm;            // [Tmax][B]  softmax normaliser per row
   const int32_t* seq_len;   // [B]
   int64_t Tmax, B, C;
-  int64_t xstride;          // items per frame in x (B, or the full batch for a shard read in place)
+  int64_t xst_t, xst_b;     // element strides of the frame and item dimensions of x (class stride 1)
   int32_t W, P, blank, blank_label;
   int32_t force_literal;    // testing knob: replay every frame literally
   Rec* rec;                 // [B][Tmax][W]
@@ -150,7 +150,10 @@ struct DecodeParams {
   // traceback's record format all follow this one value
   int32_t helper;
   int32_t test_flags;       // kTestHelperDead: the helper wave starts out "timed out" (tests only)
+  int32_t xfmt;             // kInNative (elements of T), kInF16, kInBF16 (T = float; widened by the row stage)
 };
+// element formats of x (= CTCEXT_IN_*)
+constexpr int32_t kInNative = 0, kInF16 = 1, kInBF16 = 2;
 constexpr int32_t kTestHelperDead = 1;
 // helper_kind's modes and the record size of a two-wave kernel kind (4-byte
 // Rec32 records: the score table, and the scored queue at C <= 64)

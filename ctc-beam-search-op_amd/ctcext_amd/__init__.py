@@ -4,8 +4,8 @@ tracking; a drop-in for prouast/ctc-beam-search-op's
 """
 from .ops import (CTCExtBeamSearchDecoder, Decoder, FailedPreconditionError, InternalError,
                   InvalidArgumentError, OpError, UnimplementedError, ctc_ext_beam_search_decoder,
-                  get_decoder)
+                  decode_logits, get_decoder)
 
-__all__ = ["ctc_ext_beam_search_decoder", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder",
+__all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

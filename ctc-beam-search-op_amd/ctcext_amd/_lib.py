@@ -28,7 +28,10 @@ CTCEXT_FLAG_RING_MIN = 32      # testing: the record ring at 8 frames (short ite
 CTCEXT_FLAG_NO_RING = 64       # every beam record to HBM (the ring is the default for the score-table kernel)
 CTCEXT_FLAG_HELPER_STRICT = 128     # a helper hand-over timeout fails the call instead of a one-wave re-decode
 CTCEXT_FLAG_TEST_HELPER_DEAD = 256  # testing: the helper wave starts out timed out
-CTCEXT_ABI_VERSION = 6
+CTCEXT_ABI_VERSION = 7
+CTCEXT_IN_NATIVE = 0   # inputs_format: elements of dtype
+CTCEXT_IN_F16 = 1      # float16 in memory, widened to float32 by the kernels (dtype CTCEXT_F32)
+CTCEXT_IN_BF16 = 2     # bfloat16, likewise
 CTCEXT_SCORER_BASE = 0
 CTCEXT_SCORER_BIGRAM = 1
 
@@ -50,7 +53,10 @@ class DecodeArgs(ctypes.Structure):
                 ("stream", ctypes.c_void_p),
                 ("inputs_dims", ctypes.c_int32), ("sequence_length_dims", ctypes.c_int32),
                 ("sequence_length_size", ctypes.c_int64),
-                ("scorer", ctypes.c_int32), ("pad_", ctypes.c_int32), ("scorer_table", ctypes.c_void_p)]
+                ("scorer", ctypes.c_int32), ("pad_", ctypes.c_int32), ("scorer_table", ctypes.c_void_p),
+                # ABI 7 (all zero: the dense [max_time, batch, num_classes] tensor of dtype)
+                ("inputs_format", ctypes.c_int32), ("pad2_", ctypes.c_int32),
+                ("inputs_stride_t", ctypes.c_int64), ("inputs_stride_b", ctypes.c_int64)]
 
 
 class PathSizes(ctypes.Structure):

@@ -234,12 +234,7 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
             _type_error("inputs", str(inputs.dtype).replace("torch.", ""), "float32, float64")
         x = inputs.contiguous()
         dev = x.device
-        if _is_torch(sequence_length):
-            if sequence_length.dtype.is_floating_point:
-                _type_error("sequence_length", str(sequence_length.dtype).replace("torch.", ""), "int32")
-            sl = sequence_length.to(device=dev, dtype=torch.int32).contiguous()
-        else:
-            sl = torch.as_tensor(np.asarray(sequence_length, dtype=np.int32), device=dev)
+        sl = _lengths_device(sequence_length, dev)
         keep += [x, sl]
         shape, sl_shape = tuple(x.shape), tuple(sl.shape)
         code = _lib.CTCEXT_F32 if x.dtype == torch.float32 else _lib.CTCEXT_F64
@@ -249,18 +244,13 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
     else:
         if _is_torch(inputs):
             inputs = inputs.detach().cpu().numpy()
-        if _is_torch(sequence_length):
-            sequence_length = sequence_length.detach().cpu().numpy()
         if isinstance(inputs, np.ndarray):
             if inputs.dtype not in (np.float32, np.float64):
                 _type_error("inputs", inputs.dtype.name, "float32, float64")
             x = np.ascontiguousarray(inputs)
         else:   # Python numbers convert to float32, as tf.convert_to_tensor does
             x = np.ascontiguousarray(np.asarray(inputs, dtype=np.float32))
-        sl_arr = np.asarray(sequence_length)
-        if sl_arr.dtype.kind == "f":
-            _type_error("sequence_length", sl_arr.dtype.name, "int32")
-        sl = np.ascontiguousarray(sl_arr.astype(np.int32))
+        sl = _lengths_host(sequence_length)
         keep += [x, sl]
         shape, sl_shape = x.shape, sl.shape
         code = _lib.CTCEXT_F32 if x.dtype == np.float32 else _lib.CTCEXT_F64
@@ -269,6 +259,135 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
         stream = None
     a = _args(x_ptr, shape, code, on_device, sl_ptr, sl_shape, beam_width, top_paths, merge_repeated,
               blank_index, blank_label, flags, stream)
+    return _decode_and_fetch(lib, a, keep, shape, on_device, x.device if on_device else None,
+                             x.dtype if on_device else np.dtype(x.dtype), index, outputs, devices, scorer_table)
+
+
+def logits_layout(shape, strides, batch_first=True):
+    """The stride/contiguity decision of ``decode_logits``, on plain numbers:
+    ``shape`` and ``strides`` (in elements) of a 3-D logits tensor, batch-major
+    ``[B, T, C]`` with ``batch_first`` else time-major ``[T, B, C]``.
+
+    Returns ``(copy, (max_time, batch, num_classes), stride_t, stride_b)``.
+    ``copy`` is False when the C ABI can address the tensor in place: classes
+    contiguous (``strides[-1] == 1``) and, on every dimension of extent > 1, a
+    stride of at least ``num_classes`` (an expanded or reversed view has to be
+    materialised).  With ``copy`` the strides returned are those of the dense
+    copy in the same dimension order; the stride of a dimension of extent 1
+    is the dense one."""
+    d0, d1, C = (int(v) for v in shape)
+    s0, s1, sc = (int(v) for v in strides)
+    copy = sc != 1 or (d0 > 1 and s0 < C) or (d1 > 1 and s1 < C)
+    if copy:
+        s0, s1 = d1 * C, C
+    elif d0 <= 1 and d1 <= 1:
+        s0 = s1 = C
+    elif d1 <= 1:
+        s1 = C
+    elif d0 <= 1:
+        s0 = d1 * s1
+    if batch_first:
+        return copy, (d1, d0, C), s1, s0
+    return copy, (d0, d1, C), s0, s1
+
+
+def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
+                  merge_repeated=False, blank_index=0, blank_label=-1,
+                  flags=0, outputs="auto", devices=None, scorer_table=None):
+    """Decode the logits tensor an acoustic model produces, as it is.
+
+    ``logits`` is a torch tensor of dtype float16, bfloat16, float32 or
+    float64, on the GPU or the host, or a numpy float16 / float32 / float64
+    array; ``[B, T, C]`` with ``batch_first`` (the default), else ``[T, B, C]``.
+    It may be a view (a vocabulary slice, a transpose, a padded batch): when
+    its classes are contiguous (``logits.stride(-1) == 1``) the kernels read
+    it in place through its strides and nothing is copied or converted;
+    otherwise it is made contiguous first.  Half-precision logits are widened
+    to float32 as the kernels read them, which is exact: the result is that of
+    ``ctc_ext_beam_search_decoder(logits.float().transpose(0, 1), ...)``, and
+    ``log_probability`` is float32.  The other arguments and the returned
+    ``CTCExtBeamSearchDecoder`` tuple are the drop-in function's.
+    """
+    if outputs not in ("auto", "host", "device"):
+        raise ValueError("outputs must be 'auto', 'host' or 'device'")
+    lib = _lib.load()
+    allowed = "float16, bfloat16, float32, float64"
+    if _is_torch(logits):
+        import torch
+        formats = {torch.float16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+                   torch.bfloat16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_BF16),
+                   torch.float32: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+                   torch.float64: (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+        if logits.dtype not in formats:
+            _type_error("logits", str(logits.dtype).replace("torch.", ""), allowed)
+        x = logits.detach()
+        strides = x.stride()
+    else:
+        x = logits if isinstance(logits, np.ndarray) else np.asarray(logits, dtype=np.float32)
+        formats = {np.dtype(np.float16): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+                   np.dtype(np.float32): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+                   np.dtype(np.float64): (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+        if x.dtype not in formats:
+            _type_error("logits", x.dtype.name, allowed)
+        strides = tuple(s // x.itemsize if s % x.itemsize == 0 else 0 for s in x.strides)
+    code, fmt = formats[x.dtype]
+    if len(x.shape) == 3:
+        copy, shape, st_t, st_b = logits_layout(tuple(x.shape), strides, batch_first)
+        if copy:
+            x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
+    else:   # the C ABI raises the reference's "inputs is not a 3-Tensor"
+        x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
+        shape, st_t, st_b = tuple(x.shape), 0, 0
+    on_device = _is_torch(x) and x.is_cuda
+    if on_device:
+        dev = x.device
+        sl = _lengths_device(lengths, dev)
+        x_ptr, sl_ptr = x.data_ptr(), sl.data_ptr()
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        table_dtype = torch.float32 if code == _lib.CTCEXT_F32 else torch.float64
+    else:
+        dev = None
+        sl = _lengths_host(lengths)
+        # (a CPU torch tensor is read where it lies: numpy has no bfloat16)
+        x_ptr, sl_ptr = (x.data_ptr() if _is_torch(x) else x.ctypes.data), sl.ctypes.data
+        index = stream = None
+        table_dtype = np.dtype(np.float32 if code == _lib.CTCEXT_F32 else np.float64)
+    a = _args(x_ptr, shape, code, on_device, sl_ptr, tuple(sl.shape), beam_width, top_paths, merge_repeated,
+              blank_index, blank_label, flags, stream)
+    a.inputs_format = fmt
+    a.inputs_stride_t, a.inputs_stride_b = int(st_t), int(st_b)
+    return _decode_and_fetch(lib, a, [x, sl], shape, on_device, dev, table_dtype, index, outputs, devices,
+                             scorer_table)
+
+
+def _lengths_device(sequence_length, dev):
+    """sequence_length as a contiguous int32 tensor on dev."""
+    import torch
+    if _is_torch(sequence_length):
+        if sequence_length.dtype.is_floating_point:
+            _type_error("sequence_length", str(sequence_length.dtype).replace("torch.", ""), "int32")
+        return sequence_length.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.as_tensor(np.asarray(sequence_length, dtype=np.int32), device=dev)
+
+
+def _lengths_host(sequence_length):
+    """sequence_length as a contiguous int32 numpy array."""
+    if _is_torch(sequence_length):
+        sequence_length = sequence_length.detach().cpu().numpy()
+    sl_arr = np.asarray(sequence_length)
+    if sl_arr.dtype.kind == "f":
+        _type_error("sequence_length", sl_arr.dtype.name, "int32")
+    return np.ascontiguousarray(sl_arr.astype(np.int32))
+
+
+def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index, outputs, devices, scorer_table):
+    """Everything after the inputs are described by ``a``: validation, the
+    beam-scorer table, the handle, phase 1, output allocation and phase 2.
+    ``shape`` is the logical (max_time, batch, num_classes); ``table_dtype``
+    the compute dtype (torch for device inputs, numpy for host inputs), in
+    which the scorer table is passed and log_probability comes back."""
+    code, top_paths = a.dtype, a.top_paths
     # the reference's shape/length checks run behind the C ABI, before any
     # device work (kernels.cc:97-139)
     rc = lib.ctcext_validate(ctypes.byref(a))
@@ -278,11 +397,12 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
         C = int(shape[2]) if len(shape) == 3 else 0
         if on_device:
             import torch
-            tab = torch.as_tensor(scorer_table, device=x.device, dtype=x.dtype).contiguous()
+            tab = torch.as_tensor(scorer_table, device=device, dtype=table_dtype).contiguous()
             a.scorer_table = tab.data_ptr()
         else:
             tab = np.ascontiguousarray(np.asarray(
-                scorer_table.detach().cpu().numpy() if _is_torch(scorer_table) else scorer_table, dtype=x.dtype))
+                scorer_table.detach().cpu().numpy() if _is_torch(scorer_table) else scorer_table,
+                dtype=table_dtype))
             a.scorer_table = tab.ctypes.data
         if tuple(tab.shape) != (C + 1, C):
             raise ValueError("scorer_table must be [num_classes + 1, num_classes] = [%d, %d], got %s"
@@ -300,6 +420,13 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
         dec = get_decoder(devs if len(devs) > 1 else devs[0])
     else:
         dec = get_decoder(index if index is not None else _current_device())
+    if on_device and not a.stream:
+        # torch's legacy default stream has handle 0, which the C ABI reads as
+        # "the decoder's own (non-blocking) stream": work still pending on the
+        # default stream (the kernels that produce the logits) would not be
+        # waited for, so it is, here
+        import torch
+        torch.cuda.current_stream(device).synchronize()
     sizes = dec.decode(a)
     P = int(top_paths)
     B = int(shape[1])

@@ -39,6 +39,14 @@ enum {
 
 enum { CTCEXT_F32 = 0, CTCEXT_F64 = 1 };   /* attr T: {float, double} (ops.cc:24) */
 
+/* Element type of the inputs in memory (ctcext_decode_args.inputs_format).
+ * dtype stays the compute and output type; a half format needs CTCEXT_F32:
+ * the kernels widen each element to float as they read it (exact for both
+ * formats), so the outputs are those of decoding the widened float tensor. */
+enum { CTCEXT_IN_NATIVE = 0,   /* elements of dtype */
+       CTCEXT_IN_F16 = 1,      /* IEEE binary16 */
+       CTCEXT_IN_BF16 = 2 };   /* bfloat16 */
+
 /* Beam scorer (util/ctc_beam_scorer.h:31-65).  The reference op always uses
  * BaseBeamScorer (kernels.cc:260), the identity; the decoder exposes the hook
  * (ctc_ext_beam_search_decoder.h:43-45, 103, 114, 171-182, 226).
@@ -74,8 +82,10 @@ enum {
  *   4: ctcext_stats.record_bytes, .helper     5: .helper_redecodes,
  *      ctcext_get_stats_sized, ctcext_abi_version, the HELPER_STRICT flag
  *   6: ctcext_get_stats fills the ABI-4 prefix only (fields since: _sized);
- *      ctcext_phase_counters' layout is [batch][32] */
-#define CTCEXT_ABI_VERSION 6
+ *      ctcext_phase_counters' layout is [batch][32]
+ *   7: ctcext_decode_args.inputs_format, .inputs_stride_t, .inputs_stride_b
+ *      (appended; zero = the dense [max_time, batch, num_classes] tensor of dtype) */
+#define CTCEXT_ABI_VERSION 7
 
 typedef struct ctcext_decoder ctcext_decoder;
 
@@ -86,7 +96,8 @@ typedef struct {
   int32_t dtype;                   /* CTCEXT_F32 / CTCEXT_F64 */
   int32_t inputs_on_device;        /* 1: inputs/sequence_length are device (HBM) pointers
                                       on the decoder's (root) device */
-  const void* inputs;              /* [max_time, batch_size, num_classes] row-major */
+  const void* inputs;              /* [max_time, batch_size, num_classes] row-major (or as
+                                      inputs_format / inputs_stride_* below say) */
   const int32_t* sequence_length;  /* [batch_size] */
   int64_t max_time, batch_size, num_classes;   /* inputs.dim_size(0..2) (0 past the rank) */
   int32_t beam_width;              /* attr beam_width >= 1 */
@@ -103,6 +114,17 @@ typedef struct {
   int32_t scorer;                  /* CTCEXT_SCORER_* (0: the reference op's BaseBeamScorer) */
   int32_t pad_;
   const void* scorer_table;        /* CTCEXT_SCORER_BIGRAM: [num_classes + 1][num_classes] */
+  /* ABI 7.  All zero: today's dense tensor of dtype (callers that zero the
+   * struct, or were written before these fields, need no change). */
+  int32_t inputs_format;           /* CTCEXT_IN_*: the element type inputs points at */
+  int32_t pad2_;
+  int64_t inputs_stride_t;         /* element strides of the frame and the item dimension */
+  int64_t inputs_stride_b;         /*   (the class stride is 1): element (t, b, c) is at
+                                      inputs[t * stride_t + b * stride_b + c].  Both 0: the
+                                      dense reference layout (batch * num_classes,
+                                      num_classes); dense batch-major [B, T, C] is
+                                      (num_classes, max_time * num_classes).  Device inputs
+                                      are read in place through the strides */
 } ctcext_decode_args;
 
 /* Per top path p: sizes of decoded_indices[p] ([num_decoded, 2]),
@@ -175,7 +197,13 @@ int ctcext_create_sharded(const int* devices, int n_devices, ctcext_decoder** ou
  * library's attribute checks, on the host only (no HIP call, no handle): the
  * messages are the reference's verbatim and come in its order.  The
  * sequence_length values (kernels.cc:134-139) are checked here only when they
- * are host memory (inputs_on_device == 0); ctcext_decode checks them always. */
+ * are host memory (inputs_on_device == 0); ctcext_decode checks them always.
+ * After all of those, the ABI-7 fields (CTCEXT_INVALID_ARGUMENT each):
+ *   "inputs_format must be CTCEXT_IN_NATIVE, CTCEXT_IN_F16 or CTCEXT_IN_BF16"
+ *   "half-precision inputs need dtype float32"
+ *   "inputs_stride_t and inputs_stride_b must be given together"
+ *   "inputs_stride_t is below num_classes"   (max_time > 1 only)
+ *   "inputs_stride_b is below num_classes"   (batch_size > 1 only) */
 int ctcext_validate(const ctcext_decode_args* args);
 
 /* Phase 1 (Compute up to the allocation of the outputs).  Synchronous. */
