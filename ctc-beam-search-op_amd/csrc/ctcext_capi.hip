@@ -130,6 +130,7 @@ struct Dev {
   int ring = 0;              // this call's record-ring frames (ctcx::ring_frames)
   int rec_bytes = 8;         // this call's record size (8, 16 or 4 bytes)
   int helper = 0;            // this call's two-wave kernel (ctcx::use_helper_kernel)
+  int kernel = 0;            // this call's kernels as its launchers noted them (ctcext_stats.kernel)
   int cus = 0;               // compute units of the device
 };
 
@@ -260,6 +261,8 @@ extern "C" int ctcext_row_facts(ctcext_decoder* d, const void* x, int32_t dtype,
   DeviceGuard guard;
   HIP_OR_FAIL(hipSetDevice(r.device));
   const hipStream_t st = r.own_stream;
+  int* note = ctcx_launch_note();
+  note[1] = 0;
   if (dtype == CTCEXT_F64)
     HIP_OR_FAIL(ctcx::launch_row_prep<double>(x, ctcx::kInNative, seq_len, (char*)prep, (double*)norm, max_time,
                                               batch, num_classes, batch * num_classes, num_classes, blank_index,
@@ -268,6 +271,7 @@ extern "C" int ctcext_row_facts(ctcext_decoder* d, const void* x, int32_t dtype,
     HIP_OR_FAIL(ctcx::launch_row_prep<float>(x, ctcx::kInNative, seq_len, (char*)prep, (float*)norm, max_time, batch,
                                              num_classes, batch * num_classes, num_classes, blank_index, st));
   HIP_OR_FAIL(hipStreamSynchronize(st));
+  d->stats.kernel = note[1] << 12;
   return CTCEXT_OK;
 }
 
@@ -435,6 +439,9 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   const bool prof = (a->flags & CTCEXT_FLAG_PROFILE) != 0;
   const int64_t Bo = root ? B : Bs;   // the root's walk buffers hold the whole batch
   hipStream_t s = v.s;
+  v.kernel = 0;
+  int* note = ctcx_launch_note();   // (the launchers below run on this thread)
+  note[0] = note[1] = note[2] = 0;
   HIP_OR_FAIL(v.norm.ensure(sizeof(T) * (size_t)(T_ * Bs)));
   HIP_OR_FAIL(v.rec.ensure(sizeof(ctcx::Rec) * (size_t)(Bs * T_ * W)));
   HIP_OR_FAIL(v.item.ensure(sizeof(ctcx::ItemOut) * (size_t)Bo));
@@ -552,6 +559,7 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   tp.len = (int32_t*)v.len.p;
   tp.len_stride = Bo;
   HIP_OR_FAIL(ctcx::launch_traceback(tp, s));
+  v.kernel = note[0] | (note[1] << 12) | (note[2] << 16);
   if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[3], s));
   return CTCEXT_OK;
 }
@@ -676,6 +684,7 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
   d->stats.ring_frames = root.ring;
   d->stats.record_bytes = root.rec_bytes;
   d->stats.helper = root.helper;
+  d->stats.kernel = root.kernel;
   if (a->flags & CTCEXT_FLAG_PROFILE) {
     for (int i = 0; i < nd; ++i) {
       Dev& v = d->devs[(size_t)i];

@@ -6889,6 +6889,7 @@ hipError_t launch_decode_c(const DecodeParams<T>& p, hipStream_t s) {
   }
   hipLaunchKernelGGL((ctcx_beam_decode<T, RN, WC, BIG, SC, HW, SQ>), dim3((unsigned)p.B), dim3(HW ? 128 : 64), lds,
                      s, p);
+  ctcx_launch_note()[0] = ctcx_decode_kernel_id(false, (int)sizeof(T), SC::kStateful, RN, WC, BIG, HW, SQ);
   return hipGetLastError();
 }
 
@@ -7144,6 +7145,7 @@ static hipError_t launch_row_facts(const E* x, const int32_t* sl, char* prep, fl
       constexpr int nr = 4 * facts_rows_per_wave<NV, true>();
       hipLaunchKernelGGL((ctcx_row_facts<NV, true, E>), dim3((unsigned)((rows + nr - 1) / nr)), dim3(256), 0, s, x,
                          sl, prep, rows, B, C, xst_t, xst_b, blank, norm);
+      ctcx_launch_note()[1] = kPrepFactsFused;
       return hipGetLastError();
     }
   }
@@ -7203,6 +7205,7 @@ static hipError_t launch_row_prep_e(const E* x, const int32_t* sl, char* prep, T
       else e = CTCX_FACTS(32);
 #undef CTCX_FACTS
       if (e != hipSuccess || fuse) return e;
+      ctcx_launch_note()[1] = kPrepFactsNorm;
       if (norm_v4())
         hipLaunchKernelGGL(ctcx_row_norm_v4<E>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, x, sl, nf, T_, B,
                            C, xst_t, xst_b, (const char*)prep);
@@ -7218,6 +7221,7 @@ static hipError_t launch_row_prep_e(const E* x, const int32_t* sl, char* prep, T
   if (row_b > kPrepLdsBytes) {   // the row is read from global memory
     hipLaunchKernelGGL((ctcx_row_prep<T, false, E>), dim3((unsigned)rows), dim3(64),
                        kPrepTabBytes + 4 * kPrepCompact, s, x, sl, prep, norm, B, C, xst_t, xst_b, blank);
+    ctcx_launch_note()[1] = kPrepRowGlobal;
     return hipGetLastError();
   }
   if (lds > 64 * 1024) {
@@ -7227,6 +7231,7 @@ static hipError_t launch_row_prep_e(const E* x, const int32_t* sl, char* prep, T
   }
   hipLaunchKernelGGL((ctcx_row_prep<T, true, E>), dim3((unsigned)rows), dim3(64), lds, s, x, sl, prep, norm, B, C,
                      xst_t, xst_b, blank);
+  ctcx_launch_note()[1] = kPrepRowLds;
   return hipGetLastError();
 }
 
@@ -7268,6 +7273,7 @@ hipError_t launch_row_norm(const void* x, int xfmt, const int32_t* sl, T* norm, 
     hipLaunchKernelGGL((ctcx_row_norm<T, T>), grid, dim3(64), 0, s, (const T*)x, sl, norm, T_, B, C, xst_t, xst_b,
                        (const char*)nullptr);
   }
+  ctcx_launch_note()[1] = kPrepNormOnly;
   return hipGetLastError();
 }
 template hipError_t launch_row_norm<float>(const void*, int, const int32_t*, float*, int64_t, int64_t, int64_t,
@@ -7313,9 +7319,11 @@ hipError_t launch_traceback(const TraceParams& tp, hipStream_t s) {
   const char* ev = getenv("CTCEXT_TRACEBACK");
   if (2 * (int64_t)tp.P <= 256 && (int64_t)tp.W * rb <= kTbBufBytes - 16 && !(ev && ev[0] == '0')) {
     hipLaunchKernelGGL(ctcx_traceback_seg, dim3((unsigned)tp.B), dim3(256), 0, s, tp);
+    ctcx_launch_note()[2] = kTbSegmented;
     return hipGetLastError();
   }
   hipLaunchKernelGGL(ctcx_traceback, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tp);
+  ctcx_launch_note()[2] = kTbOneThread;
   return hipGetLastError();
 }
 
@@ -7346,6 +7354,7 @@ namespace ctcx {
 template <typename T, class SC>
 static hipError_t launch_decode_gs_t(const DecodeParams<T>& p, hipStream_t s) {
   hipLaunchKernelGGL((ctcx_beam_decode<T, 1, 0, false, SC, false>), dim3((unsigned)p.B), dim3(64), 0, s, p);
+  ctcx_launch_note()[0] = ctcx_decode_kernel_id(true, (int)sizeof(T), SC::kStateful, 1, 0, false, false, false);
   return hipGetLastError();
 }
 }  // namespace ctcx

@@ -13,6 +13,23 @@
 #define CTCX_LDS __attribute__((address_space(3)))
 #endif
 
+// What the launchers of this thread last ran, for ctcext_stats.kernel
+// (include/ctcext.h, CTCEXT_KERNEL_*): [0] the decode kernel's bits 0..11,
+// [1] the pre-pass, [2] the traceback.  Written by the launchers themselves
+// (ctcx_decode.hip, every compilation of it), read by ctcext_capi.hip.  One
+// object per thread for the whole library (an inline function's static).
+inline int* ctcx_launch_note() {
+  static thread_local int note[3];
+  return note;
+}
+constexpr int ctcx_decode_kernel_id(bool gstate, int tsize, bool scored, int RN, int WC, bool BIG, bool HW, bool SQ) {
+  return (HW ? 1 : 0) | (SQ ? 2 : 0) | (RN << 2) | ((WC / 128) << 5) | (BIG ? 0x80 : 0) | (scored ? 0x100 : 0) |
+         (tsize == 8 ? 0x200 : 0) | (gstate ? 0x400 : 0) | 0x800;
+}
+// (= CTCEXT_PREPASS_*, CTCEXT_TRACEBACK_*)
+constexpr int kPrepFactsFused = 1, kPrepFactsNorm = 2, kPrepRowLds = 3, kPrepRowGlobal = 4, kPrepNormOnly = 5;
+constexpr int kTbSegmented = 1, kTbOneThread = 2;
+
 namespace ctcx {
 
 // CTCEXT_FLAG_PHASES counters per item: 0 row load, 1 recursion, 2 grow,

@@ -28,7 +28,7 @@ CTCEXT_FLAG_RING_MIN = 32      # testing: the record ring at 8 frames (short ite
 CTCEXT_FLAG_NO_RING = 64       # every beam record to HBM (the ring is the default for the score-table kernel)
 CTCEXT_FLAG_HELPER_STRICT = 128     # a helper hand-over timeout fails the call instead of a one-wave re-decode
 CTCEXT_FLAG_TEST_HELPER_DEAD = 256  # testing: the helper wave starts out timed out
-CTCEXT_ABI_VERSION = 7
+CTCEXT_ABI_VERSION = 8
 CTCEXT_IN_NATIVE = 0   # inputs_format: elements of dtype
 CTCEXT_IN_F16 = 1      # float16 in memory, widened to float32 by the kernels (dtype CTCEXT_F32)
 CTCEXT_IN_BF16 = 2     # bfloat16, likewise
@@ -83,7 +83,21 @@ class Stats(ctypes.Structure):
                 ("traceback_ms", ctypes.c_double), ("n_devices", ctypes.c_int32),
                 ("tier", ctypes.c_int32), ("ring_frames", ctypes.c_int32),
                 ("records_written", ctypes.c_int64), ("record_bytes", ctypes.c_int32),
-                ("helper", ctypes.c_int32), ("helper_redecodes", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+                ("helper", ctypes.c_int32), ("helper_redecodes", ctypes.c_int32), ("kernel", ctypes.c_int32)]
+
+
+# ctcext_stats.kernel (include/ctcext.h, CTCEXT_KERNEL_*)
+PREPASS_NAMES = ("none", "facts_fused", "facts_norm", "row_prep_lds", "row_prep_global", "norm_only")
+TRACEBACK_NAMES = ("none", "segmented", "one_thread")
+
+
+def decode_kernel_stat(k):
+    """The named fields of ctcext_stats.kernel: which decode kernel
+    instantiation, pre-pass and traceback the library's launchers ran."""
+    return {"launched": bool(k & 0x800), "tier": (k >> 10) & 1, "dtype": "f64" if k & 0x200 else "f32",
+            "scorer": "bigram" if k & 0x100 else "base", "RN": (k >> 2) & 7, "WC": ((k >> 5) & 3) * 128,
+            "BIG": bool(k & 0x80), "helper": "SQ" if k & 2 else "HW" if k & 1 else "none",
+            "prepass": PREPASS_NAMES[(k >> 12) & 7], "traceback": TRACEBACK_NAMES[(k >> 16) & 3]}
 
 
 _lib = None

@@ -108,7 +108,11 @@ class Decoder:
     def stats(self):
         s = _lib.Stats()
         _lib.get_stats(self.lib, self.handle, s)
-        return {k: getattr(s, k) for k, _ in _lib.Stats._fields_ if k != "pad_"}
+        st = {k: getattr(s, k) for k, _ in _lib.Stats._fields_}
+        # "kernel" decoded into named fields (the raw value stays as "kernel_raw")
+        st["kernel_raw"] = st["kernel"]
+        st["kernel"] = _lib.decode_kernel_stat(st["kernel_raw"])
+        return st
 
     # -- phase 1 ---------------------------------------------------------
     def decode(self, args):

@@ -84,8 +84,9 @@ enum {
  *   6: ctcext_get_stats fills the ABI-4 prefix only (fields since: _sized);
  *      ctcext_phase_counters' layout is [batch][32]
  *   7: ctcext_decode_args.inputs_format, .inputs_stride_t, .inputs_stride_b
- *      (appended; zero = the dense [max_time, batch, num_classes] tensor of dtype) */
-#define CTCEXT_ABI_VERSION 7
+ *      (appended; zero = the dense [max_time, batch, num_classes] tensor of dtype)
+ *   8: ctcext_stats.kernel (the former pad_: same size and offsets) */
+#define CTCEXT_ABI_VERSION 8
 
 typedef struct ctcext_decoder ctcext_decoder;
 
@@ -174,8 +175,46 @@ typedef struct {
   int32_t helper_redecodes;        /* last decode: 1 if a two-wave kernel's hand-over wait ran
                                       out of time and the call was decoded again with the
                                       one-wave kernels (helper is then 0) */
-  int32_t pad_;
+  int32_t kernel;                  /* last decode, root device: the kernels its launchers ran
+                                      (CTCEXT_KERNEL_* below); after ctcext_row_facts, the
+                                      pre-pass field alone */
 } ctcext_stats;
+
+/* ctcext_stats.kernel.  Each launcher records what it launched, so the value
+ * is the dispatcher's own choice, not a second copy of its rules:
+ *   bit 0       HW: a two-wave decode kernel (128 threads per item)
+ *   bit 1       SQ: ... its scored gather queue
+ *   bits 2..4   RN: heap registers per lane (1, 2, 4)
+ *   bits 5..6   WC / 128: the compile-time beam capacity (128, 256; 0: the
+ *               layout is carved from the run-time beam_width)
+ *   bit 7       BIG: the num_classes > 64 build
+ *   bit 8       the bigram beam scorer (0: BaseBeamScorer)
+ *   bit 9       double (0: float)
+ *   bit 10      the global-state tier's kernel (ctcext_stats.tier == 1)
+ *   bit 11      a decode kernel was launched
+ *   bits 12..14 the pre-pass, CTCEXT_PREPASS_*
+ *   bits 16..17 the traceback, CTCEXT_TRACEBACK_* */
+#define CTCEXT_KERNEL_HW 0x1
+#define CTCEXT_KERNEL_SQ 0x2
+#define CTCEXT_KERNEL_RN(k) (((k) >> 2) & 7)
+#define CTCEXT_KERNEL_WC(k) ((((k) >> 5) & 3) * 128)
+#define CTCEXT_KERNEL_BIG 0x80
+#define CTCEXT_KERNEL_BIGRAM 0x100
+#define CTCEXT_KERNEL_F64 0x200
+#define CTCEXT_KERNEL_GSTATE 0x400
+#define CTCEXT_KERNEL_LAUNCHED 0x800
+#define CTCEXT_KERNEL_DECODE_MASK 0xfff
+#define CTCEXT_KERNEL_PREPASS(k) (((k) >> 12) & 7)
+#define CTCEXT_KERNEL_TRACEBACK(k) (((k) >> 16) & 3)
+enum { CTCEXT_PREPASS_NONE = 0,
+       CTCEXT_PREPASS_FACTS_FUSED = 1,    /* ctcx_row_facts with the normaliser (one read) */
+       CTCEXT_PREPASS_FACTS_NORM = 2,     /* ctcx_row_facts, then a row-norm kernel */
+       CTCEXT_PREPASS_ROW_PREP_LDS = 3,   /* ctcx_row_prep, the row staged in LDS */
+       CTCEXT_PREPASS_ROW_PREP_GLOBAL = 4,/* ctcx_row_prep, the row read from global memory */
+       CTCEXT_PREPASS_NORM_ONLY = 5 };    /* ctcx_row_norm (num_classes <= 64, global-state tier) */
+enum { CTCEXT_TRACEBACK_NONE = 0,
+       CTCEXT_TRACEBACK_SEGMENTED = 1,    /* ctcx_traceback_seg: one block per item */
+       CTCEXT_TRACEBACK_ONE_THREAD = 2 }; /* ctcx_traceback: one thread per walk */
 
 /* Handle lifetime.  A handle owns a HIP stream and a grow-only device
  * workspace; it is not thread-safe (use one per thread, like an OpKernel).

@@ -40,7 +40,7 @@ def _validate(a):
 
 
 def test_abi_version_and_constants():
-    assert _lib.CTCEXT_ABI_VERSION == 7 == _lib.load().ctcext_abi_version()
+    assert _lib.CTCEXT_ABI_VERSION == 8 == _lib.load().ctcext_abi_version()
     assert (_lib.CTCEXT_IN_NATIVE, _lib.CTCEXT_IN_F16, _lib.CTCEXT_IN_BF16) == (0, 1, 2)
     # appended: every earlier field keeps its offset
     assert _lib.DecodeArgs.inputs_format.offset > _lib.DecodeArgs.scorer_table.offset

@@ -1,0 +1,283 @@
+"""Every compiled decode kernel against the oracle, one pytest id per
+instantiation, and the edges of the LDS tier.
+
+libctcext.so holds 40 one-wave instantiations of ctcx_beam_decode<T, RN, WC,
+BIG, scorer>, six two-wave ones and the four global-state builds;
+launch_decode (ctcx_decode.hip) picks one from dtype, scorer, C > 64, the beam
+range and whether the compile-time layout fits the LDS.  ctcext_stats.kernel
+(written by the launchers themselves) says which one a call ran: each cell
+below decodes three input kinds through the public op, compares all seven
+outputs bit-exactly with the oracle, and asserts that the kernel that ran is
+the cell's.  TABLE lists every instantiation; test_every_instantiation_is_accounted_for
+holds it to the build.
+
+The second half walks the edges of the LDS tier (8196 < C <= ~38500 float,
+300 < C <= ~19500 double), where the carve is within bytes of the 160 KB
+limit: the widest beam of the tier and one past it, the two-wave layouts'
+last fitting class counts, the record ring behind a run-time-W layout.  LDS
+accesses past the allocation do not fault, so a disagreement between the
+kernel's carve and decode_lds_bytes shows only as wrong outputs, here.
+"""
+import zlib
+
+import numpy as np
+import pytest
+
+import ctcext_amd
+from ctcext_amd import _lib
+from parity_util import compare
+import oracle
+
+pytestmark = pytest.mark.gpu
+
+GS = _lib.CTCEXT_FLAG_GLOBAL_STATE
+F32, F64 = "f32", "f64"
+NP = {F32: np.float32, F64: np.float64}
+CODE = {F32: _lib.CTCEXT_F32, F64: _lib.CTCEXT_F64}
+
+
+def _row(dtype, scorer, RN, WC, BIG, helper="none", tier=0):
+    return (tier, dtype, scorer, RN, WC, BIG, helper)
+
+
+# One-wave shapes (T, C, W, P) by (RN, WC, BIG): the smallest that reach the
+# instantiation.  WC = 0 with BIG needs a class count at which the
+# compile-time layout (128 or 256 beams) no longer fits the LDS.
+SMALL = {(1, 128, False): (30, 20, 100, 5), (2, 256, False): (30, 20, 200, 5), (4, 0, False): (30, 20, 400, 5),
+         (1, 128, True): (20, 300, 100, 5), (2, 256, True): (20, 300, 200, 5), (4, 0, True): (20, 300, 400, 5)}
+
+# id -> (row, [(T, C, W, P), ...], CTCEXT_HELPER or None, flags).  Every shape
+# of a cell runs all three input kinds unless it names its own.
+CELLS = {}
+
+
+def _cell(name, row, shapes, helper_env="0", flags=0, kinds=None):
+    CELLS[name] = (row, shapes, helper_env, flags, kinds)
+
+
+for _dt in (F32, F64):
+    for _sc in ("base", "bigram"):
+        for (_rn, _wc, _big), _shape in SMALL.items():
+            if _dt == F64 and _sc == "bigram" and (_rn, _wc, _big) == (4, 0, False):
+                _shape = (30, 20, 380, 5)   # two branch buffers, 8-byte values and the scorer states: 400 is past the LDS
+            _cell("%s_%s_rn%d_wc%d_%s" % (_dt, _sc, _rn, _wc, "big" if _big else "small"),
+                  _row(_dt, _sc, _rn, _wc, _big), [_shape])
+# the widest beams and the tie grid at a second class count, float
+_cell("f32_base_rn4_wc0_big_c130_ties", _row(F32, "base", 4, 0, True), [(20, 130, 300, 5)], kinds=("ties",))
+_cell("f32_base_rn4_wc0_big_w512_p200", _row(F32, "base", 4, 0, True), [(20, 300, 512, 200)])
+# the run-time-W layouts: the class count at which 128 (256) beams no longer fit
+_cell("f32_base_rn1_wc0_big", _row(F32, "base", 1, 0, True), [(8, 33000, 100, 3)])
+_cell("f32_base_rn1_wc0_big_c38000", _row(F32, "base", 1, 0, True), [(8, 38000, 8, 3)])   # the last beams of the tier
+_cell("f32_base_rn2_wc0_big", _row(F32, "base", 2, 0, True), [(8, 26000, 200, 3)])
+_cell("f64_base_rn1_wc0_big", _row(F64, "base", 1, 0, True), [(8, 15000, 100, 3)])
+_cell("f64_base_rn2_wc0_big", _row(F64, "base", 2, 0, True), [(8, 10500, 200, 3)])
+# ... with the bigram scorer, whose state arrays move those class counts down
+# and whose (C + 1) x C table is 0.6 to 3.9 GB there: a mostly-zero table
+# (_bigram_table) keeps each decode under a second
+_cell("f32_bigram_rn1_wc0_big", _row(F32, "bigram", 1, 0, True), [(8, 31400, 100, 3)])
+# (T = 4: a frame the -inf kind sends down the literal path takes ~2 s at this C x W with the scorer)
+_cell("f32_bigram_rn2_wc0_big", _row(F32, "bigram", 2, 0, True), [(4, 24100, 200, 3)])
+_cell("f64_bigram_rn1_wc0_big", _row(F64, "bigram", 1, 0, True), [(8, 14300, 100, 3)])
+_cell("f64_bigram_rn2_wc0_big", _row(F64, "bigram", 2, 0, True), [(8, 9000, 200, 3)])
+# the two-wave kernels (float, the base scorer): the score table and the
+# gather queue (CTCEXT_HELPER=1, and the default for beams of 129..256), the
+# scored queue (the default up to 128 beams; CTCEXT_HELPER=4 above)
+_cell("f32_hw_rn1_wc128_small", _row(F32, "base", 1, 128, False, "HW"), [SMALL[(1, 128, False)]], helper_env="1")
+_cell("f32_hw_rn1_wc128_big", _row(F32, "base", 1, 128, True, "HW"), [SMALL[(1, 128, True)]], helper_env="1")
+_cell("f32_hw_rn2_wc256_big", _row(F32, "base", 2, 256, True, "HW"), [SMALL[(2, 256, True)]], helper_env=None)
+_cell("f32_sq_rn1_wc128_small", _row(F32, "base", 1, 128, False, "SQ"), [SMALL[(1, 128, False)]], helper_env=None)
+_cell("f32_sq_rn1_wc128_big", _row(F32, "base", 1, 128, True, "SQ"), [SMALL[(1, 128, True)]], helper_env=None)
+_cell("f32_sq_rn2_wc256_big", _row(F32, "base", 2, 256, True, "SQ"), [SMALL[(2, 256, True)]], helper_env="4")
+# the global-state tier's four builds
+for _dt in (F32, F64):
+    for _sc in ("base", "bigram"):
+        _cell("gstate_%s_%s" % (_dt, _sc), _row(_dt, _sc, 1, 0, False, tier=1), [(10, 8, 40, 3)], flags=GS)
+
+# Every instantiation of the build: CTCX_DECODE_INSTANCES (40 one-wave), the
+# six two-wave kernels and the four global-state ones -> ("covered", cell id),
+# ("unreachable", why) or ("exempt", why; none today).
+TABLE = {}
+for _dt in (F32, F64):
+    for _sc in ("base", "bigram"):
+        for _rn, _wc in ((1, 128), (1, 0), (2, 256), (2, 0), (4, 0)):
+            for _big in (False, True):
+                _name = "%s_%s_rn%d_wc%d_%s" % (_dt, _sc, _rn, _wc, "big" if _big else "small")
+                _r = _row(_dt, _sc, _rn, _wc, _big)
+                if _wc == 0 and _rn < 4 and not _big:
+                    TABLE[_r] = ("unreachable", "C <= 64 always fits the compile-time layout of %d beams" % (128 * _rn))
+                else:
+                    TABLE[_r] = ("covered", _name)
+for _name in ("f32_hw_rn1_wc128_small", "f32_hw_rn1_wc128_big", "f32_hw_rn2_wc256_big", "f32_sq_rn1_wc128_small",
+              "f32_sq_rn1_wc128_big", "f32_sq_rn2_wc256_big", "gstate_f32_base", "gstate_f32_bigram",
+              "gstate_f64_base", "gstate_f64_bigram"):
+    TABLE[CELLS[_name][0]] = ("covered", _name)
+
+KINDS = {"normal": dict(merge_repeated=False, blank_index=0),
+         "ties": dict(merge_repeated=True, blank_index=None),    # (None: C // 2, a non-zero blank)
+         "neg_inf": dict(merge_repeated=True, blank_index=0)}
+
+_observed = set()
+
+
+def _stat_row(k):
+    return (k["tier"], k["dtype"], k["scorer"], k["RN"], k["WC"], k["BIG"], k["helper"])
+
+
+def _stats():
+    return ctcext_amd.get_decoder(0).last_stats
+
+
+def _inputs(rng, kind, T, C, dtype):
+    x = rng.standard_normal((T, 2, C))
+    if kind == "ties":
+        x = np.round(x * 2) / 2
+    elif kind == "neg_inf":
+        x[rng.random(x.shape) < 0.15] = -np.inf
+    return x.astype(NP[dtype])
+
+
+def _bigram_table(rng, C, dtype):
+    """-abs(normal) * 2 entries; past 5000 classes (a table of gigabytes) only
+    the root's row and every seventh row after it are non-zero, each entry the
+    sum of a row and a column term: the rest of the table is never written,
+    so building it stays cheap, and the expansions of one beam in seven are
+    still penalised."""
+    if C <= 5000:
+        return (-np.abs(rng.standard_normal((C + 1, C))) * 2).astype(NP[dtype])
+    tab = np.zeros((C + 1, C), NP[dtype])
+    ra = np.abs(rng.standard_normal(((C + 7) // 7, 1))).astype(NP[dtype])
+    rb = np.abs(rng.standard_normal((1, C))).astype(NP[dtype])
+    np.negative(ra + rb, out=tab[::7])
+    return tab
+
+
+def _decode_both(x, sl, W, P, kw, tab=None, flags=0, want_ref=True):
+    """The op's outputs and the oracle's for one input; the oracle must not
+    fail (an error on both sides would stand in for a comparison)."""
+    ref = oracle.decode(x, sl, W, P, scorer_table=tab, **kw) if want_ref else None
+    out = ctcext_amd.ctc_ext_beam_search_decoder(x, sl, W, P, flags=flags, scorer_table=tab, **kw)
+    return out, ref
+
+
+def _run_cell(name, monkeypatch, kinds=None, want_ref=True):
+    row, shapes, helper_env, flags, own_kinds = CELLS[name]
+    tier, dtype, scorer = row[:3]
+    if helper_env is None:
+        monkeypatch.delenv("CTCEXT_HELPER", raising=False)
+    else:
+        monkeypatch.setenv("CTCEXT_HELPER", helper_env)
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    for (T, C, W, P) in shapes:
+        sl = np.array([T, max(T - 3, 1)], np.int32)
+        assert P >= 2
+        if tier == 0 and scorer == "base":
+            # the shape is inside the LDS tier by the library's own limit
+            assert W <= ctcext_amd.get_decoder(0).lib.ctcext_max_beam_width(C, CODE[dtype]), (C, W)
+        tab = _bigram_table(rng, C, dtype) if scorer == "bigram" else None
+        for kind in kinds or own_kinds or sorted(KINDS):
+            kw = dict(KINDS[kind])
+            if kw["blank_index"] is None:
+                kw["blank_index"] = C // 2
+            x = _inputs(rng, kind, T, C, dtype)
+            try:
+                out, ref = _decode_both(x, sl, W, P, kw, tab, flags, want_ref)
+            except (oracle.OracleError, ctcext_amd.OpError) as e:
+                raise AssertionError("%s %s C=%d W=%d: %s" % (name, kind, C, W, e))
+            k = _stats()["kernel"]
+            assert k["launched"] and _stat_row(k) == row, (name, kind, (T, C, W, P), k)
+            assert _stats()["tier"] == tier
+            _observed.add(row)
+            if ref is not None:
+                compare(out, ref, P, lp_exact=True)
+
+
+@pytest.mark.parametrize("name", sorted(CELLS))
+def test_instantiation_matches_oracle(name, monkeypatch):
+    _run_cell(name, monkeypatch)
+
+
+def test_every_instantiation_is_accounted_for(monkeypatch):
+    """40 one-wave + 6 two-wave + 4 global-state rows; every one is covered by
+    a cell above (its kernel id seen in this session, or by running the cell's
+    first kind here), except the eight rows no shape reaches (WC = 0 at C <=
+    64 below RN = 4: 128 and 256 beams always fit there).  "exempt" is open to
+    the four bigram rows that need a table of gigabytes only; none uses it."""
+    assert len(TABLE) == 50
+    by = {}
+    for row, (mark, _) in TABLE.items():
+        by.setdefault(mark, []).append(row)
+    assert set(by) <= {"covered", "exempt", "unreachable"}
+    by.setdefault("exempt", [])
+    lib = ctcext_amd.get_decoder(0).lib
+    for dtype in (F32, F64):
+        assert lib.ctcext_max_beam_width(64, CODE[dtype]) >= 256
+    assert len(by["unreachable"]) == 8
+    for (tier, dtype, scorer, RN, WC, BIG, helper) in by["unreachable"]:
+        assert tier == 0 and WC == 0 and not BIG and RN in (1, 2) and helper == "none"
+    assert len(by["exempt"]) <= 4
+    for (tier, dtype, scorer, RN, WC, BIG, helper) in by["exempt"]:
+        assert tier == 0 and scorer == "bigram" and WC == 0 and BIG and RN in (1, 2)
+    assert len(by["covered"]) == 50 - 8 - len(by["exempt"])
+    for row in by["covered"]:
+        cell = TABLE[row][1]
+        assert CELLS[cell][0] == row
+        if row not in _observed:
+            _run_cell(cell, monkeypatch, kinds=(CELLS[cell][4] or ("normal",))[:1], want_ref=False)
+        assert row in _observed, cell
+    # and no cell claims a row outside the table
+    assert {c[0] for c in CELLS.values()} == set(by["covered"])
+
+
+# ---- the LDS tier's edges
+
+def _edge_case(C, W, dtype, kinds=("normal", "ties"), flags=0, T=6, P=2, seed=0):
+    """Parity of a [T, 2, C] decode at beam W for each kind; returns the stats
+    of the last one (the same kernel for every kind)."""
+    rng = np.random.default_rng(50000 + C + W + seed)
+    sl = np.array([T, max(T - 3, 1)], np.int32)
+    for kind in kinds:
+        kw = dict(KINDS[kind])
+        if kw["blank_index"] is None:
+            kw["blank_index"] = C // 2
+        x = _inputs(rng, kind, T, C, dtype)
+        out, ref = _decode_both(x, sl, W, P, kw, flags=flags)
+        compare(out, ref, P, lp_exact=True)
+    return _stats()
+
+
+@pytest.mark.parametrize("dtype,C", [(F32, 20000), (F32, 30000), (F32, 35000), (F32, 38000),
+                                     (F64, 29), (F64, 5000), (F64, 10000), (F64, 15000)])
+def test_lds_tier_exactly_full(dtype, C):
+    # the widest beam the LDS tier takes (the carve at or within bytes of the
+    # 160 KB), then one more: the global-state tier
+    W = ctcext_amd.get_decoder(0).lib.ctcext_max_beam_width(C, CODE[dtype])
+    assert W >= 2
+    st = _edge_case(C, W, dtype)
+    assert st["tier"] == 0 and st["kernel"]["tier"] == 0 and st["kernel"]["launched"], st
+    st = _edge_case(C, W + 1, dtype)
+    assert st["tier"] == 1 and st["kernel"]["tier"] == 1, st
+
+
+@pytest.mark.parametrize("C,W,helper", [(30000, 100, 3), (31000, 100, 0), (24000, 200, 2), (24900, 200, 0)])
+def test_two_wave_layout_fallback(C, W, helper, monkeypatch):
+    # the two-wave layout (the decode carve plus the helper's queue) stops
+    # fitting before the one-wave one does: the host falls back to one wave
+    monkeypatch.delenv("CTCEXT_HELPER", raising=False)
+    st = _edge_case(C, W, F32)
+    print("C=%d W=%d helper=%d kernel=%s" % (C, W, st["helper"], st["kernel"]))
+    assert st["tier"] == 0
+    assert st["helper"] == helper, st
+    assert st["kernel"]["helper"] == {0: "none", 2: "HW", 3: "SQ"}[helper], st
+
+
+def test_ring_behind_run_time_layout():
+    # C = 33000: 128 beams do not fit, the layout is carved from W itself
+    st = _edge_case(33000, 60, F32, flags=_lib.CTCEXT_FLAG_RING_MIN)
+    assert st["tier"] == 0 and st["ring_frames"] == 8, st
+    assert st["kernel"]["WC"] == 0, st
+
+
+def test_ring_dropped_when_the_layout_fills_the_lds():
+    W = ctcext_amd.get_decoder(0).lib.ctcext_max_beam_width(33000, _lib.CTCEXT_F32)
+    st = _edge_case(33000, W, F32, flags=_lib.CTCEXT_FLAG_RING_MIN)
+    assert st["tier"] == 0 and st["ring_frames"] == 0, st

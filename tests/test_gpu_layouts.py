@@ -33,6 +33,7 @@ CASES = {
     "c1001_odd": (1001, 64, 2, 12, 2, 0),
     "c1000_facts": (1000, 64, 2, 12, 2, 0),                      # cfg4's fused facts kernel
     "c5000": (5000, 256, 2, 6, 2, 0),                            # cfg5's kernels
+    "c33000_dynamic": (33000, 100, 2, 6, 2, 0),                  # 66-KB rows: the run-time-W layout, the global-row pre-pass
     "gather_queue": (29, 200, 3, 16, 3, 0),
     "one_wave_wide": (29, 300, 3, 16, 3, 0),
     "global_state": (29, 8, 2, 16, 3, _lib.CTCEXT_FLAG_GLOBAL_STATE),   # widened into workspace

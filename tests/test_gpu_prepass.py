@@ -11,7 +11,11 @@ through their effect on results; S is the gather's exactness bound
 (DESIGN.md "Kernels"), so it is pinned here directly.  The normaliser the
 same launch writes (fused into ctcx_row_facts on the register path) is
 checked bit-exact against the oracle's (oracle.row_norm, decoder.h:72-80),
-NaN / +inf rows included, and rows past an item's length are left alone."""
+NaN / +inf rows included, and rows past an item's length are left alone.
+Rows of more than 8192 classes run ctcx_row_prep: with more than 64 KB of
+dynamic LDS from C = 16384, with the row exactly filling its LDS stage at
+C * sizeof(T) = 128 KB, and reading the row from global memory past that;
+ctcext_stats.kernel says which of them ran."""
 import ctypes
 import os
 import sys
@@ -103,6 +107,7 @@ def _run(x_tb, C, blank, dtype=np.float32, seq_len=None):
                               ctypes.c_void_p(sl.data_ptr()), ctypes.c_void_p(prep.data_ptr()),
                               ctypes.c_void_p(norm.data_ptr()), ctypes.byref(rb))
     assert rc == 0, lib.ctcext_last_error()
+    _run.prepass = d.stats()["kernel"]["prepass"]   # which pre-pass the launcher ran
     return prep.cpu().numpy().reshape(T * B, rb.value), norm.cpu().numpy()
 
 
@@ -168,7 +173,32 @@ def test_row_facts_nv_boundaries(C):
     _check_f32(x, C, C // 5, seq_len=[5, 4, 5, 2, 5, 3, 1])
 
 
-@pytest.mark.parametrize("C", [68, 1000, 5000, 5001])
+# (C, the pre-pass the launcher must pick): the fused facts, the facts and a
+# norm kernel, ctcx_row_prep with the row in LDS (16384: more than 64 KB of
+# dynamic LDS; 32768: the row exactly kPrepLdsBytes), ... read from global memory
+F32_PATHS = [(68, "facts_fused"), (1024, "facts_fused"), (1028, "facts_norm"), (8192, "facts_norm"),
+             (8196, "row_prep_lds"), (1001, "row_prep_lds"), (16384, "row_prep_lds"), (32768, "row_prep_lds"),
+             (32769, "row_prep_global"), (32772, "row_prep_global"), (38000, "row_prep_global")]
+
+
+@pytest.mark.parametrize("C,path", F32_PATHS)
+def test_row_facts_path_taken(C, path):
+    rng = np.random.default_rng(7400 + C)
+    _check_f32(rng.standard_normal((1, 2, C)).astype(np.float32), C, 3)
+    assert _run.prepass == path, (C, _run.prepass)
+
+
+@pytest.mark.parametrize("C", [16384, 32768, 32769, 32772, 38000])
+def test_row_facts_wide_rows(C):
+    rng = np.random.default_rng(7500 + C)
+    for kind in ("normal", "ties", "neg_inf", "all_neg_inf", "bad"):
+        for blank in (0, C - 1):
+            x = _rows(rng, C, kind, 4).reshape(2, 2, C)
+            _check_f32(x, C, blank)
+    assert _run.prepass == dict(F32_PATHS)[C]
+
+
+@pytest.mark.parametrize("C", [68, 1000, 5000, 5001, 32772])
 def test_row_facts_ragged_lengths(C):
     # items of different lengths: some of a block's four rows are past their
     # item's end (the fused kernel's waves still meet its barriers)
@@ -180,18 +210,44 @@ def test_row_facts_ragged_lengths(C):
     _check_f32(x, C, 0, seq_len=[5, 1, 0, 3, 4, 2, 5])
 
 
-def test_row_facts_f64_header_and_block_maxima():
+def _check_f64(x_tb, C, blank, seq_len=None):
     # double rows carry no top set (|S| = 0: the decode takes the plain path)
-    C = 300
-    rng = np.random.default_rng(7300)
-    x = rng.standard_normal((2, 3, C))
-    rec, norm = _run(x, C, 5, np.float64)
-    _check_norm(x, norm)
-    rows = x.reshape(-1, C)
+    rec, norm = _run(x_tb, C, blank, np.float64, seq_len=seq_len)
+    _check_norm(x_tb, norm, seq_len)
+    rows = x_tb.reshape(-1, C)
     nblk = (C + 63) // 64
+    live = None if seq_len is None else (np.arange(x_tb.shape[0])[:, None] < np.asarray(seq_len)[None, :]).reshape(-1)
     for r in range(rows.shape[0]):
         h = rec[r]
-        assert h[0:8].view(np.float64)[0] == rows[r].max()
-        assert h[16:20].view(np.int32)[0] == 0
+        if live is not None and not live[r]:
+            assert not h.any(), "the record of a row past its item's length is left alone"
+            continue
+        bad = bool(np.isnan(rows[r]).any() or np.isposinf(rows[r]).any())
+        assert bool(h[16:20].view(np.int32)[0]) == bad, (C, r)
+        assert h[20:24].view(np.int32)[0] == 0, (C, r)
+        if bad:
+            continue
+        assert h[0:8].view(np.float64)[0] == rows[r].max(), (C, r)
         bm = np.array([rows[r][k:k + 64].max() for k in range(0, C, 64)])
-        assert np.array_equal(h[32:32 + 8 * nblk].view(np.float64), bm)
+        assert np.array_equal(h[32:32 + 8 * nblk].view(np.float64), bm), (C, r)
+
+
+# double rows: the LDS stage holds 16384 of them exactly (128 KB)
+F64_PATHS = {300: "row_prep_lds", 8192: "row_prep_lds", 16384: "row_prep_lds", 16385: "row_prep_global",
+             19000: "row_prep_global"}
+
+
+@pytest.mark.parametrize("C", sorted(F64_PATHS))
+def test_row_facts_f64_header_and_block_maxima(C):
+    rng = np.random.default_rng(7300 + (C if C != 300 else 0))
+    x = rng.standard_normal((2, 3, C))
+    _check_f64(x, C, 5)
+    assert _run.prepass == F64_PATHS[C]
+    for kind in ("neg_inf", "all_neg_inf", "bad"):
+        x = _rows(rng, C, kind, 6).astype(np.float64).reshape(2, 3, C)
+        _check_f64(x, C, C - 1)
+    # ragged lengths: rows past an item's length are neither read nor written
+    x = rng.standard_normal((4, 3, C)) * 3
+    x[1, 0, C // 5] = np.nan
+    x[0, 2, 1] = np.inf
+    _check_f64(x, C, 0, seq_len=[4, 0, 2])
