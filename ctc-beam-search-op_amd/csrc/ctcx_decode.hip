@@ -1142,6 +1142,57 @@ __device__ __forceinline__ void mpush(CTCX_LDS HE<T>* he, const typename MaskGeo
   else push_m<T>(he, g, vv, vs, p.L[0], p.R[0], c0, s0, keep);
 }
 
+// std::make_heap over [0, len), len in [2, 129], in the mask form: one sift
+// per level for all of the level's nodes at once (their subtrees are
+// disjoint), each the push_m sift started at the lane's ancestor of that
+// depth instead of the root -- one LDS read batch, the ballots and one store
+// batch per level, where wave_make_heap walks every sift down and back up one
+// dependent LDS round trip per step (28 down and as many up at len = 129).
+// Same result: below a node being sifted both subtrees are heaps already, so
+// the values along its min-child path do not decrease, and __adjust_heap's
+// hole-to-a-leaf-then-__push_heap leaves v at the first path node whose min
+// child is > v, or in a min child that is a leaf (push_m's argument, per
+// subtree).  A node without children sees +inf sentinels and keeps its value,
+// as does the missing right child of an even length: positions [len, 128]
+// must hold the sentinels.  Lanes past the level's nodes store to their dummies.
+// ROOT_MIN: position 0 holds -inf and every other value is above it (the
+// evicted front of a full beam), so the root's sift is left out: the hole
+// would run down to a leaf and -inf rise back to the root, moving every path
+// node up and down again.
+template <typename T, bool ROOT_MIN>
+__device__ __forceinline__ void wave_make_heap_m(CTCX_LDS HE<T>* he, const HeapM& g, int len) {
+  const unsigned J = threadIdx.x + 1u;                       // this lane's node, 1-based
+  const int dj = 31 - (int)__builtin_clz(J);                 // its depth
+  const int last = (len - 2) / 2;                            // the last node with a child
+#pragma unroll
+  for (int d = 6; d >= (ROOT_MIN ? 1 : 0); --d) {
+    const int lo = (1 << d) - 1;                             // the level's first position
+    if (lo > last) continue;                                 // (uniform) no node of this level has a child
+    const bool in = dj >= d;                                 // in the subtree of a node of this level
+    const int r1 = in ? (int)(J >> (dj - d)) : 1;            // that node (he index: position + 1)
+    // ancestors inside the subtree (positions >= lo; every ancestor of a lane's node is below 32)
+    const unsigned ancd = lo >= 32 ? 0u : (g.anc & ~((1u << lo) - 1u));
+    HE<T> L, R;
+    he_ld2(he, g.al, L, R);
+    const HE<T> v = he_ld(he, r1);
+    const uint64_t pickR = __ballot(!(R.v > L.v));           // min child on the right (ties: right)
+    const bool pr = __builtin_amdgcn_inverse_ballot_w64(pickR);
+    const T cv = pr ? R.v : L.v;
+    const int cs = pr ? R.s : L.s;
+    // on its level node's min-child path: every ancestor in the subtree points here
+    const uint64_t onp = __ballot(in && (((unsigned)pickR ^ g.req) & ancd) == 0u);
+    const uint64_t gt = __ballot(cv > v.v);
+    const uint64_t cnd = gt | 0xffffffff00000000ull | (pickR & 0x80000000ull);   // (push_m's stop)
+    const uint64_t cm = onp & cnd;
+    const uint64_t live = onp & ~__ballot((((unsigned)cm) & ancd) != 0u);        // at or above its path's stop
+    const bool up = __builtin_amdgcn_inverse_ballot_w64(live & ~gt);             // takes its min child
+    const bool isk = __builtin_amdgcn_inverse_ballot_w64(live & cnd);            // the stop
+    const bool vg = __builtin_amdgcn_inverse_ballot_w64(gt);
+    he_st(he, up ? g.aj : g.dum, HE<T>{cv, cs});
+    he_st(he, isk ? (vg ? g.aj : (pr ? g.ar : g.al)) : g.dum, v);
+  }
+}
+
 // The HEAP_SORTED event loop for float beams of up to 128 (exact_step), as one
 // hand-scheduled asm block: the same selections, bookkeeping and push_m sift as
 // the C++ loop it replaces (the stop found by s_ff1 of the path nodes meeting
@@ -2490,6 +2541,14 @@ constexpr int kSqMaxClasses = 32768;
 __device__ __forceinline__ uint32_t sq_pack(int i, int cw, int l) {
   return (uint32_t)i | ((uint32_t)(cw + 1) << 8) | ((uint32_t)l << 17);
 }
+// ... at small C (labels < 64: bits 17-22) also the chunk lane where the
+// offer's branch turn starts, plus one (bits 23-29; 0: in an earlier chunk),
+// so wave 0 reads it instead of deriving it from its neighbour's branch
+__device__ __forceinline__ uint32_t sq_pack_sl(int i, int cw, int l, int sl) {
+  return sq_pack(i, cw, l) | ((uint32_t)(sl + 1) << 23);
+}
+__device__ __forceinline__ int sq_label_small(uint32_t pk) { return (int)((pk >> 17) & 63u); }
+__device__ __forceinline__ int sq_turn_lane(uint32_t pk) { return (int)((pk >> 23) & 127u) - 1; }
 
 // One offer's scored fields, from the frame-start state only (what the
 // score table holds): its score (decoder.h:166-171), its branch's total, the
@@ -2548,6 +2607,14 @@ __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, i
   const int Cm1 = cx.C - 1, blank = cx.blank;
   const float rcp = 1.0f / (float)Cm1;
   cqn = 0;
+  // each offer's turn-start lane (sq_pack_sl): the chunk position of its
+  // branch's first gathered offer, unless the branch began before the span
+  // (wave 0 found that turn open in an earlier chunk).  A branch gathered in
+  // an earlier scan step of this chunk is the last one gathered there (lbr,
+  // its first position lpos): offers come in branch order.
+  const int sp_i0 = i0;
+  const bool sp_mid = li0 != 0;
+  int lbr = -1, lpos = 0;
   while (cqn < 64 && i0 < nb) {
     CTCX_HPC(cx, 31, 1);
     const int x = li0 + lane;
@@ -2578,14 +2645,23 @@ __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, i
       adv = kb;
       if (kb < 64) gstop = true;
     }
+    // branch i's offers begin at step lane b0 (lane - li; 0: in an earlier
+    // step), so its first gathered offer follows the wanted lanes below b0
+    const int b0 = lane > li ? lane - li : 0;
+    const int tl = (i == lbr) ? lpos : cqn + (int)__builtin_popcountll(wM & ((1ull << b0) - 1ull));
     if ((wM >> lane) & 1ull) {
       u32x4 e;
       e.x = __builtin_bit_cast(unsigned, (float)s);
       e.y = __builtin_bit_cast(unsigned, (float)bt);
-      e.z = sq_pack(i, cw, l);
+      e.z = sq_pack_sl(i, cw, l, (sp_mid && i == sp_i0) ? -1 : tl);
       e.w = cd.bp;
       qa[cqn + rank] = e;
       qp[cqn + rank] = (float)cd.p;
+    }
+    if (wM) {
+      const int last = 63 - (int)__builtin_clzll(wM);
+      lbr = bcast(i, last);
+      lpos = bcast(tl, last);
     }
     cqn += __builtin_popcountll(wM);
     // (i0, li0) += adv offers
@@ -3087,7 +3163,195 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   // double rows |S| = 0 and the S path below is never taken)
   const int tsn = BIG ? cx.rns : 0;
   const T txo = BIG ? cx.rxout : NI;
+  // The scored queue at small C (float, base scorer): once the beam is a heap
+  // (the chunk that fills it goes by the generic path below), the rest of the
+  // frame's grow is scored chunks only, and they run as one loop of their own,
+  // as the windows do: the heap's geometry and addresses are set up once per
+  // frame, the front and the bump pointer stay in registers from chunk to
+  // chunk, and a chunk is its hand-over read, the unpack (the turn-start lane
+  // comes packed: sq_pack_sl), the events and the flush, with none of the
+  // generic chunk path's state around them.  Same decisions, pushes, slots,
+  // records and published bottoms as that path, chunk for chunk; the bounded
+  // wait, a dead helper and the re-offers of branch children are its code.
+  constexpr bool kSqHeapM = SQ && HW && !BIG && RN == 1 && sizeof(T) == 4;
+  constexpr bool kSqLoop = kSqHeapM && !SC::kStateful && !kSetK && !kBatLazy;
   while (i0 < nb && !stop) {
+    if constexpr (kSqLoop) {
+      if (full && st == kTopHeap && W >= 2) {
+        const auto geo = mask_geo<RN>(cx.hdum);
+        const unsigned heb = (unsigned)(uintptr_t)he;   // LDS byte address of he[0]
+        const unsigned aj = heb + 8u * (unsigned)(lane + 1), al = heb + 8u * (unsigned)(2 * lane + 2);
+        const unsigned ar = al + 8u, dum = heb + 8u * (unsigned)(cx.hdum + lane);
+        T fv = front.v;
+        int fs = front.s;
+        int nfree = nextfree;
+        while (!stop) {
+          // the next chunk of the helper's queue: the published count first,
+          // the slot's words in the same batch
+          const int slot = gqc & gq.sm;
+          int h0 = 0, h3 = 0;
+          auto read_slot = [&]() {
+            h0 = gq.h[slot * 4 + 0]; h3 = gq.h[slot * 4 + 3];
+            gqa = gq.a[slot * 64 + lane];
+            gqv = gq.p[slot * 64 + lane];
+          };
+          {
+            int rdy = __hip_atomic_load(&cx.misc[kCtlReady], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __asm__ volatile("" ::: "memory");
+            read_slot();
+            CTCX_ONE_TRIP(rdy, "v"(h0), "v"(h3), "v"(gqa), "v"(gqv));
+            if (__builtin_expect(uni(rdy) <= gqc && !cx.tabdead, 0)) {
+              // the helper is behind: the bounded wait of the generic path (a
+              // wait that runs out, or a helper that gave up, ends the grow)
+              uint64_t tw = 0;
+              const uint64_t tq0 = pc ? __builtin_amdgcn_s_memtime() : 0;
+              int spins = 0;
+              for (int spin = 0;; ++spin) {
+                spins = spin + 1;
+                __builtin_amdgcn_s_sleep(CTCX_SLEEP);
+                if (ctl_ld(cx.misc, kCtlReady) > gqc) break;
+                if (ctl_ld(cx.misc, kCtlDead) != 0 || wait_expired(spin, tw)) {   // never in a correct run
+                  cx.tabdead = 1;
+                  __hip_atomic_store(&cx.misc[kCtlDead], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                  break;
+                }
+              }
+              __asm__ volatile("" ::: "memory");
+              read_slot();
+              if (pc) {
+                (void)uni((int)h0);
+                pc[19] += __builtin_amdgcn_s_memtime() - tq0;
+                pc[20] += spins;
+              }
+            }
+          }
+          __asm__ volatile("" ::: "memory");
+          ++gqc;
+          __hip_atomic_store(&cx.misc[kCtlCons], gqc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          cqn = cx.tabdead ? 0 : uni(h0);
+          gstop = uni(h3) != 0;
+          if (cqn == 0) {
+            if (gstop) stop = true;
+            break;
+          }
+          const uint64_t tc0 = pc ? __builtin_amdgcn_s_memtime() : 0;
+          const bool valid = lane < cqn;
+          const uint32_t ax = gqa.x, ay = gqa.y, az = gqa.z, aw = gqa.w;   // (scalar copies: see the generic path)
+          const uint32_t pk = valid ? az : 0u;
+          const int i = (int)(pk & 255u);
+          const int c = (int)((pk >> 8) & 511u) - 1;
+          const int l = sq_label_small(pk);
+          const int sl = sq_turn_lane(pk);
+          const T s = (T)__builtin_bit_cast(float, ax);
+          const T bt = (T)__builtin_bit_cast(float, ay);
+          const bool isbc = c >= 0;
+          const uint64_t isbm = __ballot(isbc);
+          // what events change: the branch deactivated (read only after a
+          // deactivation this frame), the branch child evicted
+          bool live = valid;
+          if (dz) live = live && !(cx.bst[i] & S_DEACT);
+          bool cev = false;
+          if (isbm) cev = isbc && (cx.bst[isbc ? c : i] & S_EVICT);
+          T bat = sl > 0 ? fv : NI;
+          const uint64_t startsM = __ballot(valid && sl == lane && lane != 0);   // branch turns starting mid-chunk
+          if (pc) pc[10] += __builtin_amdgcn_s_memtime() - tc0;
+          if (!__ballot(live && ((s > fv) | (isbc && cev)))) {
+            if (startsM & ~__ballot(bt > fv)) break;   // no event here: every start sees this bottom
+            if (gstop) break;
+            continue;
+          }
+          const uint64_t tc1 = pc ? __builtin_amdgcn_s_memtime() : 0;
+          if (pc) { pc[8] += tc1 - tc0; pc[11] += 1; }
+          int myslot = -1;   // slot of this lane's accepted offer (-1: none, or evicted again)
+          int evr = 0;       // record nv-th: evicted branch slot, or kDeactRec | rejected branch
+          int nv = 0;
+          uint64_t done = 0;
+          const uint64_t liveM = __ballot(live);
+          uint64_t NC = liveM & ~isbm, LB = liveM & isbm, RB = LB & __ballot(cev);
+          for (;;) {
+            int k;
+            fv = uni(fv); fs = uni(fs); nfree = uni(nfree); nv = uni(nv);
+            int nev_asm = 0;
+            const uint64_t ta = pc ? __builtin_amdgcn_s_memtime() : 0;
+            const int est = heap_events_f32(s, c, sl, geo.anc, geo.req, aj, al, ar, dum, myslot, evr, bat, NC, RB, done,
+                                            LB, fv, fs, nfree, nv, uni(nb), k, nev_asm);
+            if (pc) { pc[13] += __builtin_amdgcn_s_memtime() - ta; pc[6] += uni(nev_asm); pc[12] += 1; }
+            if (est == 0) break;
+            k = uni(k);
+            // lane k re-offers a branch child: was k's turn skipped?
+            const uint64_t gtM = __ballot(s > fv);
+            const uint64_t m = ((gtM & NC) | RB) & ~done;   // its lowest lane is k
+            if ((__ballot(!(bt > bat)) >> k) & 1ull) {
+              const uint64_t keepM = lowmask(bcast(sl, k));   // that branch and every later one
+              NC &= keepM; LB &= keepM; RB &= keepM;
+              stop = true;
+              continue;
+            }
+            done = m ^ (m - 1ull);
+            const int kc = bcast(c, k);
+            if (!((gtM >> k) & 1ull)) {
+              // re-offered evicted branch rejected -> deactivated (decoder.h:200-205)
+              evr = writelane(evr, kc | kDeactRec, nv);
+              dz = true;
+              nv += 1;
+              const uint64_t dm = ~__ballot(i == kc);
+              NC &= dm; LB &= dm; RB &= dm;
+              continue;
+            }
+            // accepted: the branch's entry keeps its slot
+            if (fs < nb) {
+              evr = writelane(evr, fs, nv);
+              nv += 1;
+              RB |= LB & __ballot(c == fs);
+            }
+            const T k_s = bcast(s, k);
+            myslot = (myslot == fs) ? -1 : myslot;
+            myslot = __builtin_amdgcn_inverse_ballot_w64(1ull << k) ? kc : myslot;
+            MPairs<T, RN> pp;
+            mpairs<T, RN>(he, geo, pp);
+            T c0;
+            int s0;
+            bool keep;
+            mpush<T, RN>(he, geo, k_s, kc, pp, c0, s0, keep);
+            fv = keep ? k_s : c0;
+            fs = keep ? kc : s0;
+            bat = (sl > k) ? fv : bat;
+          }
+          // the turn continuing into the next chunk: skipped -> so is every later one
+          if ((__ballot(valid && !(bt > bat)) >> (cqn - 1)) & 1ull) stop = true;
+          if (gstop) stop = true;
+          // flush: resets and flags first, then the surviving accepted entries
+          const uint64_t q5 = pc ? __builtin_amdgcn_s_memtime() : 0;
+          if (lane < nv) {
+            const int rs = evr & ~kDeactRec;
+            if (evr & kDeactRec) {
+              __hip_atomic_fetch_or(&cx.bst[rs], S_DEACT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+              cx.et[rs] = NI; cx.eb[rs] = NI; cx.el[rs] = NI; cx.eflg[rs] = 0;
+              __hip_atomic_fetch_or(&cx.bst[rs], S_EVICT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+          }
+          if (myslot >= 0) {
+            cx.et[myslot] = s; cx.eb[myslot] = NI; cx.el[myslot] = s;
+            cx.ecn[myslot] = (T)gqv; cx.ebpn[myslot] = aw;
+            cx.eflg[myslot] = F_HN;
+            cx.ekind[myslot] = isbc ? ((uint32_t)c << 1) : (((uint32_t)i << 1) | 1u);
+            cx.elab[myslot] = l;
+            if (isbc) __hip_atomic_fetch_and(&cx.bst[c], ~S_EVICT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+          // the helper gathers the next chunks against this bottom
+          __hip_atomic_store(&cx.misc[kCtlBot], (int)__builtin_bit_cast(unsigned, (float)fv), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (pc) pc[15] += __builtin_amdgcn_s_memtime() - q5;
+          if (pc) pc[9] += __builtin_amdgcn_s_memtime() - tc1;
+        }
+        front.v = fv;
+        front.s = fs;
+        bottom = fv;
+        nextfree = nfree;
+        break;
+      }
+    }
     if constexpr (RN == 1 && !BIG && sizeof(T) == 4 && !SC::kStateful && !SQ) {
       if (st == kTopHeap && W >= 2) {
         // the windows run as one loop of their own (each window ends with the
@@ -3509,7 +3773,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
           if constexpr (SQ) {
             gqa = gq.a[slot * 64 + lane];
             gqv = gq.p[slot * 64 + lane];
-            gqp = gq.a[slot * 64 + (lane > 0 ? lane - 1 : 0)].z;
+            if constexpr (BIG) gqp = gq.a[slot * 64 + (lane > 0 ? lane - 1 : 0)].z;   // (small C: sq_pack_sl)
           } else {
             gqe = gq.e[slot * 64 + lane];
             gqp = gq.e[slot * 64 + (lane > 0 ? lane - 1 : 0)];
@@ -3597,13 +3861,18 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
       const uint32_t pk = valid ? az : 0u;   // (lanes past cqn: branch 0, no child)
       i = (int)(pk & 255u);
       c = (int)((pk >> 8) & 511u) - 1;
-      l = (int)(pk >> 17);
       s = (T)__builtin_bit_cast(float, ax);
       bt = (T)__builtin_bit_cast(float, ay);
       cd = Best<T>{(T)gqv, aw, true};
-      const int ip = lane > 0 ? (int)(gqp & 255u) : -1;
-      const uint64_t fm = __ballot(valid && i != ip) & lowmask(lane + 1);
-      sl = (i > cq_i0 || cq_l0 == 0) ? 63 - __builtin_clzll(fm) : -1;
+      if constexpr (BIG) {
+        l = (int)(pk >> 17);
+        const int ip = lane > 0 ? (int)(gqp & 255u) : -1;
+        const uint64_t fm = __ballot(valid && i != ip) & lowmask(lane + 1);
+        sl = (i > cq_i0 || cq_l0 == 0) ? 63 - __builtin_clzll(fm) : -1;
+      } else {   // small C: the helper packed the turn-start lane (sq_pack_sl)
+        l = sq_label_small(pk);
+        sl = sq_turn_lane(pk);
+      }
 #ifdef CTCX_SQ_CHECK   // (diagnostics: wave 0 recomputes every scored field; mismatches counted in misc[15])
       {
         T s2, bt2;
@@ -4155,7 +4424,12 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
 #ifdef CTCX_FASTLOOP_PROF
             const uint64_t q4 = __builtin_amdgcn_s_memtime();
 #endif
-            wave_make_heap(he, W + 1);
+            if constexpr (kSqHeapM) {   // the mask form (its sentinels past the W + 1 elements first)
+              heap_sentinels(he, W + 1, 128);
+              wave_make_heap_m<T, true>(he, heap_m(cx.hdum), W + 1);   // (the front was set to -inf above)
+            } else {
+              wave_make_heap(he, W + 1);
+            }
             const HE<T> r0 = he_ld(he, 1);
             front = wave_adjust_heap<T, RN>(he, heap_geo<RN>(W, cx.hdum), nv, W);   // pop_heap(W + 1)
             if (lane == 0) he_st(he, W + 1, r0);
