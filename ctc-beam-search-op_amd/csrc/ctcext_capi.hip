@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/ctcext.h"
+#define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
 
 namespace ctcx {
@@ -43,6 +44,15 @@ hipError_t launch_pack(const PackParams& pp, hipStream_t s);
 }  // namespace ctcx
 // the global-state tier (ctcx_decode.hip compiled with CTCX_GSTATE)
 hipError_t ctcx_gstate_launch_decode(const void* p, int is_f64, int scored, hipStream_t s);
+// the stream builds (CTCX_STREAM, and CTCX_GSTATE with it): p is this file's
+// DecodeParams<T>, the stream's own parameters travel beside it
+hipError_t ctcx_stream_launch_decode(const void* p, const CtcxStreamParams* sp, int is_f64, hipStream_t s);
+hipError_t ctcx_gstate_stream_launch_decode(const void* p, const CtcxStreamParams* sp, int is_f64, int scored,
+                                            hipStream_t s);
+
+static_assert(sizeof(ctcx::DecodeParams<float>) == kCtcxDecodeParamsBytes &&
+                  sizeof(ctcx::DecodeParams<double>) == kCtcxDecodeParamsBytes,
+              "the stream launchers copy exactly this struct (ctcx_kernels.h)");
 
 static thread_local std::string g_err;
 
@@ -54,6 +64,18 @@ constexpr int kDefaultHelperMode = ctcx::kHelperScored;
 static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
+}
+
+// CTCEXT_HELPER (diagnostics; read once per decode call, and once at a
+// stream's open): 0 the one-wave kernels, 1 the score table / unscored gather
+// queue, 3 the scored gather queue (beams <= 128; the default), 4 the scored
+// queue for beams <= 256
+static int helper_mode_from_env() {
+  const char* hv = getenv("CTCEXT_HELPER");
+  return !hv || !hv[0] ? kDefaultHelperMode
+         : hv[0] == '0' ? ctcx::kHelperNone
+         : hv[0] == '3' ? ctcx::kHelperScored
+         : hv[0] == '4' ? ctcx::kHelperScoredWide : ctcx::kHelperLegacy;
 }
 
 #define HIP_OR_FAIL(expr)                                                             \
@@ -769,14 +791,7 @@ extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args
   d->sizes.assign((size_t)P, ctcext_path_sizes{0, 0, 0, 0});
   d->stats = ctcext_stats{};
   if (B > 0) {
-    // CTCEXT_HELPER (diagnostics, read once per call): 0 the one-wave kernels,
-    // 1 the score table / unscored gather queue, 3 the scored gather queue
-    // (beams <= 128; the default), 4 the scored queue for beams <= 256
-    const char* hv = getenv("CTCEXT_HELPER");
-    const int helper_mode = !hv || !hv[0] ? kDefaultHelperMode
-                            : hv[0] == '0' ? ctcx::kHelperNone
-                            : hv[0] == '3' ? ctcx::kHelperScored
-                            : hv[0] == '4' ? ctcx::kHelperScoredWide : ctcx::kHelperLegacy;
+    const int helper_mode = helper_mode_from_env();
     rc = (a->dtype == CTCEXT_F32) ? run_decode<float>(d, a, hsl, s, helper_mode)
                                   : run_decode<double>(d, a, hsl, s, helper_mode);
     if (rc != CTCEXT_OK) return rc;
@@ -879,6 +894,466 @@ extern "C" int ctcext_fetch(ctcext_decoder* d, const ctcext_outputs* o) {
     }
   }
   HIP_OR_FAIL(hipStreamSynchronize(s));
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Streaming decode (ctcext.h, "Streaming decode").  A stream owns the records
+// of max_frames frames per item, two state buffers (header + LDS image per
+// item; the push reads one and writes the other, and they swap when the push
+// succeeded) and, on the global-state tier, the state itself.  A push runs
+// the chunk's pre-pass, the stream build of the decode kernel the stream chose
+// at open, and (sizes != NULL) the traceback over all frames so far into the
+// decoder's walk buffers, which ctcext_fetch packs as after ctcext_decode.
+
+struct ctcext_stream {
+  ctcext_decoder* dec = nullptr;
+  ctcext_stream_args a{};
+  bool gs = false, scored = false;
+  int helper = 0;            // the two-wave kernel of the stream's life (ctcx::use_helper_kernel at open)
+  int rec_fmt = 0, rec_bytes = 8;
+  int64_t image_bytes = 0;   // the decode kernel's dynamic LDS bytes (0 on the global-state tier)
+  int64_t stride = 0;        // bytes per item in a state buffer
+  void* state[2] = {nullptr, nullptr};
+  int cur = 0;               // state[cur]: the committed state
+  void* rec = nullptr;
+  void* gstate = nullptr;
+  void* sctab = nullptr;
+  void* cum = nullptr;       // [B] int32: frames per item including the running push (the traceback's lengths)
+  DevBuf x, xw, sl, norm, prep;
+  std::vector<int64_t> frames;
+};
+
+// The stream's attributes as the one-shot argument struct, for the shared
+// checks (one frame of a well-formed batch; inputs are not read by them).
+static ctcext_decode_args stream_decode_args(const ctcext_stream_args* a) {
+  static const int32_t one = 1;
+  ctcext_decode_args d{};
+  d.dtype = a->dtype;
+  d.inputs_on_device = 1;
+  d.inputs = &one;
+  d.sequence_length = &one;
+  d.max_time = 1; d.batch_size = a->batch_size; d.num_classes = a->num_classes;
+  d.beam_width = a->beam_width; d.top_paths = a->top_paths; d.merge_repeated = a->merge_repeated;
+  d.blank_index = a->blank_index; d.blank_label = a->blank_label; d.flags = a->flags;
+  d.inputs_dims = 3; d.sequence_length_dims = 1; d.sequence_length_size = a->batch_size;
+  d.scorer = a->scorer; d.scorer_table = a->scorer_table;
+  return d;
+}
+
+extern "C" int ctcext_stream_validate(const ctcext_stream_args* a) {
+  if (!a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ctcext_decode_args d = stream_decode_args(a);
+  int rc = validate_shapes(&d);
+  if (rc == CTCEXT_OK) rc = check_limits(&d);
+  // (the table is host memory whatever on_device says: ctcext.h)
+  if (rc == CTCEXT_OK) rc = check_table(&d, a->scorer_table);
+  if (rc == CTCEXT_OK && (a->flags & ~(CTCEXT_FLAG_FORCE_LITERAL | CTCEXT_FLAG_GLOBAL_STATE | CTCEXT_FLAG_PROFILE)))
+    rc = fail(CTCEXT_INVALID_ARGUMENT, "stream flags: CTCEXT_FLAG_FORCE_LITERAL, _GLOBAL_STATE and _PROFILE only");
+  if (rc == CTCEXT_OK && a->max_frames < 0) rc = fail(CTCEXT_INVALID_ARGUMENT, "max_frames is negative");
+  if (rc == CTCEXT_OK && a->max_frames > INT32_MAX)
+    rc = fail(CTCEXT_UNIMPLEMENTED, "max_frames beyond this library's 32-bit frame indices");
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+// A chunk against its stream's attributes, host only: the layout checks of
+// ctcext_validate with chunk_time as max_time, and the lengths when the
+// caller holds them on the host (hcl; null: not checked here).
+static int check_chunk(const ctcext_stream_args* a, const ctcext_chunk* c, const int32_t* hcl) {
+  if (!a || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (c->chunk_time < 0) return fail(CTCEXT_INVALID_ARGUMENT, "inputs has a negative dimension");
+  if (a->batch_size > 0 && c->chunk_time > 0 && !c->inputs) return fail(CTCEXT_INVALID_ARGUMENT, "null input pointer");
+  if (hcl) {
+    const int rc = check_lengths(hcl, a->batch_size, c->chunk_time);
+    if (rc != CTCEXT_OK) return rc;
+  }
+  ctcext_decode_args d = stream_decode_args(a);
+  d.max_time = c->chunk_time;
+  d.inputs_format = c->inputs_format;
+  d.inputs_stride_t = c->inputs_stride_t;
+  d.inputs_stride_b = c->inputs_stride_b;
+  return check_layout(&d);
+}
+
+extern "C" int ctcext_stream_validate_chunk(const ctcext_stream_args* a, const ctcext_chunk* c) {
+  int rc = ctcext_stream_validate(a);
+  if (rc != CTCEXT_OK) return rc;
+  rc = check_chunk(a, c, (c && !a->on_device) ? c->chunk_length : nullptr);
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+static void stream_free(ctcext_stream* st) {
+  void* ps[] = {st->state[0], st->state[1], st->rec, st->gstate, st->sctab, st->cum};
+  for (void* p : ps)
+    if (p) (void)hipFree(p);
+  DevBuf* bufs[] = {&st->x, &st->xw, &st->sl, &st->norm, &st->prep};
+  for (DevBuf* b : bufs) b->release();
+  delete st;
+}
+
+// The DecodeParams of a push (or, with no chunk yet, of the kernel query at open).
+template <typename T>
+static ctcx::DecodeParams<T> stream_decode_params(const ctcext_stream* st) {
+  const ctcext_stream_args& a = st->a;
+  ctcx::DecodeParams<T> p{};
+  p.Tmax = a.max_frames; p.B = a.batch_size; p.C = a.num_classes;
+  p.W = a.beam_width; p.P = a.top_paths; p.blank = a.blank_index; p.blank_label = a.blank_label;
+  p.force_literal = ((a.flags & CTCEXT_FLAG_FORCE_LITERAL) || a.num_classes < 2) ? 1 : 0;
+  p.rec = (ctcx::Rec*)st->rec;
+  p.scorer_tab = (const T*)st->sctab;
+  p.ring = 0;                 // every record is written: a later chunk may reach what a ring would prune
+  p.helper = st->helper;
+  if (st->gs) {
+    p.gstate = (char*)st->gstate;
+    p.gstate_stride = (int64_t)ctcx::gstate_bytes(a.beam_width, (int)sizeof(T), st->scored);
+  }
+  return p;
+}
+
+template <typename T>
+static int stream_open_t(ctcext_stream* st) {
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size, C = a.num_classes, F = a.max_frames;
+  const int W = a.beam_width, P = a.top_paths;
+  Dev& root = st->dec->devs[0];
+  hipStream_t s = root.own_stream;
+  if (st->scored) {
+    const size_t tb = (size_t)((C + 1) * C) * sizeof(T);
+    HIP_OR_FAIL(hipMalloc(&st->sctab, tb));
+    // (host memory, checked by ctcext_stream_validate; the copy is done before open returns)
+    HIP_OR_FAIL(hipMemcpyAsync(st->sctab, a.scorer_table, tb, hipMemcpyHostToDevice, s));
+  }
+  if (B > 0x7fffffffLL || (!st->gs && (W > ctcx::kMaxRecBeam || C > ctcx::kMaxRecClasses)))
+    return fail(CTCEXT_INTERNAL, "shard shape outside the kernel's limits");
+  int* note = ctcx_launch_note();
+  note[0] = 0;
+  if (st->gs) {
+    st->helper = 0;
+    st->image_bytes = 0;
+    st->rec_fmt = ctcx::kRecFmt128;
+    HIP_OR_FAIL(hipMalloc(&st->gstate, ctcx::gstate_bytes(W, (int)sizeof(T), st->scored) * (size_t)B + 256));
+  } else {
+    // the kernel of the stream's life: launch_decode's rules with the helper
+    // kind decided here; its launcher reports the LDS bytes (the image) and
+    // launches nothing
+    ctcx::DecodeParams<T> p = stream_decode_params<T>(st);
+    const int hk = ctcx::helper_kind<T>(p, helper_mode_from_env());
+    p.helper = st->helper = ctcx::use_helper_kernel<T>(p, hk);
+    int64_t lds = 0;
+    CtcxStreamParams sp{};
+    sp.query = &lds;
+    HIP_OR_FAIL(ctcx_stream_launch_decode(&p, &sp, sizeof(T) == 8, s));
+    st->image_bytes = lds;
+    st->rec_fmt = ctcx::helper_rec32(st->helper, C) ? ctcx::kRecFmt32 : ctcx::kRecFmt64;
+  }
+  st->rec_bytes = st->rec_fmt == ctcx::kRecFmt128 ? 16 : st->rec_fmt == ctcx::kRecFmt32 ? 4 : 8;
+  st->stride = (int64_t)((ctcx_stream_hdr_bytes(P) + (size_t)st->image_bytes + 255) & ~(size_t)255);
+  const size_t sb = (size_t)st->stride * (size_t)B + 256;
+  for (int k = 0; k < 2; ++k) {
+    HIP_OR_FAIL(hipMalloc(&st->state[k], sb));
+    HIP_OR_FAIL(hipMemsetAsync(st->state[k], 0, sb, s));   // frames == 0: every item starts from Reset()
+  }
+  HIP_OR_FAIL(hipMalloc(&st->rec, (size_t)st->rec_bytes * (size_t)(B * F * W) + 256));
+  HIP_OR_FAIL(hipMalloc(&st->cum, 4 * (size_t)B + 256));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  st->frames.assign((size_t)B, 0);
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_open(ctcext_decoder* d, const ctcext_stream_args* a, ctcext_stream** out) {
+  if (!d || !a || !out) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_stream_validate(a);
+  if (rc != CTCEXT_OK) return rc;
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a stream needs a one-device decoder handle");
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(d->devs[0].device));
+  ctcext_stream* st = new ctcext_stream();
+  st->dec = d;
+  st->a = *a;
+  const ctcext_decode_args da = stream_decode_args(a);
+  st->gs = use_gstate(&da);
+  st->scored = a->scorer != CTCEXT_SCORER_BASE && a->batch_size > 0;
+  rc = a->dtype == CTCEXT_F64 ? stream_open_t<double>(st) : stream_open_t<float>(st);
+  st->a.scorer_table = nullptr;   // (copied)
+  if (rc != CTCEXT_OK) {
+    const std::string keep = g_err;
+    stream_free(st);
+    g_err = keep;
+    return rc;
+  }
+  *out = st;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" void ctcext_stream_close(ctcext_stream* st) {
+  if (!st) return;
+  DeviceGuard guard;
+  Dev& root = st->dec->devs[0];
+  (void)hipSetDevice(root.device);
+  if (root.own_stream) (void)hipStreamSynchronize(root.own_stream);
+  stream_free(st);
+}
+
+extern "C" int ctcext_stream_frames(ctcext_stream* st, int64_t* frames) {
+  if (!st || !frames) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  for (size_t b = 0; b < st->frames.size(); ++b) frames[b] = st->frames[b];
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_reset(ctcext_stream* st, const int32_t* items, int64_t n) {
+  if (!st) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const int64_t B = st->a.batch_size;
+  if (items) {
+    if (n < 0) return fail(CTCEXT_INVALID_ARGUMENT, "negative item count");
+    for (int64_t i = 0; i < n; ++i)
+      if (items[i] < 0 || items[i] >= B) return fail(CTCEXT_INVALID_ARGUMENT, "stream item out of range [0, batch_size)");
+  }
+  DeviceGuard guard;
+  Dev& root = st->dec->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.own_stream;
+  // frames = 0 in the committed header: the item's next push runs Reset()
+  const int64_t cnt = items ? n : B;
+  for (int64_t i = 0; i < cnt; ++i) {
+    const int64_t b = items ? items[i] : i;
+    HIP_OR_FAIL(hipMemsetAsync((char*)st->state[st->cur] + (size_t)b * (size_t)st->stride, 0, sizeof(CtcxStreamHdr), s));
+  }
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  for (int64_t i = 0; i < cnt; ++i) st->frames[(size_t)(items ? items[i] : i)] = 0;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+template <typename T>
+static int stream_push_t(ctcext_stream* st, const ctcext_chunk* c, const std::vector<int32_t>& hcl,
+                         ctcext_path_sizes* sizes, hipStream_t s) {
+  ctcext_decoder* d = st->dec;
+  Dev& root = d->devs[0];
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size, C = a.num_classes, F = a.max_frames, Tc = c->chunk_time;
+  const int W = a.beam_width, P = a.top_paths;
+  const int ts = (int)sizeof(T);
+  const bool prof = ((a.flags | c->flags) & CTCEXT_FLAG_PROFILE) != 0;
+  int* note = ctcx_launch_note();
+  note[0] = note[1] = note[2] = 0;
+
+  // the chunk's element strides, as run_decode takes a whole tensor's
+  int xfmt = c->inputs_format;
+  const size_t es = xfmt == CTCEXT_IN_NATIVE ? (size_t)ts : 2;
+  int64_t st_t = c->inputs_stride_t ? c->inputs_stride_t : B * C;
+  int64_t st_b = c->inputs_stride_b ? c->inputs_stride_b : C;
+  if (Tc <= 1 && B <= 1) st_t = st_b = C;
+  else if (Tc <= 1) st_t = st_b * B;
+  else if (B <= 1) st_b = st_t * Tc;
+  const void* x = c->inputs;
+  const int32_t* sl = nullptr;
+  std::vector<int32_t> hcum((size_t)B);
+  for (int64_t b = 0; b < B; ++b) hcum[(size_t)b] = (int32_t)(st->frames[(size_t)b] + hcl[(size_t)b]);
+  HIP_OR_FAIL(hipMemcpyAsync(st->cum, hcum.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  if (a.on_device && c->chunk_length) {
+    sl = c->chunk_length;
+  } else {
+    HIP_OR_FAIL(st->sl.ensure(4 * (size_t)B + 16));
+    HIP_OR_FAIL(hipMemcpyAsync(st->sl.p, hcl.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
+    sl = (const int32_t*)st->sl.p;
+  }
+  if (!a.on_device && Tc > 0) {
+    // host chunks: the rows as a dense tensor on the device, in their own
+    // element type and dimension order (run_decode's shard copy, whole batch)
+    const size_t cb = (size_t)C * es;
+    HIP_OR_FAIL(st->x.ensure(cb * (size_t)B * (size_t)Tc + 16));
+    const char* src = (const char*)c->inputs;
+    const bool bmajor = st_t < st_b;
+    const int64_t no = bmajor ? B : Tc, ni = bmajor ? Tc : B;
+    const int64_t so = bmajor ? st_b : st_t, si = bmajor ? st_t : st_b;
+    const size_t slab = cb * (size_t)ni;
+    if (si == C && (so == ni * C || no == 1)) {
+      HIP_OR_FAIL(hipMemcpyAsync(st->x.p, src, slab * (size_t)no, hipMemcpyDefault, s));
+    } else if (si == C && so >= ni * C) {
+      HIP_OR_FAIL(hipMemcpy2DAsync(st->x.p, slab, src, (size_t)so * es, slab, (size_t)no, hipMemcpyDefault, s));
+    } else {
+      for (int64_t o = 0; o < no; ++o)
+        HIP_OR_FAIL(hipMemcpy2DAsync((char*)st->x.p + (size_t)o * slab, cb, src + (size_t)o * (size_t)so * es,
+                                     (size_t)si * es, cb, (size_t)ni, hipMemcpyDefault, s));
+    }
+    x = st->x.p;
+    st_t = bmajor ? C : B * C;
+    st_b = bmajor ? Tc * C : C;
+  }
+
+  HIP_OR_FAIL(root.item.ensure(sizeof(ctcx::ItemOut) * (size_t)B));
+  HIP_OR_FAIL(root.top_pos.ensure(4 * (size_t)(B * P)));
+  HIP_OR_FAIL(root.top_kind.ensure(4 * (size_t)(B * P)));
+  HIP_OR_FAIL(root.logp.ensure(sizeof(T) * (size_t)(B * P)));
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[0], s));
+  if (Tc > 0) {   // the pre-pass over the chunk's rows (chunk-local indices)
+    HIP_OR_FAIL(st->norm.ensure(sizeof(T) * (size_t)(Tc * B)));
+    if (st->gs && xfmt != CTCEXT_IN_NATIVE) {
+      HIP_OR_FAIL(st->xw.ensure(4 * (size_t)(Tc * B * C) + 16));
+      HIP_OR_FAIL(ctcx::launch_widen_rows(x, xfmt, (float*)st->xw.p, Tc, B, C, st_t, st_b, s));
+      x = st->xw.p;
+      xfmt = CTCEXT_IN_NATIVE;
+      st_t = B * C;
+      st_b = C;
+    }
+    if (!st->gs && C > 64) {
+      HIP_OR_FAIL(st->prep.ensure(ctcx::prep_row_bytes(C, ts) * (size_t)(Tc * B)));
+      HIP_OR_FAIL(ctcx::launch_row_prep<T>(x, xfmt, sl, (char*)st->prep.p, (T*)st->norm.p, Tc, B, C, st_t, st_b,
+                                           a.blank_index, s));
+    } else {
+      HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, xfmt, sl, (T*)st->norm.p, Tc, B, C, st_t, st_b, s));
+    }
+  }
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[1], s));
+
+  ctcx::DecodeParams<T> p = stream_decode_params<T>(st);
+  p.x = (const T*)x;
+  p.xfmt = xfmt;
+  p.norm = (const T*)st->norm.p;
+  p.seq_len = sl;
+  p.xst_t = st_t; p.xst_b = st_b;
+  p.item = (ctcx::ItemOut*)root.item.p;
+  p.top_pos = (int32_t*)root.top_pos.p;
+  p.top_kind = (int32_t*)root.top_kind.p;
+  p.log_prob = (T*)root.logp.p;
+  p.prep = (const char*)st->prep.p;
+  p.test_flags = (c->flags & CTCEXT_FLAG_TEST_HELPER_DEAD) ? ctcx::kTestHelperDead : 0;
+  CtcxStreamParams sp{};
+  sp.in = (const char*)st->state[st->cur];
+  sp.out = (char*)st->state[st->cur ^ 1];
+  sp.stride = st->stride;
+  sp.image_bytes = st->image_bytes;
+  if (st->gs) HIP_OR_FAIL(ctcx_gstate_stream_launch_decode(&p, &sp, ts == 8, st->scored, s));
+  else HIP_OR_FAIL(ctcx_stream_launch_decode(&p, &sp, ts == 8, s));
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[2], s));
+
+  HIP_OR_FAIL(d->h_item.ensure(sizeof(ctcx::ItemOut) * (size_t)B + 16));
+  if (sizes) {
+    // the walks of every frame so far, from the records the stream keeps
+    HIP_OR_FAIL(root.seq.ensure(4 * (size_t)(B * P * 2 * F) + 16));
+    HIP_OR_FAIL(root.len.ensure(4 * (size_t)(B * P * 2)));
+    ctcx::TraceParams tp{};
+    tp.rec = p.rec; tp.item = p.item; tp.seq_len = (const int32_t*)st->cum; tp.top_pos = p.top_pos;
+    tp.top_kind = p.top_kind;
+    tp.Tmax = F; tp.B = B; tp.W = W; tp.P = P; tp.merge = a.merge_repeated ? 1 : 0;
+    tp.blank_label = a.blank_label;
+    tp.rec_fmt = st->rec_fmt;
+    tp.foff = nullptr;
+    tp.seq = (int32_t*)root.seq.p;
+    tp.len = (int32_t*)root.len.p;
+    tp.len_stride = B;
+    HIP_OR_FAIL(ctcx::launch_traceback(tp, s));
+    HIP_OR_FAIL(d->h_res.ensure(8 * (size_t)(P * 4) + 16));
+    HIP_OR_FAIL(d->off.ensure(8 * (size_t)(B * P * 2)));
+    HIP_OR_FAIL(d->res.ensure(8 * (size_t)(P * 4)));
+    HIP_OR_FAIL(d->h_kind.ensure(4 * (size_t)(B * P) + 16));
+    HIP_OR_FAIL(ctcx::launch_scan((const int32_t*)root.len.p, (int64_t*)d->off.p, (int64_t*)d->res.p, B, P, s));
+    HIP_OR_FAIL(hipMemcpyAsync(d->h_res.p, d->res.p, 8 * (size_t)(P * 4), hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipMemcpyAsync(d->h_kind.p, root.top_kind.p, 4 * (size_t)(B * P), hipMemcpyDeviceToHost, s));
+  }
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[3], s));
+  HIP_OR_FAIL(hipMemcpyAsync(d->h_item.p, root.item.p, sizeof(ctcx::ItemOut) * (size_t)B, hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+
+  const ctcx::ItemOut* io = (const ctcx::ItemOut*)d->h_item.p;
+  for (int64_t b = 0; b < B; ++b)
+    if (io[b].pad != 0)   // (the state buffers are not swapped: the stream stays at its pre-push state)
+      return fail(CTCEXT_INTERNAL, "decode kernel: a helper-wave hand-over wait timed out");
+  // the push is committed
+  st->cur ^= 1;
+  for (int64_t b = 0; b < B; ++b) st->frames[(size_t)b] = hcum[(size_t)b];
+  d->stats = ctcext_stats{};
+  d->stats.tier = st->gs ? 1 : 0;
+  d->stats.record_bytes = st->rec_bytes;
+  d->stats.helper = st->helper;
+  d->stats.kernel = note[0] | (note[1] << 12) | (note[2] << 16);
+  if (prof) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, root.ev[0], root.ev[1]);
+    d->stats.norm_kernel_ms = ms;
+    (void)hipEventElapsedTime(&ms, root.ev[1], root.ev[2]);
+    d->stats.decode_kernel_ms = ms;
+    (void)hipEventElapsedTime(&ms, root.ev[2], root.ev[3]);
+    d->stats.traceback_ms = ms;
+  }
+  for (int64_t b = 0; b < B; ++b) {   // (the kernel carries the counters in the item's header: cumulative)
+    d->stats.literal_frames += io[b].literal_steps;
+    d->stats.literal_nonfinite += io[b].why_nonfinite;
+    d->stats.literal_fill += io[b].why_fill;
+    d->stats.duplicate_frames += io[b].dup_frames;
+    d->stats.records_written += io[b].records;
+  }
+  if (!sizes) return CTCEXT_OK;
+  for (int64_t b = 0; b < B; ++b)
+    if (io[b].n_leaves < P) return fail(CTCEXT_INVALID_ARGUMENT, "Less leaves in the beam search than requested.");
+  const int32_t* kinds = (const int32_t*)d->h_kind.p;
+  for (int64_t q = 0; q < B * P; ++q) d->stats.no_label_paths += (kinds[q] < 0) ? 1 : 0;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctcext_path_sizes* sizes) {
+  if (!st || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  ctcext_decoder* d = st->dec;
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size;
+  const int P = a.top_paths;
+  if (c->flags & ~(CTCEXT_FLAG_TEST_HELPER_DEAD | CTCEXT_FLAG_PROFILE))
+    return fail(CTCEXT_INVALID_ARGUMENT, "chunk flags: CTCEXT_FLAG_TEST_HELPER_DEAD and _PROFILE only");
+  int rc = check_chunk(&a, c, nullptr);
+  if (rc != CTCEXT_OK) return rc;
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = c->stream ? (hipStream_t)c->stream : root.own_stream;
+  // the chunk's lengths are read on the host, as ctcext_decode reads sequence_length
+  std::vector<int32_t> hcl((size_t)B, (int32_t)c->chunk_time);
+  if (B > 0 && c->chunk_length) {
+    if (a.on_device) {
+      HIP_OR_FAIL(hipMemcpyAsync(hcl.data(), c->chunk_length, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+      HIP_OR_FAIL(hipStreamSynchronize(s));
+    } else {
+      memcpy(hcl.data(), c->chunk_length, 4 * (size_t)B);
+    }
+  }
+  rc = check_lengths(hcl.data(), B, c->chunk_time);
+  if (rc != CTCEXT_OK) return rc;
+  for (int64_t b = 0; b < B; ++b) {
+    if (hcl[(size_t)b] < 0) hcl[(size_t)b] = 0;   // (the kernels read a negative length as 0)
+    const int64_t tot = st->frames[(size_t)b] + hcl[(size_t)b];
+    if (tot > a.max_frames)
+      return fail(CTCEXT_INVALID_ARGUMENT, "stream capacity exceeded: item " + std::to_string(b) + " would hold " +
+                                               std::to_string(tot) + " frames of max_frames " +
+                                               std::to_string(a.max_frames));
+  }
+  d->have = false;
+  if (B > 0) {
+    rc = a.dtype == CTCEXT_F32 ? stream_push_t<float>(st, c, hcl, sizes, s) : stream_push_t<double>(st, c, hcl, sizes, s);
+    if (rc != CTCEXT_OK) return rc;
+  }
+  if (!sizes) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  d->B = B;
+  d->sizes.assign((size_t)P, ctcext_path_sizes{0, 0, 0, 0});
+  if (B > 0) {
+    const int64_t* r = (const int64_t*)d->h_res.p;
+    for (int p = 0; p < P; ++p) {
+      d->sizes[p].num_decoded = r[(p * 2 + 0) * 2];
+      d->sizes[p].max_decoded = r[(p * 2 + 0) * 2 + 1];
+      d->sizes[p].num_alignment = r[(p * 2 + 1) * 2];
+      d->sizes[p].max_alignment = r[(p * 2 + 1) * 2 + 1];
+    }
+  }
+  d->have = true;
+  d->dtype = a.dtype;
+  d->T = a.max_frames; d->C = a.num_classes; d->W = a.beam_width; d->P = P;
+  root.s = s;
+  for (int p = 0; p < P; ++p) sizes[p] = d->sizes[p];
   g_err.clear();
   return CTCEXT_OK;
 }

@@ -33,6 +33,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#ifdef CTCX_STREAM
+#include <stddef.h>
+#include <string.h>
+#endif
 
 #include <type_traits>
 #include <utility>
@@ -5369,6 +5373,47 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
   int flushed = 0, nflush = 0, nrec = 0;   // first frame not yet in HBM, flushes, ring stream cursor
   int64_t nrec_all = 0;                    // records written without the ring (T * W can pass 2^31)
 
+#ifdef CTCX_STREAM
+  // A stream's push: sl frames of item b's chunk, on top of the hin.frames the
+  // item has behind it.  Its state at a frame boundary is the whole LDS
+  // allocation (the global-state build: the carve, which already lives in the
+  // stream's HBM buffer) and the scalars of the header.
+  const char* const st_in = prm.st.in + b * prm.st.stride;
+  char* const st_out = prm.st.out + b * prm.st.stride;
+  const CtcxStreamHdr hin = *(const CtcxStreamHdr*)st_in;
+  const int t0g = uni(hin.frames);  // the item's global index of the chunk's first frame
+  const bool resume = t0g > 0;      // (uniform)
+  const size_t st_hdr = ctcx_stream_hdr_bytes(prm.P);
+  if (resume && sl == 0) {
+    // no frame for this item: state and header pass through to the out
+    // buffer, and the item reports the hypotheses it had
+    const size_t n16 = (st_hdr + (size_t)prm.st.image_bytes + 15) >> 4;   // (stride is a multiple of 256)
+    for (size_t q = tid; q < n16; q += NT) ((u32x4*)st_out)[q] = ((const u32x4*)st_in)[q];
+    const int32_t* hp = (const int32_t*)(st_in + sizeof(CtcxStreamHdr));
+    const int64_t* hl = (const int64_t*)(hp + 2 * prm.P);
+    for (int q = tid; q < prm.P; q += NT) {
+      prm.top_pos[b * prm.P + q] = hp[q];
+      prm.top_kind[b * prm.P + q] = hp[prm.P + q];
+      prm.log_prob[b * prm.P + q] = *(const T*)(hl + q);
+    }
+    if (tid == 0) {
+      ItemOut io;
+      io.n_leaves = hin.n_leaves; io.literal_steps = hin.literal_steps; io.dup_frames = hin.dup_frames;
+      io.why_nonfinite = hin.why_nonfinite; io.why_fill = hin.why_fill; io.pad = 0; io.records = hin.records;
+      prm.item[b] = io;
+    }
+    return;
+  }
+#ifndef CTCX_GSTATE
+  if (resume) {   // the image into LDS: 16-byte loads over all threads, then the words the layout's sizes leave over
+    const char* img = st_in + st_hdr;
+    const size_t nby = (size_t)prm.st.image_bytes, n16 = nby >> 4;
+    for (size_t q = tid; q < n16; q += NT) ((CTCX_LDS u32x4*)lds)[q] = ((const u32x4*)img)[q];
+    for (size_t q = (n16 << 2) + tid; q < (nby >> 2); q += NT) ((CTCX_LDS uint32_t*)lds)[q] = ((const uint32_t*)img)[q];
+    __syncthreads();
+  }
+#endif
+#endif
   // Reset(): root with newp.total = newp.blank = 0 (decoder.h:213-227)
   int buf = 0;
   if (tid < 32) cx.etab[tid] = gm::exp2f_tab(tid);
@@ -5377,6 +5422,13 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     // run out of time, so the failure path runs without a hang)
     cx.misc[kCtlDead] = (HW && (prm.test_flags & kTestHelperDead)) ? 1 : 0;
     cx.misc[15] = 0;
+#ifdef CTCX_STREAM
+  }
+  // (the per-launch words above are set after the load; the rest of Reset()
+  // is for an item without frames behind it)
+  if (!resume) {
+  if (tid == 0) {
+#endif
     cx.lab[0][0] = -1; cx.par[0][0] = -1; cx.flg[0][0] = F_ROOT;
     cx.ot[0][0] = T(0); cx.ob[0][0] = T(0); cx.ol[0][0] = ninf<T>();
     cx.cb[0][0] = T(0); cx.cn[0][0] = T(0);
@@ -5395,12 +5447,25 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     CTCX_LDS uint64_t* z = row_cbm(cx);
     for (int k = lane; k < nw + (nw + 63) / 64; k += 64) z[k] = 0ull;
   }
+#ifdef CTCX_STREAM
+  }   // !resume
+#endif
   int nb = 1;
   int literal_steps = 0;
   int why_nf = 0, why_fill = 0, dup_frames = 0;
   bool tiefree = false;  // the previous frame's beam had no tie (kSetMode)
   bool dup = false;   // this frame's beam holds an entry twice (literal frames only)
   int n_leaves = 1;
+#ifdef CTCX_STREAM
+  if (resume) {   // the scalars a frame hands to the next, and the item's counters so far
+    buf = uni(hin.buf); nb = uni(hin.nb); dup = uni(hin.dup) != 0; tiefree = uni(hin.tiefree) != 0;
+    n_leaves = uni(hin.n_leaves); literal_steps = uni(hin.literal_steps); dup_frames = uni(hin.dup_frames);
+    why_nf = uni(hin.why_nonfinite); why_fill = uni(hin.why_fill); nrec_all = (int64_t)uni64((uint64_t)hin.records);
+  }
+#define CTCX_FRAME(t) (t0g + (t))   // the item's global frame index: where a record lives
+#else
+#define CTCX_FRAME(t) (t)
+#endif
   __syncthreads();
 
 #ifdef CTCX_PHASES
@@ -5661,11 +5726,11 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
       if constexpr (SC::kStateful) sel(cx.est, nx)[k] = cx.eest[e];
       const uint32_t bpb = (ef & F_HB) ? cx.ebpb[e] : kBpNone, bpn = (ef & F_HN) ? cx.ebpn[e] : kBpNone;
 #ifdef CTCX_GSTATE
-      ((Rec16*)prm.rec)[((int64_t)b * prm.Tmax + t) * W + k] = Rec16{kd, cx.elab[e], bpb, bpn};
+      ((Rec16*)prm.rec)[((int64_t)b * prm.Tmax + CTCX_FRAME(t)) * W + k] = Rec16{kd, cx.elab[e], bpb, bpn};
 #else
       const RT rc = RecOps<RT>::pack(kd, cx.elab[e], bpb, bpn);
       if (R > 0) rg.rec[(t & (R - 1)) * W + k] = rc;
-      else rstream[(int64_t)t * W + k] = rc;
+      else rstream[(int64_t)CTCX_FRAME(t) * W + k] = rc;
 #endif
     };
     if constexpr (STAGED) {
@@ -5799,7 +5864,37 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     prm.top_pos[b * prm.P + q] = opos;
     prm.top_kind[b * prm.P + q] = kind;
     prm.log_prob[b * prm.P + q] = lp;
+#ifdef CTCX_STREAM
+    {   // ... and into the header, for a later push that brings this item no frame
+      int32_t* hp = (int32_t*)(st_out + sizeof(CtcxStreamHdr));
+      int64_t* hl = (int64_t*)(hp + 2 * prm.P);
+      hp[q] = opos;
+      hp[prm.P + q] = kind;
+      hl[q] = 0;
+      *(T*)(hl + q) = lp;
+    }
+#endif
   }
+#ifdef CTCX_STREAM
+  if (tid == 0) {
+    CtcxStreamHdr ho{};
+    ho.frames = t0g + sl;
+    ho.buf = buf; ho.nb = nb; ho.dup = dup ? 1 : 0; ho.tiefree = tiefree ? 1 : 0;
+    ho.n_leaves = n_leaves; ho.literal_steps = literal_steps; ho.dup_frames = dup_frames;
+    ho.why_nonfinite = why_nf; ho.why_fill = why_fill; ho.records = nrec_all;
+    *(CtcxStreamHdr*)st_out = ho;
+  }
+#ifndef CTCX_GSTATE
+  {
+    // the image: the whole LDS allocation as the chunk's last commit left it
+    // (every wave is past the loop's closing barrier; nothing below writes LDS)
+    char* img = st_out + st_hdr;
+    const size_t nby = (size_t)prm.st.image_bytes, n16 = nby >> 4;
+    for (size_t q = tid; q < n16; q += NT) ((u32x4*)img)[q] = ((const CTCX_LDS u32x4*)lds)[q];
+    for (size_t q = (n16 << 2) + tid; q < (nby >> 2); q += NT) ((uint32_t*)img)[q] = ((const CTCX_LDS uint32_t*)lds)[q];
+  }
+#endif
+#endif
   if (tid == 0) {
     ItemOut io;
     io.n_leaves = n_leaves;
@@ -7156,6 +7251,16 @@ hipError_t launch_decode_c(const DecodeParams<T>& p, hipStream_t s) {
           ((SQ && !BIG) ? sq_ctab_bytes(WC, 0) : 0);
   if (p.ring > 0) lds = ((lds + 15) & ~(size_t)15) + ring_lds_bytes(p.ring, p.W, HW && !BIG ? 4 : 8);
   if (lds > kLdsBytes) return hipErrorInvalidValue;
+#ifdef CTCX_STREAM
+  // the image is this allocation: the host asks for its size at open (query),
+  // and a push must bring exactly that (a stream runs one kernel for its life)
+  if (p.st.query) {
+    *p.st.query = (int64_t)lds;
+    ctcx_launch_note()[0] = ctcx_decode_kernel_id(false, (int)sizeof(T), SC::kStateful, RN, WC, BIG, HW, SQ) | kStreamKernelBit;
+    return hipSuccess;
+  }
+  if (p.ring != 0 || p.st.image_bytes != (int64_t)lds) return hipErrorInvalidValue;
+#endif
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)ctcx_beam_decode<T, RN, WC, BIG, SC, HW, SQ>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -7164,6 +7269,9 @@ hipError_t launch_decode_c(const DecodeParams<T>& p, hipStream_t s) {
   hipLaunchKernelGGL((ctcx_beam_decode<T, RN, WC, BIG, SC, HW, SQ>), dim3((unsigned)p.B), dim3(HW ? 128 : 64), lds,
                      s, p);
   ctcx_launch_note()[0] = ctcx_decode_kernel_id(false, (int)sizeof(T), SC::kStateful, RN, WC, BIG, HW, SQ);
+#ifdef CTCX_STREAM
+  ctcx_launch_note()[0] |= kStreamKernelBit;
+#endif
   return hipGetLastError();
 }
 
@@ -7629,10 +7737,14 @@ template <typename T, class SC>
 static hipError_t launch_decode_gs_t(const DecodeParams<T>& p, hipStream_t s) {
   hipLaunchKernelGGL((ctcx_beam_decode<T, 1, 0, false, SC, false>), dim3((unsigned)p.B), dim3(64), 0, s, p);
   ctcx_launch_note()[0] = ctcx_decode_kernel_id(true, (int)sizeof(T), SC::kStateful, 1, 0, false, false, false);
+#ifdef CTCX_STREAM
+  ctcx_launch_note()[0] |= kStreamKernelBit;
+#endif
   return hipGetLastError();
 }
 }  // namespace ctcx
 
+#ifndef CTCX_STREAM
 // Called by the C-ABI layer with its DecodeParams<T> (the same header, so the
 // same layout, in namespace ctcx there).
 hipError_t ctcx_gstate_launch_decode(const void* p, int is_f64, int scored, hipStream_t s) {
@@ -7647,4 +7759,98 @@ hipError_t ctcx_gstate_launch_decode(const void* p, int is_f64, int scored, hipS
   return scored ? ctcx::launch_decode_gs_t<float, ctcx::BigramBeamScorer<float>>(q, s)
                 : ctcx::launch_decode_gs_t<float, ctcx::BaseBeamScorer<float>>(q, s);
 }
+#endif  // !CTCX_STREAM
 #endif
+
+#ifdef CTCX_STREAM
+// ---------------------------------------------------------------------------
+// The stream builds (this file compiled once more per part with CTCX_STREAM,
+// namespace ctcx_st, and once more as the global-state tier with both macros,
+// namespace ctcx_gs_st; csrc/Makefile).  The C-ABI layer passes its
+// DecodeParams<T> -- the default build's struct, which is this one without
+// its last member -- and the stream's parameters beside it.
+namespace ctcx {
+template <typename T>
+static DecodeParams<T> stream_params(const void* p, const CtcxStreamParams* sp) {
+  static_assert(offsetof(DecodeParams<T>, st) + sizeof(CtcxStreamParams) == sizeof(DecodeParams<T>), "st is the last member");
+  static_assert(offsetof(DecodeParams<T>, st) == kCtcxDecodeParamsBytes, "the host layer's DecodeParams<T> ends where st begins");
+  DecodeParams<T> q{};
+  memcpy((void*)&q, p, offsetof(DecodeParams<T>, st));
+  q.st = *sp;
+  return q;
+}
+}  // namespace ctcx
+
+#ifdef CTCX_GSTATE
+hipError_t ctcx_gstate_stream_launch_decode(const void* p, const CtcxStreamParams* sp, int is_f64, int scored,
+                                            hipStream_t s) {
+  if (is_f64) {
+    const auto q = ctcx::stream_params<double>(p, sp);
+    if (q.B == 0) return hipSuccess;
+    return scored ? ctcx::launch_decode_gs_t<double, ctcx::BigramBeamScorer<double>>(q, s)
+                  : ctcx::launch_decode_gs_t<double, ctcx::BaseBeamScorer<double>>(q, s);
+  }
+  const auto q = ctcx::stream_params<float>(p, sp);
+  if (q.B == 0) return hipSuccess;
+  return scored ? ctcx::launch_decode_gs_t<float, ctcx::BigramBeamScorer<float>>(q, s)
+                : ctcx::launch_decode_gs_t<float, ctcx::BaseBeamScorer<float>>(q, s);
+}
+#elif CTCX_PART == 14
+// Part 14 of the stream build: the dispatcher over the instantiations of
+// parts 1..13 (launch_decode's choices, with the two-wave kernel as the host
+// decided it in p.helper at open).
+namespace ctcx {
+#define CTCX_X(P, T, RN, WC, BIG, SC) \
+  extern template hipError_t launch_decode_c<T, RN, WC, BIG, SC>(const DecodeParams<T>&, hipStream_t);
+CTCX_DECODE_INSTANCES(CTCX_X)
+#undef CTCX_X
+extern template hipError_t launch_decode_c<float, 1, 128, false, BaseBeamScorer<float>, true>(
+    const DecodeParams<float>&, hipStream_t);
+extern template hipError_t launch_decode_c<float, 1, 128, true, BaseBeamScorer<float>, true>(
+    const DecodeParams<float>&, hipStream_t);
+extern template hipError_t launch_decode_c<float, 2, 256, true, BaseBeamScorer<float>, true>(
+    const DecodeParams<float>&, hipStream_t);
+extern template hipError_t launch_decode_c<float, 1, 128, false, BaseBeamScorer<float>, true, true>(
+    const DecodeParams<float>&, hipStream_t);
+extern template hipError_t launch_decode_c<float, 1, 128, true, BaseBeamScorer<float>, true, true>(
+    const DecodeParams<float>&, hipStream_t);
+extern template hipError_t launch_decode_c<float, 2, 256, true, BaseBeamScorer<float>, true, true>(
+    const DecodeParams<float>&, hipStream_t);
+
+template <typename T, int RN, int WC, class SC>
+static hipError_t stream_decode_r(const DecodeParams<T>& p, hipStream_t s) {
+  return p.C > 64 ? launch_decode_c<T, RN, WC, true, SC>(p, s) : launch_decode_c<T, RN, WC, false, SC>(p, s);
+}
+template <typename T, class SC>
+static hipError_t stream_decode_w(const DecodeParams<T>& p, hipStream_t s) {
+  auto fits = [&](int wc) { return decode_lds_bytes(wc, p.C, (int)sizeof(T), SC::kStateful) <= kLdsBytes; };
+  if (p.W <= 128) return fits(128) ? stream_decode_r<T, 1, 128, SC>(p, s) : stream_decode_r<T, 1, 0, SC>(p, s);
+  if (p.W <= 256) return fits(256) ? stream_decode_r<T, 2, 256, SC>(p, s) : stream_decode_r<T, 2, 0, SC>(p, s);
+  return stream_decode_r<T, 4, 0, SC>(p, s);
+}
+template <typename T>
+static hipError_t stream_decode(const DecodeParams<T>& p, hipStream_t s) {
+  if (p.B == 0 && !p.st.query) return hipSuccess;
+  if (p.scorer_tab) return stream_decode_w<T, BigramBeamScorer<T>>(p, s);
+  if constexpr (sizeof(T) == 4) {
+    const int hk = p.helper;
+    using SC = BaseBeamScorer<float>;
+    if (hk == 1) return launch_decode_c<float, 1, 128, false, SC, true>(p, s);
+    if (hk == 2)
+      return p.W <= 128 ? launch_decode_c<float, 1, 128, true, SC, true>(p, s)
+                        : launch_decode_c<float, 2, 256, true, SC, true>(p, s);
+    if (hk == 3)
+      return p.C <= 64   ? launch_decode_c<float, 1, 128, false, SC, true, true>(p, s)
+             : p.W <= 128 ? launch_decode_c<float, 1, 128, true, SC, true, true>(p, s)
+                          : launch_decode_c<float, 2, 256, true, SC, true, true>(p, s);
+  }
+  return stream_decode_w<T, BaseBeamScorer<T>>(p, s);
+}
+}  // namespace ctcx
+
+hipError_t ctcx_stream_launch_decode(const void* p, const CtcxStreamParams* sp, int is_f64, hipStream_t s) {
+  if (is_f64) return ctcx::stream_decode<double>(ctcx::stream_params<double>(p, sp), s);
+  return ctcx::stream_decode<float>(ctcx::stream_params<float>(p, sp), s);
+}
+#endif
+#endif  // CTCX_STREAM

@@ -30,6 +30,39 @@ constexpr int ctcx_decode_kernel_id(bool gstate, int tsize, bool scored, int RN,
 constexpr int kPrepFactsFused = 1, kPrepFactsNorm = 2, kPrepRowLds = 3, kPrepRowGlobal = 4, kPrepNormOnly = 5;
 constexpr int kTbSegmented = 1, kTbOneThread = 2;
 
+#if defined(CTCX_STREAM) || defined(CTCX_STREAM_HOST)
+// Streaming decode (the CTCX_STREAM builds of ctcx_decode.hip; the host layer
+// sees the declarations through CTCX_STREAM_HOST).  A stream keeps, per item
+// and twice (the push reads one buffer and writes the other; the host swaps
+// them when the push succeeded), ctcx_stream_hdr_bytes(P) of header followed
+// by the image of the decode kernel's whole dynamic LDS allocation:
+//   StreamHdr | top_pos[P] | top_kind[P] | log_prob[P] (8 bytes each) | image
+// frames == 0 is an item without state: the kernel runs Reset() for it.
+constexpr int kStreamKernelBit = 0x8000;   // = CTCEXT_KERNEL_STREAM
+// The host layer hands the stream launchers its DecodeParams<T>, which is the
+// stream builds' struct without its last member (st).  Both sides assert this
+// size (the host its sizeof, the stream builds st's offset), so that a field
+// added to one of them cannot make the launcher read past the caller's struct.
+constexpr size_t kCtcxDecodeParamsBytes = 200;
+struct CtcxStreamHdr {
+  int32_t frames;         // frames decoded so far (the item's global index of the chunk's first frame)
+  int32_t buf, nb, dup;   // the kernel's frame-boundary scalars: branch buffer, beam size, duplicate entries
+  int32_t n_leaves, literal_steps, dup_frames, why_nonfinite, why_fill;
+  int32_t tiefree;        // (kSetMode builds)
+  int64_t records;
+  int32_t pad[4];
+};
+static_assert(sizeof(CtcxStreamHdr) == 64, "CtcxStreamHdr layout");
+__host__ __device__ inline size_t ctcx_stream_hdr_bytes(int P) { return (64 + 16 * (size_t)P + 15) & ~(size_t)15; }
+struct CtcxStreamParams {
+  const char* in;         // item b's state at in + b * stride (read)
+  char* out;              // ... and at out + b * stride (written); the global-state build keeps headers only
+  int64_t stride;
+  int64_t image_bytes;    // the launch's dynamic LDS bytes (0 in the global-state build)
+  int64_t* query;         // host only: non-null makes the launcher report its LDS bytes here and launch nothing
+};
+#endif
+
 namespace ctcx {
 
 // CTCEXT_FLAG_PHASES counters per item: 0 row load, 1 recursion, 2 grow,
@@ -168,6 +201,13 @@ struct DecodeParams {
   int32_t helper;
   int32_t test_flags;       // kTestHelperDead: the helper wave starts out "timed out" (tests only)
   int32_t xfmt;             // kInNative (elements of T), kInF16, kInBF16 (T = float; widened by the row stage)
+#ifdef CTCX_STREAM
+  // stream builds only (the default build's kernel arguments stay as they
+  // are).  There seq_len holds the chunk's frames per item, x / norm / prep
+  // the chunk's rows, Tmax the stream's capacity (rec is [B][Tmax][W] for the
+  // stream's life) and ring is 0.
+  CtcxStreamParams st;
+#endif
 };
 // element formats of x (= CTCEXT_IN_*)
 constexpr int32_t kInNative = 0, kInF16 = 1, kInBF16 = 2;

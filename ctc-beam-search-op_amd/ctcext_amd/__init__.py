@@ -3,9 +3,9 @@ tracking; a drop-in for prouast/ctc-beam-search-op's
 ``ctc_ext_beam_search_decoder`` (tensorflow_ctc_ext_beam_search_decoder/__init__.py:19).
 """
 from .ops import (CTCExtBeamSearchDecoder, Decoder, FailedPreconditionError, InternalError,
-                  InvalidArgumentError, OpError, UnimplementedError, ctc_ext_beam_search_decoder,
+                  InvalidArgumentError, OpError, StreamDecoder, UnimplementedError, ctc_ext_beam_search_decoder,
                   decode_logits, get_decoder)
 
-__all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder",
+__all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

@@ -39,7 +39,10 @@ CTCEXT_SCORER_BIGRAM = 1
 EXPORTED_SYMBOLS = ("ctcext_create", "ctcext_create_sharded", "ctcext_destroy", "ctcext_validate",
                     "ctcext_decode", "ctcext_decode_sharded", "ctcext_fetch", "ctcext_get_stats",
                     "ctcext_last_error", "ctcext_max_beam_width", "ctcext_phase_counters", "ctcext_row_facts",
-                    "ctcext_get_stats_sized", "ctcext_abi_version")
+                    "ctcext_get_stats_sized", "ctcext_abi_version",
+                    "ctcext_stream_validate", "ctcext_stream_validate_chunk", "ctcext_stream_open",
+                    "ctcext_stream_push", "ctcext_stream_frames", "ctcext_stream_reset", "ctcext_stream_close")
+CTCEXT_KERNEL_STREAM = 0x8000   # ctcext_stats.kernel: a stream build of the decode kernel
 
 
 class DecodeArgs(ctypes.Structure):
@@ -57,6 +60,26 @@ class DecodeArgs(ctypes.Structure):
                 # ABI 7 (all zero: the dense [max_time, batch, num_classes] tensor of dtype)
                 ("inputs_format", ctypes.c_int32), ("pad2_", ctypes.c_int32),
                 ("inputs_stride_t", ctypes.c_int64), ("inputs_stride_b", ctypes.c_int64)]
+
+
+class StreamArgs(ctypes.Structure):
+    """ctcext_stream_args: a stream's attributes, fixed for its life."""
+    _fields_ = [("dtype", ctypes.c_int32), ("on_device", ctypes.c_int32),
+                ("batch_size", ctypes.c_int64), ("num_classes", ctypes.c_int64),
+                ("max_frames", ctypes.c_int64),
+                ("beam_width", ctypes.c_int32), ("top_paths", ctypes.c_int32),
+                ("merge_repeated", ctypes.c_int32), ("blank_index", ctypes.c_int32),
+                ("blank_label", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("scorer", ctypes.c_int32), ("pad_", ctypes.c_int32), ("scorer_table", ctypes.c_void_p)]
+
+
+class Chunk(ctypes.Structure):
+    """ctcext_chunk: one push of a stream."""
+    _fields_ = [("inputs", ctypes.c_void_p), ("chunk_length", ctypes.c_void_p),
+                ("chunk_time", ctypes.c_int64),
+                ("inputs_format", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("inputs_stride_t", ctypes.c_int64), ("inputs_stride_b", ctypes.c_int64),
+                ("stream", ctypes.c_void_p)]
 
 
 class PathSizes(ctypes.Structure):
@@ -97,6 +120,7 @@ def decode_kernel_stat(k):
     return {"launched": bool(k & 0x800), "tier": (k >> 10) & 1, "dtype": "f64" if k & 0x200 else "f32",
             "scorer": "bigram" if k & 0x100 else "base", "RN": (k >> 2) & 7, "WC": ((k >> 5) & 3) * 128,
             "BIG": bool(k & 0x80), "helper": "SQ" if k & 2 else "HW" if k & 1 else "none",
+            "stream": bool(k & CTCEXT_KERNEL_STREAM),
             "prepass": PREPASS_NAMES[(k >> 12) & 7], "traceback": TRACEBACK_NAMES[(k >> 16) & 3]}
 
 
@@ -152,6 +176,21 @@ def load():
                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
         lib.ctcext_row_facts.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_stream_open"):   # (CTCEXT_HAS_STREAM; older builds stay loadable for A/B runs)
+        lib.ctcext_stream_validate.argtypes = [ctypes.POINTER(StreamArgs)]
+        lib.ctcext_stream_validate.restype = ctypes.c_int
+        lib.ctcext_stream_validate_chunk.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(Chunk)]
+        lib.ctcext_stream_validate_chunk.restype = ctypes.c_int
+        lib.ctcext_stream_open.argtypes = [ctypes.c_void_p, ctypes.POINTER(StreamArgs), ctypes.POINTER(ctypes.c_void_p)]
+        lib.ctcext_stream_open.restype = ctypes.c_int
+        lib.ctcext_stream_push.argtypes = [ctypes.c_void_p, ctypes.POINTER(Chunk), ctypes.POINTER(PathSizes)]
+        lib.ctcext_stream_push.restype = ctypes.c_int
+        lib.ctcext_stream_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.ctcext_stream_frames.restype = ctypes.c_int
+        lib.ctcext_stream_reset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        lib.ctcext_stream_reset.restype = ctypes.c_int
+        lib.ctcext_stream_close.argtypes = [ctypes.c_void_p]
+        lib.ctcext_stream_close.restype = None
     _lib = lib
     return lib
 

@@ -432,9 +432,277 @@ def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index
         import torch
         torch.cuda.current_stream(device).synchronize()
     sizes = dec.decode(a)
-    P = int(top_paths)
-    B = int(shape[1])
-    if outputs == "device" or (outputs == "auto" and on_device):
+    out = _fetch_outputs(dec, sizes, int(shape[1]), int(top_paths), code,
+                         outputs == "device" or (outputs == "auto" and on_device))
+    del keep
+    _print_no_label(dec.last_stats["no_label_paths"])
+    return out
+
+
+def _host_empty():
+    """Host output allocator: numpy views of pinned torch CPU tensors (the
+    caching host allocator reuses the pinned pages, so the GPU copies the
+    components down at full PCIe rate without first-touch page faults), or
+    plain numpy without torch."""
+    try:
+        import torch
+        if torch.cuda.is_available():
+            tdt = {np.dtype(np.int64): torch.int64, np.dtype(np.float32): torch.float32,
+                   np.dtype(np.float64): torch.float64}
+
+            def empty(shape, dt):
+                return torch.empty(shape, dtype=tdt[np.dtype(dt)], pin_memory=True).numpy()
+            return empty
+    except ImportError:
+        pass
+    return np.empty
+
+
+class StreamDecoder:
+    """Streaming decode: push the logits of a batch in chunks of frames and
+    read, after each push, the hypotheses of everything pushed so far --
+    bit for bit what ``decode_logits`` returns for that prefix.
+
+        s = StreamDecoder(batch_size, num_classes, beam_width, top_paths, max_frames)
+        for chunk in chunks:              # [B, t, C] each (batch_first), t may vary
+            out = s.push(chunk, lengths)  # lengths: frames of this chunk per item (None: all t)
+        s.reset([1])                      # item 1 starts a new utterance; the others go on
+        s.close()                         # or use it as a context manager
+
+    ``max_frames`` is the capacity per item: the beam records of that many
+    frames are kept on the device.  ``dtype`` is the compute and output type;
+    ``"float32"`` streams take float16 / bfloat16 / float32 chunks, ``"float64"``
+    ones float64.  Chunks are torch tensors (GPU or host) or numpy arrays, as
+    ``decode_logits`` takes them, strided views included; whether they live on
+    the device or the host is fixed by the first push.  The decode kernel is
+    chosen at that moment (dtype, scorer, num_classes, beam_width and the
+    ``CTCEXT_HELPER`` environment variable) and stays for the stream's life.
+    """
+
+    def __init__(self, batch_size, num_classes, beam_width, top_paths, max_frames, *,
+                 dtype="float32", merge_repeated=False, blank_index=0, blank_label=-1,
+                 device=None, scorer_table=None, flags=0):
+        self.lib = _lib.load()
+        name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
+        if name not in ("float32", "float64"):
+            _type_error("dtype", name, "float32, float64")
+        self._np_dtype = np.dtype(name)
+        a = _lib.StreamArgs()
+        a.dtype = _lib.CTCEXT_F32 if name == "float32" else _lib.CTCEXT_F64
+        a.batch_size, a.num_classes, a.max_frames = int(batch_size), int(num_classes), int(max_frames)
+        a.beam_width, a.top_paths = int(beam_width), int(top_paths)
+        a.merge_repeated = 1 if merge_repeated else 0
+        a.blank_index, a.blank_label, a.flags = int(blank_index), int(blank_label), int(flags)
+        self._args = a
+        self._table = None
+        if scorer_table is not None:
+            tab = np.ascontiguousarray(np.asarray(
+                scorer_table.detach().cpu().numpy() if _is_torch(scorer_table) else scorer_table,
+                dtype=self._np_dtype))
+            C = int(num_classes)
+            if tuple(tab.shape) != (C + 1, C):
+                raise ValueError("scorer_table must be [num_classes + 1, num_classes] = [%d, %d], got %s"
+                                 % (C + 1, C, tuple(tab.shape)))
+            self._table = tab
+            a.scorer = _lib.CTCEXT_SCORER_BIGRAM
+            a.scorer_table = tab.ctypes.data   # (host memory wherever the chunks live: ctcext.h)
+        # the attribute checks run on the host now; the stream itself opens
+        # with the first push, which fixes where the chunks live
+        rc = self.lib.ctcext_stream_validate(ctypes.byref(a))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        self._device = _device_index(device)
+        self.dec = None
+        self.handle = None
+        self.on_device = None
+        self.closed = False
+        self.last_stats = None
+
+    # -- lifetime ----------------------------------------------------------
+    def _open(self, on_device, index):
+        if self._device is not None:
+            if on_device and index != self._device:
+                raise ValueError("the chunk lives on cuda:%d, the stream on cuda:%d" % (index, self._device))
+            index = self._device
+        self.dec = get_decoder(index if index is not None else _current_device())
+        a = self._args
+        a.on_device = 1 if on_device else 0
+        h = ctypes.c_void_p()
+        rc = self.lib.ctcext_stream_open(self.dec.handle, ctypes.byref(a), ctypes.byref(h))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        self.handle = h
+        self.on_device = on_device
+
+    def close(self):
+        if self.handle and self.dec is not None and self.dec.handle:
+            self.lib.ctcext_stream_close(self.handle)
+        self.handle = None
+        self.closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_open(self):
+        if self.closed:
+            raise FailedPreconditionError("the stream is closed", _lib.CTCEXT_FAILED_PRECONDITION)
+
+    @property
+    def frames(self):
+        """Frames pushed so far per item: numpy int64 [batch_size]."""
+        self._check_open()
+        out = np.zeros((int(self._args.batch_size),), np.int64)
+        if self.handle:
+            rc = self.lib.ctcext_stream_frames(self.handle, out.ctypes.data)
+            if rc != _lib.CTCEXT_OK:
+                _raise(self.lib, rc)
+        return out
+
+    def reset(self, items=None):
+        """Put ``items`` (None: all) back to no frames; the others are untouched."""
+        self._check_open()
+        if not self.handle:
+            return
+        if items is None:
+            rc = self.lib.ctcext_stream_reset(self.handle, None, 0)
+        else:
+            arr = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1))
+            rc = self.lib.ctcext_stream_reset(self.handle, arr.ctypes.data, int(arr.size))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+
+    # -- push ---------------------------------------------------------------
+    def push(self, chunk, lengths=None, *, batch_first=True, results=True, outputs="auto", flags=0):
+        """Decode ``chunk`` (``[B, t, C]`` with ``batch_first``, else ``[t, B, C]``)
+        on top of what the stream holds.  ``lengths``: frames of this chunk per
+        item, 0..t (None: t for all).  Returns the ``CTCExtBeamSearchDecoder``
+        tuple of the prefix pushed so far, or None with ``results=False``
+        (no traceback, no outputs: the cheap push between two reads)."""
+        self._check_open()
+        if outputs not in ("auto", "host", "device"):
+            raise ValueError("outputs must be 'auto', 'host' or 'device'")
+        lib = self.lib
+        a = self._args
+        allowed = "float16, bfloat16, float32" if a.dtype == _lib.CTCEXT_F32 else "float64"
+        if _is_torch(chunk):
+            import torch
+            formats = {torch.float16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+                       torch.bfloat16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_BF16),
+                       torch.float32: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+                       torch.float64: (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+            if chunk.dtype not in formats:
+                _type_error("chunk", str(chunk.dtype).replace("torch.", ""), allowed)
+            x = chunk.detach()
+            strides = x.stride()
+            dname = str(x.dtype).replace("torch.", "")
+        else:
+            x = chunk if isinstance(chunk, np.ndarray) else np.asarray(chunk, dtype=self._np_dtype)
+            formats = {np.dtype(np.float16): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+                       np.dtype(np.float32): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+                       np.dtype(np.float64): (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+            if x.dtype not in formats:
+                _type_error("chunk", x.dtype.name, allowed)
+            strides = tuple(s // x.itemsize if s % x.itemsize == 0 else 0 for s in x.strides)
+            dname = x.dtype.name
+        code, fmt = formats[x.dtype]
+        if fmt == _lib.CTCEXT_IN_NATIVE and code != a.dtype:
+            _type_error("chunk", dname, allowed)
+        if len(x.shape) != 3:
+            raise InvalidArgumentError("inputs is not a 3-Tensor", _lib.CTCEXT_INVALID_ARGUMENT)
+        copy, shape, st_t, st_b = logits_layout(tuple(x.shape), strides, batch_first)
+        if (shape[1], shape[2]) != (a.batch_size, a.num_classes):
+            raise InvalidArgumentError("chunk has batch_size %d and num_classes %d, the stream %d and %d"
+                                       % (shape[1], shape[2], a.batch_size, a.num_classes),
+                                       _lib.CTCEXT_INVALID_ARGUMENT)
+        if copy:
+            x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
+        if shape[0] == 0:   # no frame: nothing is addressed, whatever strides an empty view reports
+            st_t = st_b = 0
+        on_device = bool(_is_torch(x) and x.is_cuda)
+        if self.on_device is not None and on_device != self.on_device:
+            raise ValueError("this stream's chunks live on the %s (fixed by its first push)"
+                             % ("device" if self.on_device else "host"))
+        c = _lib.Chunk()
+        c.chunk_time = int(shape[0])
+        c.inputs_format, c.flags = fmt, int(flags)
+        c.inputs_stride_t, c.inputs_stride_b = int(st_t), int(st_b)
+        sl = None
+        if on_device:
+            dev = x.device
+            index = dev.index if dev.index is not None else torch.cuda.current_device()
+            if lengths is not None:
+                sl = _lengths_device(lengths, dev)
+                c.chunk_length = sl.data_ptr()
+            c.inputs = x.data_ptr()
+            c.stream = torch.cuda.current_stream(dev).cuda_stream
+        else:
+            dev = index = None
+            if lengths is not None:
+                sl = _lengths_host(lengths)
+                c.chunk_length = sl.ctypes.data
+            c.inputs = x.data_ptr() if _is_torch(x) else x.ctypes.data
+        if sl is not None and tuple(sl.shape) != (int(a.batch_size),):
+            raise FailedPreconditionError("len(sequence_length) != batch_size.  len(sequence_length):  %d batch_size: %d"
+                                          % (sl.shape[0] if len(sl.shape) else 0, a.batch_size),
+                                          _lib.CTCEXT_FAILED_PRECONDITION)
+        if not self.handle:
+            # host-side checks of the first chunk before the stream opens
+            a.on_device = 1 if on_device else 0
+            rc = lib.ctcext_stream_validate_chunk(ctypes.byref(a), ctypes.byref(c))
+            if rc != _lib.CTCEXT_OK:
+                _raise(lib, rc)
+            self._open(on_device, index)
+        dec = self.dec
+        if on_device and not c.stream:
+            import torch
+            torch.cuda.current_stream(dev).synchronize()   # (see _decode_and_fetch)
+        P = int(a.top_paths)
+        sizes = (_lib.PathSizes * max(P, 1))() if results else None
+        rc = lib.ctcext_stream_push(self.handle, ctypes.byref(c), sizes)
+        self.last_stats = dec.last_stats = dec.stats()
+        if rc != _lib.CTCEXT_OK:
+            _raise(lib, rc)
+        del x, sl
+        if not results:
+            return None
+        szs = [(s.num_decoded, s.max_decoded, s.num_alignment, s.max_alignment) for s in sizes]
+        out = _fetch_outputs(dec, szs, int(a.batch_size), P, a.dtype,
+                             outputs == "device" or (outputs == "auto" and on_device))
+        _print_no_label(dec.last_stats["no_label_paths"])
+        return out
+
+
+def _device_index(device):
+    """``device`` (None, an ordinal, a ``torch.device`` or a string such as
+    "cuda:1") as a device ordinal, or None when it names none."""
+    if device is None:
+        return None
+    if isinstance(device, (int, np.integer)) and not isinstance(device, bool):
+        return int(device)
+    import torch
+    if isinstance(device, (str, torch.device)):
+        d = torch.device(device)
+        if d.type != "cuda":
+            raise ValueError("a StreamDecoder runs on a GPU: device must be a cuda device, not %r" % (device,))
+        return d.index
+    raise TypeError("device must be None, an int, a torch.device or a string, not %s" % type(device).__name__)
+
+
+def _fetch_outputs(dec, sizes, B, P, code, to_device):
+    """Phase 2 for a decoder whose fetch state a decode or a stream push has
+    set: allocate the seven outputs (device tensors on the decoder's device, or
+    pinned host arrays) from the per-path ``sizes`` and fill them."""
+    if to_device:
         import torch
         dev = torch.device("cuda", dec.device)
         i64 = dict(dtype=torch.int64, device=dev)
@@ -459,25 +727,4 @@ def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index
         lp = empty((B, P), fdt)
         lists = [[t.ctypes.data for t in lst] for lst in (di, dv, ds, ai, av, ash)]
         dec.fetch(lists, lp.ctypes.data, False)
-    del keep
-    _print_no_label(dec.last_stats["no_label_paths"])
     return CTCExtBeamSearchDecoder(di, dv, ds, ai, av, ash, lp)
-
-
-def _host_empty():
-    """Host output allocator: numpy views of pinned torch CPU tensors (the
-    caching host allocator reuses the pinned pages, so the GPU copies the
-    components down at full PCIe rate without first-touch page faults), or
-    plain numpy without torch."""
-    try:
-        import torch
-        if torch.cuda.is_available():
-            tdt = {np.dtype(np.int64): torch.int64, np.dtype(np.float32): torch.float32,
-                   np.dtype(np.float64): torch.float64}
-
-            def empty(shape, dt):
-                return torch.empty(shape, dtype=tdt[np.dtype(dt)], pin_memory=True).numpy()
-            return empty
-    except ImportError:
-        pass
-    return np.empty

@@ -193,6 +193,7 @@ typedef struct {
  *   bit 10      the global-state tier's kernel (ctcext_stats.tier == 1)
  *   bit 11      a decode kernel was launched
  *   bits 12..14 the pre-pass, CTCEXT_PREPASS_*
+ *   bit 15      a stream build of the decode kernel (CTCEXT_KERNEL_STREAM, below)
  *   bits 16..17 the traceback, CTCEXT_TRACEBACK_* */
 #define CTCEXT_KERNEL_HW 0x1
 #define CTCEXT_KERNEL_SQ 0x2
@@ -293,6 +294,80 @@ const char* ctcext_last_error(void);
  * HBM, 16-byte records, the literal path every frame): any shape the
  * reference accepts, at a lower rate. */
 int32_t ctcext_max_beam_width(int64_t num_classes, int32_t dtype);
+
+/* ---------------------------------------------------------------------------
+ * Streaming decode.  A stream keeps the beam of every item of a batch between
+ * calls: the caller pushes the logits in chunks of frames, and after each push
+ * ctcext_fetch on the owning decoder returns the hypotheses of everything
+ * pushed so far -- bit for bit what ctcext_decode returns for that prefix.
+ * New entry points and structs only (CTCEXT_ABI_VERSION is unchanged; detect
+ * them by CTCEXT_HAS_STREAM at build time or by symbol at run time).
+ *
+ * One device per stream: a handle of ctcext_create_sharded with more than one
+ * device answers CTCEXT_UNIMPLEMENTED.  Several streams may be open on one
+ * decoder; they are independent, only the fetch state (the last push with
+ * sizes != NULL, or the last ctcext_decode) is the decoder's.  The decode
+ * kernel is chosen once at open (dtype, scorer, num_classes, beam_width and
+ * the CTCEXT_HELPER environment variable as read then) and runs for the
+ * stream's life, without the record ring. */
+#define CTCEXT_HAS_STREAM 1
+#define CTCEXT_KERNEL_STREAM 0x8000   /* ctcext_stats.kernel bit 15: a stream build of the decode kernel */
+
+typedef struct ctcext_stream ctcext_stream;
+
+typedef struct {            /* fixed for the stream's life */
+  int32_t dtype;            /* CTCEXT_F32 / CTCEXT_F64 */
+  int32_t on_device;        /* chunks and lengths are device pointers on the decoder's device */
+  int64_t batch_size, num_classes;
+  int64_t max_frames;       /* capacity per item: records for this many frames are allocated */
+  int32_t beam_width, top_paths, merge_repeated, blank_index, blank_label;
+  int32_t flags;            /* CTCEXT_FLAG_FORCE_LITERAL, _GLOBAL_STATE, _PROFILE */
+  int32_t scorer; int32_t pad_;
+  const void* scorer_table; /* CTCEXT_SCORER_BIGRAM: [num_classes + 1][num_classes] of dtype, in HOST
+                               memory whatever on_device says (unlike ctcext_decode_args): its entries
+                               are checked by ctcext_stream_validate and it is copied at open */
+} ctcext_stream_args;
+
+typedef struct {
+  const void* inputs;       /* [chunk_time, batch, num_classes], or through format/strides as in ctcext_decode_args */
+  const int32_t* chunk_length; /* [batch]: frames of this chunk per item, 0..chunk_time; NULL = chunk_time for all */
+  int64_t chunk_time;
+  int32_t inputs_format; int32_t flags;   /* flags: CTCEXT_FLAG_TEST_HELPER_DEAD, _PROFILE only */
+  int64_t inputs_stride_t, inputs_stride_b;
+  void* stream;             /* hipStream_t, NULL = the decoder's own */
+} ctcext_chunk;
+
+/* The attribute checks of ctcext_validate for a stream, host only, no HIP
+ * call (the bigram table's entries included: it is host memory); plus
+ * "max_frames is negative" and "stream flags: CTCEXT_FLAG_FORCE_LITERAL,
+ * _GLOBAL_STATE and _PROFILE only". */
+int ctcext_stream_validate(const ctcext_stream_args* args);
+/* ... and a chunk against those attributes, host only as well (part of the
+ * public stream ABI: a front end checks a block before it queues it): the checks
+ * ctcext_stream_push runs before any device work, except the stream's
+ * capacity -- the ABI-7 layout messages of ctcext_validate with chunk_time as
+ * max_time, and "sequence_length(b) <= chunk_time" when the lengths are host
+ * memory (on_device == 0). */
+int ctcext_stream_validate_chunk(const ctcext_stream_args* args, const ctcext_chunk* chunk);
+int ctcext_stream_open(ctcext_decoder* dec, const ctcext_stream_args* args, ctcext_stream** out);
+/* Decodes the chunk on top of what the stream holds.  Synchronous.  With
+ * sizes != NULL it also walks the records of all frames so far and sets the
+ * decoder's fetch state.  Validation comes before any device work; a rejected
+ * push (also: "stream capacity exceeded: item %d would hold %d frames of
+ * max_frames %d", CTCEXT_INVALID_ARGUMENT) and a failed one (CTCEXT_INTERNAL:
+ * a helper-wave hand-over timeout; a stream cannot re-decode with another
+ * kernel) leave the stream as it was.  "Less leaves in the beam search than
+ * requested." (CTCEXT_INVALID_ARGUMENT, as ctcext_decode of that prefix) is
+ * reported with the chunk pushed.  ctcext_stats after a push: the counters are
+ * cumulative over the stream's items. */
+int ctcext_stream_push(ctcext_stream* s, const ctcext_chunk* chunk, ctcext_path_sizes* sizes);
+/* frames[batch]: frames pushed so far per item. */
+int ctcext_stream_frames(ctcext_stream* s, int64_t* frames);
+/* Puts the n named items (items == NULL: all) back to no frames, for a
+ * continuous-batching slot that starts a new utterance; others are untouched. */
+int ctcext_stream_reset(ctcext_stream* s, const int32_t* items, int64_t n);
+/* Close every stream before ctcext_destroy of its decoder. */
+void ctcext_stream_close(ctcext_stream* s);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""What streaming costs: the summed time of the pushes of one cfg3 batch
+(B=256, T=1500, C=29, W=128, P=3) at several chunk sizes, beside the one-shot
+decode_logits of the same tensor on the same build and box.
+
+Every push but the last runs with results=False (no traceback, no outputs);
+the last one returns the hypotheses, as the one-shot call does.  The
+difference to the one-shot time is the per-push cost: the pre-pass launch,
+the state image's load and store, the host synchronisation.  The 1500-frame
+row is one push: the stream build of the kernel (no record ring, image saved
+once) against the default one; the one-shot call is timed with and without
+its record ring, since a stream writes every record.
+
+    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--out FILE]
+
+Prints one table and one JSON line.  It is a report, not a check, and it does
+not touch bench.py.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ctc-beam-search-op_amd"))
+
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+
+import ctcext_amd    # noqa: E402
+from ctcext_amd import _lib   # noqa: E402
+
+B, T, C, W, P = 256, 1500, 29, 128, 3
+KW = dict(merge_repeated=True, blank_index=0)
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def one_shot(x, sl, flags=0):
+    return ctcext_amd.decode_logits(x, sl, W, P, batch_first=False, outputs="device", flags=flags, **KW)
+
+
+def streamed(x, chunk):
+    with ctcext_amd.StreamDecoder(B, C, W, P, T, **KW) as s:
+        s.push(x[:0], batch_first=False, results=False)   # opens the stream: its allocations are not timed
+        ms = 0.0
+        out = None
+        for t0 in range(0, T, chunk):
+            t1 = min(t0 + chunk, T)
+            dt, out = _timed(lambda: s.push(x[t0:t1], batch_first=False, results=t1 == T, outputs="device"))
+            ms += dt
+        kernel = s.last_stats["kernel"]
+    return ms, out, kernel
+
+
+def _same(a, b):
+    for p in range(P):
+        for name in ("decoded_indices", "decoded_values", "alignment_indices", "alignment_values"):
+            if not torch.equal(getattr(a, name)[p], getattr(b, name)[p]):
+                return False
+    return torch.equal(a.log_probability, b.log_probability)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--chunks", default="1500,100,10")
+    ap.add_argument("--out", default=None, help="also write the table and the JSON line here")
+    args = ap.parse_args()
+    chunks = [int(c) for c in args.chunks.split(",")]
+    rng = np.random.default_rng(20251015)
+    x = torch.as_tensor(rng.standard_normal((T, B, C), dtype=np.float32), device="cuda:0")
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    ref = one_shot(x, sl)   # warm-up: workspace, kernels
+    rows = {}
+    rows["one-shot"] = [_timed(lambda: one_shot(x, sl))[0] for _ in range(args.runs)]
+    rows["one-shot, no ring"] = [_timed(lambda: one_shot(x, sl, _lib.CTCEXT_FLAG_NO_RING))[0]
+                                 for _ in range(args.runs)]
+    kernel = None
+    for c in chunks:
+        ms, out, kernel = streamed(x, c)   # warm-up
+        if not _same(out, ref):
+            raise SystemExit("chunk size %d: the streamed result differs from the one-shot one" % c)
+        rows["stream, %d-frame pushes" % c] = [streamed(x, c)[0] for _ in range(args.runs)]
+    base = statistics.median(rows["one-shot"])
+    lines = ["%-28s %9s %9s %9s %8s %10s" % ("B=256 T=1500 C=29 W=128 P=3", "median ms", "min", "max", "vs 1-shot",
+                                              "per push")]
+    res = {"shape": [B, T, C, W, P], "runs": args.runs, "stream_kernel": kernel, "rows": {}}
+    for name, v in rows.items():
+        med = statistics.median(v)
+        n = 1
+        if name.startswith("stream"):
+            n = -(-T // int(name.split()[1].split("-")[0]))
+        per = "" if n == 1 else "%+.3f ms" % ((med - base) / n)
+        lines.append("%-28s %9.2f %9.2f %9.2f %7.1f%% %10s" % (name, med, min(v), max(v), 100 * (med / base - 1), per))
+        res["rows"][name] = {"median_ms": round(med, 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3),
+                             "pushes": n}
+    text = "\n".join(lines) + "\n" + json.dumps(res)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
