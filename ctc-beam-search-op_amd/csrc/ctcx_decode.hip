@@ -1815,6 +1815,128 @@ __device__ __forceinline__ void extract_f32(unsigned heb, int hi, int lo, int ba
         "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251");
 }
 
+// extract_f32 with the heap in registers for the whole call (beams up to 128;
+// the two-node kernels keep extract_f32).  extract_f32 ends every pop with two
+// node stores and begins the next with a read of the same lines and a wait for
+// it (~99 cycles on the serial chain), yet every value that read returns was
+// in some lane's registers before the stores went out, and nothing else reads
+// `he` while wave 0 pops (the helper ranks a copy).  Here P = v[232:235] holds
+// lane j's child pair (L.v, L.s, R.v, R.s): read from `he` once at entry,
+// carried from pop to pop, written back once at exit with the root, so `he`
+// is what extract_f32 leaves at every call boundary (dummy slots aside).
+// One pop:
+//   * e[len - 1] is a child of lane (len - 2) / 2: two v_readlane of P (the
+//     loop is unrolled by two, the side is the parity of len), and that lane's
+//     entry becomes the sentinel;
+//   * every lane publishes what its node holds after the sift if the path
+//     reaches it: v where its min child is > v (gt: v lands there), else its
+//     min child (it moves up) -- lane 0's pair is the new root: the front --
+//     and then lane 0, whose node is nobody's child, publishes v;
+//   * every lane fetches the published pair of its min child's lane (two
+//     ds_bpermute: no LDS) -- lanes whose min child is not a lane (lanes
+//     32..63, lane 31 on the right) fetch lane 0's, v;
+//   * the lanes that take their min child (up: on the root's min-child path,
+//     no proper ancestor meeting the stop condition, no gt) put the fetched
+//     pair in P on the min child's side: the child moved up, or v landed
+//     there.  Nothing else changes: a child on the path has its parent on it.
+//     Without the stores nothing needs the stop's lane, so up is a per-lane
+//     test against the stop-condition mask (ancestors of a lane are below 32:
+//     its low word), not a scalar s_ff1 chain.
+// The fetch goes out as soon as gt is known and its latency overlaps the rest
+// of the mask algebra.  tests/test_cpu_heap_forward.py is this rule on the
+// host against libstdc++; tools/heap_fwd_unit.hip runs both loops on the GPU.
+// Temporaries: s80..s81, s85..s95, s98, vcc, m0, v232..v251 (clobbered).
+#define CTCX_XFWD_POP(XV, XS, NEXTLANE)                                                                     \
+      "s_lshl_b64 s[80:81], 1, s90\n\t"                    /* the lane e[len - 1] is a child of */         \
+      "v_readlane_b32 s86, " XV ", s90\n\t"                /* v = e[len - 1] */                            \
+      "v_readlane_b32 s87, " XS ", s90\n\t"                                                                  \
+      "v_cndmask_b32_e64 " XV ", " XV ", v242, s[80:81]\n\t" /* vacated: the sentinel */                   \
+      "v_cmp_ngt_f32_e64 s[92:93], v234, v232\n\t"         /* pickR = !(R > L) */                          \
+      "v_cndmask_b32_e64 " XS ", " XS ", v243, s[80:81]\n\t"                                                 \
+      "v_writelane_b32 %[srt], %[fs], m0\n\t"              /* the front: position len - 1 */               \
+      "v_mov_b64_e32 v[238:239], s[86:87]\n\t"                                                               \
+      "v_cndmask_b32_e64 v248, v232, v234, s[92:93]\n\t"   /* cv */                                        \
+      "v_cmp_lt_f32_e32 vcc, s86, v248\n\t"                /* gt: min child > v */                         \
+      "v_cndmask_b32_e64 v249, v233, v235, s[92:93]\n\t"   /* cs */                                        \
+      "v_cndmask_b32_e64 v237, v246, v247, s[92:93]\n\t"   /* the min child's lane (x 4) */                \
+      "v_cndmask_b32_e32 v240, v248, v238, vcc\n\t"        /* published: v (gt) or the min child */        \
+      "v_cndmask_b32_e32 v241, v249, v239, vcc\n\t"                                                          \
+      "s_and_b32 s98, s92, %[k31]\n\t"                                                                       \
+      "v_bitop3_b32 v244, s92, %[req], %[anc] bitop3:0x28\n\t"  /* (pickR ^ req) & anc */                  \
+      "v_readfirstlane_b32 %[fs], v241\n\t"                /* the root's: the new front */                 \
+      "v_writelane_b32 v240, s86, 0\n\t"                   /* lane 0 publishes v */                        \
+      "v_writelane_b32 v241, s87, 0\n\t"                                                                     \
+      "s_or_b32 s98, s98, vcc_lo\n\t"                      /* the stop condition, lanes 0..31 */           \
+      "ds_bpermute_b32 v250, v237, v240\n\t"               /* the min child's published pair */            \
+      "ds_bpermute_b32 v251, v237, v241\n\t"                                                                 \
+      "v_and_or_b32 v245, s98, %[anc], v244\n\t"           /* off the path, or below the stop */           \
+      "s_sub_u32 m0, m0, 1\n\t" NEXTLANE                                                                     \
+      "v_cmp_eq_u32_e64 s[94:95], 0, v245\n\t"             /* live: path nodes at or above the stop */     \
+      "s_andn2_b64 s[94:95], s[94:95], vcc\n\t"            /* up: takes its min child */                   \
+      "s_and_b64 s[80:81], s[94:95], s[92:93]\n\t"         /* ... the right one */                         \
+      "s_andn2_b64 s[88:89], s[94:95], s[92:93]\n\t"       /* ... the left one */                          \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                             \
+      "v_cndmask_b32_e64 v232, v232, v250, s[88:89]\n\t"                                                     \
+      "v_cndmask_b32_e64 v233, v233, v251, s[88:89]\n\t"                                                     \
+      "v_cndmask_b32_e64 v234, v234, v250, s[80:81]\n\t"                                                     \
+      "v_cndmask_b32_e64 v235, v235, v251, s[80:81]\n\t"                                                     \
+      "s_cmp_ge_i32 m0, s85\n\t"
+__device__ __forceinline__ void extract_fwd_f32(unsigned heb, int hi, int lo, int base, unsigned anc, unsigned req,
+                                                unsigned aj, unsigned al, unsigned dum, int& srt, int& fs) {
+  const unsigned k31 = 0x80000000u;
+  // every scalar operand provably uniform (the asm's "s" constraints)
+  heb = (unsigned)uni((int)heb); hi = uni(hi); lo = uni(lo); base = uni(base); fs = uni(fs);
+  asm volatile(
+      "s_cmp_le_i32 %[hi], %[lo]\n\t"
+      "s_cbranch_scc1 .Lxf_end_%=\n\t"
+      "ds_read_b128 v[232:235], %[al]\n\t"                 // P: the child pairs
+      "v_mov_b32_e32 v242, 0x7f800000\n\t"                 // the sentinel (+inf, -1)
+      "v_mov_b32_e32 v243, -1\n\t"
+      "s_sub_u32 s86, %[hi], 1\n\t"
+      "s_sub_u32 m0, s86, %[base]\n\t"                     // position len - 1's lane in srt (-1 per pop)
+      "s_sub_u32 s85, %[lo], %[base]\n\t"                  // the last pop's
+      "s_sub_u32 s90, %[hi], 2\n\t"
+      "s_lshr_b32 s90, s90, 1\n\t"                         // the lane position len - 1 is a child of (-1 per two pops)
+      // the lane (x 4) a fetch reads: the left and the right child's, lane 0
+      // where the child is not a lane
+      "v_sub_u32_e32 v247, %[al], %[aj]\n\t"               // 8 * lane + 8
+      "s_mov_b32 s80, 0x7fffffff\n\t"
+      "s_mov_b32 s81, 0\n\t"
+      "v_add_u32_e32 v246, -4, v247\n\t"
+      "v_cndmask_b32_e64 v247, 0, v247, s[80:81]\n\t"      // right: lanes 0..30
+      "s_mov_b32 s80, -1\n\t"
+      "v_cndmask_b32_e64 v246, 0, v246, s[80:81]\n\t"      // left: lanes 0..31
+      "s_bitcmp1_b32 %[hi], 0\n\t"                         // len odd: e[len - 1] is a right child
+      "s_waitcnt lgkmcnt(0)\n\t"
+      "s_cbranch_scc0 .Lxf_odd_%=\n"
+      ".Lxf_even_%=:\n\t"
+      CTCX_XFWD_POP("v234", "v235", "")
+      "s_cbranch_scc0 .Lxf_done_%=\n"
+      ".Lxf_odd_%=:\n\t"
+      CTCX_XFWD_POP("v232", "v233", "s_sub_u32 s90, s90, 1\n\t")
+      "s_cbranch_scc1 .Lxf_even_%=\n"
+      // back to he: the pairs, and the root (v if it stayed there, else its min child)
+      ".Lxf_done_%=:\n\t"
+      "v_readfirstlane_b32 s91, v248\n\t"
+      "v_mov_b32_e32 v236, %[dum]\n\t"
+      "s_add_u32 s88, %[heb], 8\n\t"
+      "s_bitcmp1_b32 vcc_lo, 0\n\t"                        // keep: v stayed at the root
+      "s_cselect_b32 s86, s86, s91\n\t"
+      "v_mov_b32_e32 v239, %[fs]\n\t"
+      "v_writelane_b32 v236, s88, 0\n\t"                   // lane 0: the root (the others: dummies)
+      "v_mov_b32_e32 v238, s86\n\t"
+      "ds_write_b128 %[al], v[232:235]\n\t"
+      "ds_write_b64 v236, v[238:239]\n"
+      ".Lxf_end_%=:\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : [srt] "+v"(srt), [fs] "+s"(fs)
+      : [heb] "s"(heb), [hi] "s"(hi), [lo] "s"(lo), [base] "s"(base), [anc] "v"(anc), [req] "v"(req), [aj] "v"(aj),
+        [al] "v"(al), [dum] "v"(dum), [k31] "s"(k31)
+      : "memory", "vcc", "m0", "s80", "s81", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94",
+        "s95", "s98", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243",
+        "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251");
+}
+
 // extract_f32 over the two-group heap (beams 129..256: the push_m2 sift), for
 // pops that leave more than 128 elements (len > 129); below that the heap
 // fits the one-group form and extract_f32 takes over on the same layout (the
@@ -4587,7 +4709,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
     if constexpr (sizeof(T) == 4) {
       const unsigned heb = (unsigned)(uintptr_t)he;
       const unsigned aj = heb + 8u * (unsigned)(lane + 1), al = heb + 8u * (unsigned)(2 * lane + 2);
-      const unsigned ar = al + 8u, dum = heb + 8u * (unsigned)(cx.hdum + lane);
+      const unsigned dum = heb + 8u * (unsigned)(cx.hdum + lane);
       fs = uni(fs);
       // positions 127..64 into srt1, 63..2 into srt0, in four segments; with
       // the helper ranking (ext_rank), kCtlStop is read between them and the
@@ -4603,7 +4725,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
 #ifdef CTCX_PHASE_EXTT
         const uint64_t sx0 = __builtin_amdgcn_s_memtime();
 #endif
-        if (hi > l) extract_f32(heb, uni(hi), uni(l), base, geo.anc, geo.req, aj, al, ar, dum, srt, fs);
+        if (hi > l) extract_fwd_f32(heb, uni(hi), uni(l), base, geo.anc, geo.req, aj, al, dum, srt, fs);
 #ifdef CTCX_PHASE_EXTT
         if (pc && hi > l) { pc[23] += __builtin_amdgcn_s_memtime() - sx0; pc[17] += 1; pc[18] += hi - l; }
 #endif
