@@ -41,6 +41,9 @@ hipError_t launch_widen_rows(const void* x, int xfmt, float* out, int64_t T_, in
                              int64_t xst_b, hipStream_t s);
 hipError_t launch_scan(const int32_t* len, int64_t* off, int64_t* res, int64_t B, int P, hipStream_t s);
 hipError_t launch_pack(const PackParams& pp, hipStream_t s);
+hipError_t launch_dense_prologue(DensePrologueParams pp, const void* table, int64_t table_n, int f64, int32_t* bad,
+                                 hipStream_t s);
+hipError_t launch_pack_dense(const PackDenseParams& pp, hipStream_t s);
 }  // namespace ctcx
 // the global-state tier (ctcx_decode.hip compiled with CTCX_GSTATE)
 hipError_t ctcx_gstate_launch_decode(const void* p, int is_f64, int scored, hipStream_t s);
@@ -146,8 +149,9 @@ struct Dev {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t s = nullptr;   // stream of the current call
-  hipEvent_t ev[4] = {};
+  hipEvent_t ev[5] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
+  DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
   int64_t lo = 0, nb = 0;    // this call's shard [lo, lo + nb)
   int ring = 0;              // this call's record-ring frames (ctcx::ring_frames)
   int rec_bytes = 8;         // this call's record size (8, 16 or 4 bytes)
@@ -162,7 +166,7 @@ struct ctcext_decoder {
   std::vector<Dev> devs;
   // root-side: scan results and output staging
   DevBuf off, res, ptrs, out_idx, out_val;
-  HostBuf h_item, h_res, h_kind;
+  HostBuf h_item, h_res, h_kind, h_status;
   // state of the last successful decode (consumed by fetch)
   bool have = false;
   int dtype = 0;
@@ -170,13 +174,21 @@ struct ctcext_decoder {
   int32_t W = 0, P = 0;
   std::vector<ctcext_path_sizes> sizes;
   ctcext_stats stats{};
+  // the last ctcext_decode_dense (read by ctcext_dense_check)
+  struct {
+    bool have = false;
+    int64_t B = 0, T = 0;
+    int32_t P = 0, flags = 0;
+    double pack_ms = 0;      // CTCEXT_FLAG_PROFILE: the pack kernel's time (ctcext_dense_pack_ms)
+    hipStream_t s = nullptr;
+  } dense;
 };
 
 static void release_dev(Dev& d) {
   (void)hipSetDevice(d.device);
   if (d.own_stream) (void)hipStreamSynchronize(d.own_stream);
   DevBuf* bufs[] = {&d.x, &d.xw, &d.sl, &d.norm, &d.prep, &d.rec, &d.foff, &d.item, &d.top_pos, &d.top_kind, &d.logp,
-                    &d.seq, &d.len, &d.phase, &d.sctab, &d.gstate};
+                    &d.seq, &d.len, &d.phase, &d.sctab, &d.gstate, &d.dsl, &d.dstat};
   for (DevBuf* b : bufs) b->release();
   for (auto& ev : d.ev)
     if (ev) (void)hipEventDestroy(ev);
@@ -251,6 +263,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   d->h_item.release();
   d->h_res.release();
   d->h_kind.release();
+  d->h_status.release();
   for (Dev& v : d->devs) release_dev(v);
   delete d;
 }
@@ -450,20 +463,30 @@ static void shard_bounds(const std::vector<int32_t>& hsl, int n, std::vector<int
   }
 }
 
-// Enqueues norm + decode + traceback of one shard on its device's stream.
+// What the launches of one shard need, decided on the host.
+template <typename T>
+struct ShardPlan {
+  ctcx::DecodeParams<T> p{};
+  ctcx::TraceParams tp{};
+  bool gs = false, scored = false;
+  // a half shard of the global-state tier is widened into workspace first:
+  // the caller's rows (p.x then points at the widened copy)
+  bool widen = false;
+  const void* x_in = nullptr;
+  int xfmt_in = 0;
+  int64_t xst_t_in = 0, xst_b_in = 0;
+};
+
+// Sizes the workspace of one shard (grow-only: nothing is allocated or freed
+// when it already fits) and fills the kernels' parameters.  Launches nothing.
 // x/sl point at the shard's first item; x holds elements of xfmt
 // (CTCEXT_IN_*), row (t, b) of the shard xst_t * t + xst_b * b elements in.
 template <typename T>
-static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_decode_args* a, const void* x, int xfmt,
-                         int64_t xst_t, int64_t xst_b, const int32_t* sl, int helper_mode) {
+static int plan_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_decode_args* a, const void* x, int xfmt,
+                      int64_t xst_t, int64_t xst_b, const int32_t* sl, int helper_mode, ShardPlan<T>& pl) {
   const int64_t T_ = a->max_time, C = a->num_classes, B = d->B, Bs = v.nb;
   const int W = a->beam_width, P = a->top_paths;
-  const bool prof = (a->flags & CTCEXT_FLAG_PROFILE) != 0;
   const int64_t Bo = root ? B : Bs;   // the root's walk buffers hold the whole batch
-  hipStream_t s = v.s;
-  v.kernel = 0;
-  int* note = ctcx_launch_note();   // (the launchers below run on this thread)
-  note[0] = note[1] = note[2] = 0;
   HIP_OR_FAIL(v.norm.ensure(sizeof(T) * (size_t)(T_ * Bs)));
   HIP_OR_FAIL(v.rec.ensure(sizeof(ctcx::Rec) * (size_t)(Bs * T_ * W)));
   HIP_OR_FAIL(v.item.ensure(sizeof(ctcx::ItemOut) * (size_t)Bo));
@@ -473,8 +496,8 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   HIP_OR_FAIL(v.seq.ensure(4 * (size_t)(Bo * P * 2 * T_)));
   HIP_OR_FAIL(v.len.ensure(4 * (size_t)(Bo * P * 2)));
 
-  const bool gs = use_gstate(a);
-  const bool scored = a->scorer != CTCEXT_SCORER_BASE;
+  const bool gs = pl.gs = use_gstate(a);
+  const bool scored = pl.scored = a->scorer != CTCEXT_SCORER_BASE;
   if (gs) {
     // the global-state tier: 16-byte records, the beam state in HBM
     HIP_OR_FAIL(v.rec.ensure(sizeof(ctcx::Rec16) * (size_t)(Bs * T_ * W)));
@@ -482,30 +505,21 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   } else if (C > 64) {
     HIP_OR_FAIL(v.prep.ensure(ctcx::prep_row_bytes(C, (int)sizeof(T)) * (size_t)(T_ * Bs)));
   }
-
-  if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[0], s));
   if (gs && xfmt != CTCEXT_IN_NATIVE && Bs > 0) {
     // the global-state tier reads its rows in place, as T: a half shard is
     // widened into workspace first (the slow catch-all tier; its kernels
     // stay as they are)
     HIP_OR_FAIL(v.xw.ensure(4 * (size_t)(T_ * Bs * C) + 16));
-    HIP_OR_FAIL(ctcx::launch_widen_rows(x, xfmt, (float*)v.xw.p, T_, Bs, C, xst_t, xst_b, s));
+    pl.widen = true;
+    pl.x_in = x; pl.xfmt_in = xfmt; pl.xst_t_in = xst_t; pl.xst_b_in = xst_b;
     x = v.xw.p;
     xfmt = CTCEXT_IN_NATIVE;
     xst_t = Bs * C;
     xst_b = C;
   }
-  if (!gs && C > 64) {
-    // large C: the normaliser and the row facts the decode kernel reads per
-    // frame, one parallel pre-pass
-    HIP_OR_FAIL(ctcx::launch_row_prep<T>(x, xfmt, sl, (char*)v.prep.p, (T*)v.norm.p, T_, Bs, C, xst_t, xst_b,
-                                         a->blank_index, s));
-  } else {
-    HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, xfmt, sl, (T*)v.norm.p, T_, Bs, C, xst_t, xst_b, s));
-  }
-  if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[1], s));
 
-  ctcx::DecodeParams<T> p{};
+  ctcx::DecodeParams<T>& p = pl.p;
+  p = ctcx::DecodeParams<T>{};
   p.x = (const T*)x;
   p.xfmt = xfmt;
   p.norm = (const T*)v.norm.p;
@@ -524,10 +538,8 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   p.prof = nullptr;
   p.scorer_tab = nullptr;
   p.prep = (const char*)v.prep.p;
-  if (a->scorer == CTCEXT_SCORER_BIGRAM) {   // each device reads its own copy
-    const size_t tb = (size_t)((C + 1) * C) * sizeof(T);
-    HIP_OR_FAIL(v.sctab.ensure(tb));
-    HIP_OR_FAIL(hipMemcpyAsync(v.sctab.p, a->scorer_table, tb, hipMemcpyDefault, s));
+  if (a->scorer == CTCEXT_SCORER_BIGRAM) {   // each device reads its own copy (enqueue_shard copies it)
+    HIP_OR_FAIL(v.sctab.ensure((size_t)((C + 1) * C) * sizeof(T)));
     p.scorer_tab = (const T*)v.sctab.p;
   }
   if (a->flags & CTCEXT_FLAG_PHASES) {
@@ -564,13 +576,10 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   if (gs) {
     p.gstate = (char*)v.gstate.p;
     p.gstate_stride = (int64_t)ctcx::gstate_bytes(W, (int)sizeof(T), scored);
-    HIP_OR_FAIL(ctcx_gstate_launch_decode(&p, sizeof(T) == 8, scored, s));
-  } else {
-    HIP_OR_FAIL(ctcx::launch_decode<T>(p, s));
   }
-  if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[2], s));
 
-  ctcx::TraceParams tp{};
+  ctcx::TraceParams& tp = pl.tp;
+  tp = ctcx::TraceParams{};
   tp.rec = p.rec; tp.item = p.item; tp.seq_len = sl; tp.top_pos = p.top_pos; tp.top_kind = p.top_kind;
   tp.Tmax = T_; tp.B = Bs; tp.W = W; tp.P = P; tp.merge = a->merge_repeated ? 1 : 0;
   tp.blank_label = a->blank_label;
@@ -580,10 +589,64 @@ static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_deco
   tp.seq = (int32_t*)v.seq.p;
   tp.len = (int32_t*)v.len.p;
   tp.len_stride = Bo;
-  HIP_OR_FAIL(ctcx::launch_traceback(tp, s));
+  return CTCEXT_OK;
+}
+
+// Enqueues norm + decode + traceback of one shard on its device's stream
+// (plan_shard's arguments): the workspace is grown first, then only launches,
+// asynchronous copies and event records follow.
+template <typename T>
+static int enqueue_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_decode_args* a, const void* x, int xfmt,
+                         int64_t xst_t, int64_t xst_b, const int32_t* sl, int helper_mode) {
+  const int64_t T_ = a->max_time, C = a->num_classes, Bs = v.nb;
+  const bool prof = (a->flags & CTCEXT_FLAG_PROFILE) != 0;
+  hipStream_t s = v.s;
+  v.kernel = 0;
+  ShardPlan<T> pl;
+  const int rc = plan_shard<T>(d, v, root, a, x, xfmt, xst_t, xst_b, sl, helper_mode, pl);
+  if (rc != CTCEXT_OK) return rc;
+  const ctcx::DecodeParams<T>& p = pl.p;
+  int* note = ctcx_launch_note();   // (the launchers below run on this thread)
+  note[0] = note[1] = note[2] = 0;
+
+  if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[0], s));
+  if (pl.widen)
+    HIP_OR_FAIL(ctcx::launch_widen_rows(pl.x_in, pl.xfmt_in, (float*)v.xw.p, T_, Bs, C, pl.xst_t_in, pl.xst_b_in, s));
+  if (!pl.gs && C > 64) {
+    // large C: the normaliser and the row facts the decode kernel reads per
+    // frame, one parallel pre-pass
+    HIP_OR_FAIL(ctcx::launch_row_prep<T>(p.x, p.xfmt, sl, (char*)v.prep.p, (T*)v.norm.p, T_, Bs, C, p.xst_t, p.xst_b,
+                                         a->blank_index, s));
+  } else {
+    HIP_OR_FAIL(ctcx::launch_row_norm<T>(p.x, p.xfmt, sl, (T*)v.norm.p, T_, Bs, C, p.xst_t, p.xst_b, s));
+  }
+  if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[1], s));
+
+  if (a->scorer == CTCEXT_SCORER_BIGRAM)
+    HIP_OR_FAIL(hipMemcpyAsync(v.sctab.p, a->scorer_table, (size_t)((C + 1) * C) * sizeof(T), hipMemcpyDefault, s));
+  if (pl.gs) {
+    HIP_OR_FAIL(ctcx_gstate_launch_decode(&p, sizeof(T) == 8, pl.scored, s));
+  } else {
+    HIP_OR_FAIL(ctcx::launch_decode<T>(p, s));
+  }
+  if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[2], s));
+
+  HIP_OR_FAIL(ctcx::launch_traceback(pl.tp, s));
   v.kernel = note[0] | (note[1] << 12) | (note[2] << 16);
   if (prof) HIP_OR_FAIL(hipEventRecord(v.ev[3], s));
   return CTCEXT_OK;
+}
+
+// The inputs' element strides (both 0 in a: the dense reference layout); the
+// stride of a dimension of extent 1 addresses nothing, and takes the value a
+// dense tensor would have.
+static void input_strides(const ctcext_decode_args* a, int64_t& st_t, int64_t& st_b) {
+  const int64_t T_ = a->max_time, B = a->batch_size, C = a->num_classes;
+  st_t = a->inputs_stride_t ? a->inputs_stride_t : B * C;
+  st_b = a->inputs_stride_b ? a->inputs_stride_b : C;
+  if (T_ <= 1 && B <= 1) st_t = st_b = C;
+  else if (T_ <= 1) st_t = st_b * B;
+  else if (B <= 1) st_b = st_t * T_;
 }
 
 template <typename T>
@@ -592,15 +655,10 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
   const int64_t T_ = a->max_time, B = a->batch_size, C = a->num_classes;
   const int P = a->top_paths;
   const int ts = (int)sizeof(T);
-  // the inputs' element size and element strides (both 0: the dense
-  // reference layout); the stride of a dimension of extent 1 addresses
-  // nothing, and takes the value a dense tensor would have
+  // the inputs' element size and element strides
   const size_t es = a->inputs_format == CTCEXT_IN_NATIVE ? (size_t)ts : 2;
-  int64_t st_t = a->inputs_stride_t ? a->inputs_stride_t : B * C;
-  int64_t st_b = a->inputs_stride_b ? a->inputs_stride_b : C;
-  if (T_ <= 1 && B <= 1) st_t = st_b = C;
-  else if (T_ <= 1) st_t = st_b * B;
-  else if (B <= 1) st_b = st_t * T_;
+  int64_t st_t, st_b;
+  input_strides(a, st_t, st_b);
   const int nd = (int)d->devs.size();
   Dev& root = d->devs[0];
   std::vector<int64_t> lo;
@@ -752,6 +810,7 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
 extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args* a, ctcext_path_sizes* sizes) {
   if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   d->have = false;
+  d->dense.have = false;   // (the workspace ctcext_dense_check reads is this call's now)
   int rc = validate_shapes(a);
   if (rc != CTCEXT_OK) return rc;
   DeviceGuard guard;
@@ -895,6 +954,230 @@ extern "C" int ctcext_fetch(ctcext_decoder* d, const ctcext_outputs* o) {
   }
   HIP_OR_FAIL(hipStreamSynchronize(s));
   g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Dense, enqueue-only decode (ctcext.h, "Dense, enqueue-only decode").  The
+// checks of ctcext_decode that read data (check_lengths, check_table, the
+// per-item results) run on the device: a prologue writes the lengths the
+// kernels read and the status known before the decode, enqueue_shard runs on
+// those lengths, and ctcx_pack_dense finishes the status and writes the padded
+// outputs.  ctcext_dense_check reads the workspace copy of the status later.
+
+extern "C" int ctcext_dense_validate(const ctcext_decode_args* a, const ctcext_dense_outputs* o) {
+  int rc = validate_shapes(a);
+  if (rc == CTCEXT_OK) rc = check_limits(a);
+  if (rc == CTCEXT_OK) rc = check_layout(a);
+  if (rc != CTCEXT_OK) return rc;
+  if (!a->inputs_on_device) return fail(CTCEXT_INVALID_ARGUMENT, "ctcext_decode_dense needs device inputs");
+  if (a->batch_size > 0 && (!o || !o->decoded || !o->decoded_length || !o->alignment || !o->alignment_length ||
+                            !o->log_probability || !o->status))
+    return fail(CTCEXT_INVALID_ARGUMENT, "null dense output pointer");
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// The workspace of a dense call and its plan; launches nothing.  Sized as the
+// synchronous path sizes it (plan_shard over the whole batch on the root),
+// plus the prologue's words and the pinned buffers ctcext_dense_check fills.
+template <typename T>
+static int dense_plan(ctcext_decoder* d, const ctcext_decode_args* a, int helper_mode, ShardPlan<T>& pl) {
+  const int64_t B = a->batch_size;
+  Dev& root = d->devs[0];
+  int64_t st_t, st_b;
+  input_strides(a, st_t, st_b);
+  d->B = B;
+  root.lo = 0;
+  root.nb = B;
+  HIP_OR_FAIL(root.dsl.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(root.dstat.ensure(4 * (2 * (size_t)B + 1)));
+  HIP_OR_FAIL(d->h_item.ensure(sizeof(ctcx::ItemOut) * (size_t)B + 16));
+  HIP_OR_FAIL(d->h_kind.ensure(4 * (size_t)(B * a->top_paths) + 16));
+  HIP_OR_FAIL(d->h_status.ensure(4 * (size_t)B + 16));
+  return plan_shard<T>(d, root, true, a, a->inputs, a->inputs_format, st_t, st_b, (const int32_t*)root.dsl.p,
+                       helper_mode, pl);
+}
+
+// The checks both entry points share; *s is the call's stream.
+static int dense_begin(ctcext_decoder* d, const ctcext_decode_args* a, hipStream_t* s) {
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "the dense decode needs a one-device decoder handle");
+  // the null stream itself with the flag: torch's legacy default stream has
+  // handle 0, and the decoder's own (non-blocking) stream is not ordered behind it
+  *s = a->stream ? (hipStream_t)a->stream
+       : (a->flags & CTCEXT_FLAG_DENSE_NULL_STREAM) ? (hipStream_t) nullptr : d->devs[0].own_stream;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_reserve(ctcext_decoder* d, const ctcext_decode_args* a) {
+  if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = validate_shapes(a);
+  if (rc == CTCEXT_OK) rc = check_limits(a);
+  if (rc == CTCEXT_OK) rc = check_layout(a);
+  if (rc != CTCEXT_OK) return rc;
+  hipStream_t s;
+  rc = dense_begin(d, a, &s);
+  if (rc != CTCEXT_OK || a->batch_size == 0) return rc;
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(d->devs[0].device));
+  // (the handle's state of the last call -- fetch, check, stats -- is not touched)
+  const int64_t B0 = d->B;
+  const int helper_mode = helper_mode_from_env();
+  if (a->dtype == CTCEXT_F32) {
+    ShardPlan<float> pl;
+    rc = dense_plan<float>(d, a, helper_mode, pl);
+  } else {
+    ShardPlan<double> pl;
+    rc = dense_plan<double>(d, a, helper_mode, pl);
+  }
+  d->B = B0;
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+template <typename T>
+static int dense_enqueue(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_dense_outputs* o,
+                         int helper_mode) {
+  const int64_t T_ = a->max_time, B = a->batch_size, C = a->num_classes;
+  Dev& root = d->devs[0];
+  hipStream_t s = root.s;
+  ShardPlan<T> pl;
+  int rc = dense_plan<T>(d, a, helper_mode, pl);   // (nothing to grow after a reserve or a call of this shape)
+  if (rc != CTCEXT_OK) return rc;
+  int32_t* const pre = (int32_t*)root.dstat.p;
+  int32_t* const fin = pre + B;
+  ctcx::DensePrologueParams pp{};
+  pp.seq_len = a->sequence_length;
+  pp.sl = (int32_t*)root.dsl.p;
+  pp.pre = pre;
+  pp.Tmax = T_; pp.B = B;
+  const bool bigram = a->scorer == CTCEXT_SCORER_BIGRAM;
+  HIP_OR_FAIL(ctcx::launch_dense_prologue(pp, bigram ? a->scorer_table : nullptr, bigram ? (C + 1) * C : 0,
+                                          sizeof(T) == 8, fin + B, s));
+  int64_t st_t, st_b;
+  input_strides(a, st_t, st_b);
+  rc = enqueue_shard<T>(d, root, true, a, a->inputs, a->inputs_format, st_t, st_b, pp.sl, helper_mode);
+  if (rc != CTCEXT_OK) return rc;
+  ctcx::PackDenseParams pd{};
+  pd.seq = (const int32_t*)root.seq.p;
+  pd.len = (const int32_t*)root.len.p;
+  pd.item = (const ctcx::ItemOut*)root.item.p;
+  pd.pre = pre;
+  pd.log_prob = root.logp.p;
+  pd.Tmax = T_; pd.B = B; pd.P = a->top_paths; pd.f64 = sizeof(T) == 8;
+  pd.pad_value = o->pad_value;
+  pd.decoded = o->decoded; pd.alignment = o->alignment;
+  pd.decoded_length = o->decoded_length; pd.alignment_length = o->alignment_length;
+  pd.out_log_prob = o->log_probability;
+  pd.status = o->status;
+  pd.status_ws = fin;
+  HIP_OR_FAIL(ctcx::launch_pack_dense(pd, s));
+  if (a->flags & CTCEXT_FLAG_PROFILE) HIP_OR_FAIL(hipEventRecord(root.ev[4], s));
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_dense_outputs* o) {
+  if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  d->have = false;
+  d->dense.have = false;
+  int rc = ctcext_dense_validate(a, o);
+  if (rc != CTCEXT_OK) return rc;
+  hipStream_t s;
+  rc = dense_begin(d, a, &s);
+  if (rc != CTCEXT_OK) return rc;
+  if (a->batch_size > 0 && (((uintptr_t)o->decoded | (uintptr_t)o->alignment) & 7))
+    return fail(CTCEXT_INVALID_ARGUMENT, "dense outputs decoded and alignment need 8-byte alignment");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  root.s = s;
+  d->stats = ctcext_stats{};
+  if (a->batch_size > 0) {
+    const int helper_mode = helper_mode_from_env();
+    rc = a->dtype == CTCEXT_F32 ? dense_enqueue<float>(d, a, o, helper_mode)
+                                : dense_enqueue<double>(d, a, o, helper_mode);
+    if (rc != CTCEXT_OK) return rc;
+    // what the host knows; ctcext_dense_check fills the counters
+    d->stats.tier = use_gstate(a) ? 1 : 0;
+    d->stats.ring_frames = root.ring;
+    d->stats.record_bytes = root.rec_bytes;
+    d->stats.helper = root.helper;
+    d->stats.kernel = root.kernel;
+  }
+  d->B = a->batch_size;
+  d->dense.have = true;
+  d->dense.B = a->batch_size; d->dense.T = a->max_time; d->dense.P = a->top_paths; d->dense.flags = a->flags;
+  d->dense.s = s;
+  d->dense.pack_ms = 0;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_check(ctcext_decoder* d) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have) return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_check without a ctcext_decode_dense");
+  const int64_t B = d->dense.B;
+  const int P = d->dense.P;
+  if (B == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  HIP_OR_FAIL(hipMemcpyAsync(d->h_status.p, (const int32_t*)root.dstat.p + B, 4 * (size_t)B, hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipMemcpyAsync(d->h_item.p, root.item.p, sizeof(ctcx::ItemOut) * (size_t)B, hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipMemcpyAsync(d->h_kind.p, root.top_kind.p, 4 * (size_t)(B * P), hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+
+  ctcext_stats st{};
+  st.tier = d->stats.tier; st.ring_frames = d->stats.ring_frames; st.record_bytes = d->stats.record_bytes;
+  st.helper = d->stats.helper; st.kernel = d->stats.kernel;
+  if (d->dense.flags & CTCEXT_FLAG_PROFILE) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, root.ev[0], root.ev[1]) == hipSuccess) st.norm_kernel_ms = ms;
+    if (hipEventElapsedTime(&ms, root.ev[1], root.ev[2]) == hipSuccess) st.decode_kernel_ms = ms;
+    if (hipEventElapsedTime(&ms, root.ev[2], root.ev[3]) == hipSuccess) st.traceback_ms = ms;
+    if (hipEventElapsedTime(&ms, root.ev[3], root.ev[4]) == hipSuccess) d->dense.pack_ms = ms;
+    (void)hipGetLastError();
+  }
+  const ctcx::ItemOut* io = (const ctcx::ItemOut*)d->h_item.p;
+  const int32_t* status = (const int32_t*)d->h_status.p;
+  int32_t any = 0;
+  int64_t first_len = -1;
+  for (int64_t b = 0; b < B; ++b) {
+    st.literal_frames += io[b].literal_steps;
+    st.literal_nonfinite += io[b].why_nonfinite;
+    st.literal_fill += io[b].why_fill;
+    st.duplicate_frames += io[b].dup_frames;
+    st.records_written += io[b].records;
+    any |= status[b];
+    if ((status[b] & CTCEXT_ITEM_LENGTH) && first_len < 0) first_len = b;
+  }
+  d->stats = st;
+  // ctcext_decode's own order: the table and the lengths before any device
+  // work, the hand-over timeout before TopPaths' leaves
+  if (any & CTCEXT_ITEM_TABLE)
+    return fail(CTCEXT_INVALID_ARGUMENT, "beam scorer table entries must be log-probabilities (<= 0)");
+  if (first_len >= 0)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "sequence_length(" + std::to_string(first_len) + ") <= " + std::to_string(d->dense.T));
+  if (any & CTCEXT_ITEM_HELPER_TIMEOUT)
+    return fail(CTCEXT_INTERNAL, "decode kernel: a helper-wave hand-over wait timed out");
+  if (any & CTCEXT_ITEM_FEW_LEAVES)
+    return fail(CTCEXT_INVALID_ARGUMENT, "Less leaves in the beam search than requested.");
+  const int32_t* kinds = (const int32_t*)d->h_kind.p;
+  for (int64_t q = 0; q < B * P; ++q) d->stats.no_label_paths += (kinds[q] < 0) ? 1 : 0;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_pack_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !(d->dense.flags & CTCEXT_FLAG_PROFILE))
+    return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE dense decode checked yet");
+  *ms = d->dense.pack_ms;
   return CTCEXT_OK;
 }
 
@@ -1330,6 +1613,7 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
                                                std::to_string(a.max_frames));
   }
   d->have = false;
+  d->dense.have = false;   // (the workspace ctcext_dense_check reads is this call's now)
   if (B > 0) {
     rc = a.dtype == CTCEXT_F32 ? stream_push_t<float>(st, c, hcl, sizes, s) : stream_push_t<double>(st, c, hcl, sizes, s);
     if (rc != CTCEXT_OK) return rc;

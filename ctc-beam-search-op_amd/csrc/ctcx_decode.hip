@@ -17,6 +17,8 @@
 //                     the records backwards (LabelSeq / AlignmentLabelSeq).
 //   ctcx_scan         per (path, kind) exclusive scan of sequence lengths.
 //   ctcx_pack         int64 SparseTensor components (StoreAllDecodedSequences).
+//   ctcx_dense_prologue, ctcx_pack_dense   the enqueue-only path: lengths and
+//                     table checked on the device, padded [B][P][Tmax] outputs.
 //
 // The beam update per frame has two exact implementations:
 //   * the FAST path (exact_step, whole wave): beams sit at LDS slots; offers are
@@ -7355,6 +7357,81 @@ __global__ __launch_bounds__(64) void ctcx_pack(PackParams pp) {
   }
 }
 
+// ---- the dense, enqueue-only path (ctcext_decode_dense): everything the
+// synchronous call decides on the host from data, decided here instead
+
+// check_table_t's rule on the device table: *bad becomes nonzero if an entry
+// is > 0 or NaN (the host's memset node zeroes it before the launch).
+template <typename T>
+__global__ __launch_bounds__(256) void ctcx_dense_table_scan(const T* tab, int64_t n, int32_t* bad) {
+  int any = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    any |= !(tab[i] <= T(0)) ? 1 : 0;
+  if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(bad, 1);
+}
+
+// check_lengths on the device: the lengths the kernels read (a length above
+// Tmax, and every length under a bad table, is 0; a negative one stays, the
+// kernels read it as 0) and the status bits known before the decode.
+__global__ __launch_bounds__(256) void ctcx_dense_prologue(DensePrologueParams pp) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= pp.B) return;
+  const int32_t v = pp.seq_len[b];
+  int32_t st = 0;
+  if (pp.table_bad && *pp.table_bad) st |= kItemTable;
+  if (v > pp.Tmax) st |= kItemLength;
+  pp.sl[b] = st ? 0 : v;
+  pp.pre[b] = st;
+}
+
+// The padded outputs: one block per (item, path, kind) row of Tmax int64.
+// Element i is the traceback's reversed walk read backwards below the row's
+// length and pad_value from there on.  A row starts on an 8-byte boundary
+// (odd Tmax, or an output view): the element before the first 16-byte
+// boundary and the one after the last pair are written alone, the pairs
+// between them as 16-byte stores.  An item with any status bit is empty.
+__global__ __launch_bounds__(256) void ctcx_pack_dense(PackDenseParams pp) {
+  typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
+  const int64_t g = blockIdx.x;                 // ((b * P) + p) * 2 + w
+  const int w = (int)(g & 1);
+  const int64_t bpp = g >> 1;
+  const int64_t b = bpp / pp.P;
+  const int p = (int)(bpp - b * pp.P);
+  const int64_t T_ = pp.Tmax;
+  int32_t st = pp.pre[b];
+  if (pp.item[b].pad != 0) st |= kItemHelperTimeout;
+  if (!(st & (kItemLength | kItemTable)) && pp.item[b].n_leaves < pp.P) st |= kItemFewLeaves;
+  int64_t n = st ? 0 : pp.len[((int64_t)p * 2 + w) * pp.B + b];
+  n = n < 0 ? 0 : n > T_ ? T_ : n;
+  const int32_t* s = pp.seq + g * T_;
+  int64_t* out = (w ? pp.alignment : pp.decoded) + bpp * T_;
+  const int64_t pad = pp.pad_value;
+  auto at = [&](int64_t i) -> int64_t { return i < n ? (int64_t)s[n - 1 - i] : pad; };
+  const int64_t head = (int64_t)(((uintptr_t)out >> 3) & 1) < T_ ? (int64_t)(((uintptr_t)out >> 3) & 1) : T_;
+  const int64_t pairs = (T_ - head) >> 1;
+  for (int64_t q = threadIdx.x; q < pairs; q += 256) {
+    const int64_t i = head + 2 * q;
+    i64x2 v;
+    v.x = at(i);
+    v.y = at(i + 1);
+    *(i64x2*)(out + i) = v;
+  }
+  if (threadIdx.x == 0) {
+    if (head) out[0] = at(0);
+    const int64_t tail = head + 2 * pairs;
+    if (tail < T_) out[tail] = at(tail);
+    (w ? pp.alignment_length : pp.decoded_length)[bpp] = (int32_t)n;
+    if (w == 0) {
+      if (pp.f64) ((double*)pp.out_log_prob)[bpp] = st ? -__builtin_inf() : ((const double*)pp.log_prob)[bpp];
+      else ((float*)pp.out_log_prob)[bpp] = st ? -__builtin_inff() : ((const float*)pp.log_prob)[bpp];
+      if (p == 0) {
+        pp.status[b] = st;
+        pp.status_ws[b] = st;
+      }
+    }
+  }
+}
+
 #endif  // CTCX_PART == 0 (the non-template kernels)
 
 }  // namespace ctcx
@@ -7840,6 +7917,39 @@ hipError_t launch_pack(const PackParams& pp, hipStream_t s) {
   const int64_t n = pp.B * pp.P * 2;
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(ctcx_pack, dim3((unsigned)n), dim3(64), 0, s, pp);
+  return hipGetLastError();
+}
+
+// The dense path's prologue: with a bigram table (table_n entries of float,
+// or double with f64) its scan into *bad first, then the lengths.
+hipError_t launch_dense_prologue(DensePrologueParams pp, const void* table, int64_t table_n, int f64, int32_t* bad,
+                                 hipStream_t s) {
+  if (pp.B == 0) return hipSuccess;
+  if (pp.B > 0x7fffffffLL) return hipErrorInvalidValue;
+  pp.table_bad = nullptr;
+  if (table && table_n > 0) {
+    hipError_t e = hipMemsetAsync(bad, 0, 4, s);
+    if (e != hipSuccess) return e;
+    const int64_t blocks = (table_n + 255) / 256 < 1024 ? (table_n + 255) / 256 : 1024;
+    if (f64)
+      hipLaunchKernelGGL(ctcx_dense_table_scan<double>, dim3((unsigned)blocks), dim3(256), 0, s, (const double*)table,
+                         table_n, bad);
+    else
+      hipLaunchKernelGGL(ctcx_dense_table_scan<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)table,
+                         table_n, bad);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    pp.table_bad = bad;
+  }
+  hipLaunchKernelGGL(ctcx_dense_prologue, dim3((unsigned)((pp.B + 255) / 256)), dim3(256), 0, s, pp);
+  return hipGetLastError();
+}
+
+hipError_t launch_pack_dense(const PackDenseParams& pp, hipStream_t s) {
+  const int64_t n = pp.B * pp.P * 2;
+  if (n == 0) return hipSuccess;
+  if (n > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ctcx_pack_dense, dim3((unsigned)n), dim3(256), 0, s, pp);
   return hipGetLastError();
 }
 #endif  // CTCX_PART == 0

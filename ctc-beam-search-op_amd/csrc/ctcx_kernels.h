@@ -245,6 +245,36 @@ struct PackParams {
   int64_t* const* val;      // [P*2] -> int64 [n]
 };
 
+// The dense, enqueue-only path (ctcext_decode_dense): per-item status bits
+// (= CTCEXT_ITEM_*), the prologue and the padded pack.
+constexpr int32_t kItemLength = 1, kItemFewLeaves = 2, kItemHelperTimeout = 4, kItemTable = 8;
+
+struct DensePrologueParams {
+  const int32_t* seq_len;   // [B] the caller's lengths
+  int32_t* sl;              // [B] sanitised: a length above Tmax, or any length under a bad table, is 0
+  int32_t* pre;             // [B] kItemLength / kItemTable
+  const int32_t* table_bad; // one word, nonzero: the bigram table holds an entry > 0 or NaN (null: no table)
+  int64_t Tmax, B;
+};
+
+struct PackDenseParams {
+  const int32_t* seq;       // as TraceParams::seq
+  const int32_t* len;       // [P][2][B]
+  const ItemOut* item;      // [B]
+  const int32_t* pre;       // [B] the prologue's status bits
+  const void* log_prob;     // [B][P] of T
+  int64_t Tmax, B;
+  int32_t P, f64;
+  int64_t pad_value;
+  int64_t* decoded;         // [B][P][Tmax]
+  int64_t* alignment;       // [B][P][Tmax]
+  int32_t* decoded_length;  // [B][P]
+  int32_t* alignment_length;// [B][P]
+  void* out_log_prob;       // [B][P] of T
+  int32_t* status;          // [B] the caller's
+  int32_t* status_ws;       // [B] the workspace copy ctcext_dense_check reads
+};
+
 // Size of the per-frame LDS hash table of new leaves (power of two >= 2W).
 __host__ __device__ inline int htab_size(int W) {
   int n = 16;

@@ -43,6 +43,15 @@ EXPORTED_SYMBOLS = ("ctcext_create", "ctcext_create_sharded", "ctcext_destroy", 
                     "ctcext_stream_validate", "ctcext_stream_validate_chunk", "ctcext_stream_open",
                     "ctcext_stream_push", "ctcext_stream_frames", "ctcext_stream_reset", "ctcext_stream_close")
 CTCEXT_KERNEL_STREAM = 0x8000   # ctcext_stats.kernel: a stream build of the decode kernel
+# the dense, enqueue-only decode (CTCEXT_HAS_DENSE)
+DENSE_SYMBOLS = ("ctcext_dense_validate", "ctcext_dense_reserve", "ctcext_decode_dense", "ctcext_dense_check",
+                 "ctcext_dense_pack_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + DENSE_SYMBOLS
+CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
+CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
+CTCEXT_ITEM_FEW_LEAVES = 2       # fewer leaves than top_paths
+CTCEXT_ITEM_HELPER_TIMEOUT = 4   # a two-wave hand-over wait ran out
+CTCEXT_ITEM_TABLE = 8            # the bigram table holds an entry > 0 or NaN
 
 
 class DecodeArgs(ctypes.Structure):
@@ -80,6 +89,14 @@ class Chunk(ctypes.Structure):
                 ("inputs_format", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("inputs_stride_t", ctypes.c_int64), ("inputs_stride_b", ctypes.c_int64),
                 ("stream", ctypes.c_void_p)]
+
+
+class DenseOutputs(ctypes.Structure):
+    """ctcext_dense_outputs: the padded device outputs of ctcext_decode_dense."""
+    _fields_ = [("decoded", ctypes.c_void_p), ("decoded_length", ctypes.c_void_p),
+                ("alignment", ctypes.c_void_p), ("alignment_length", ctypes.c_void_p),
+                ("log_probability", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("pad_value", ctypes.c_int64)]
 
 
 class PathSizes(ctypes.Structure):
@@ -191,6 +208,17 @@ def load():
         lib.ctcext_stream_reset.restype = ctypes.c_int
         lib.ctcext_stream_close.argtypes = [ctypes.c_void_p]
         lib.ctcext_stream_close.restype = None
+    if hasattr(lib, "ctcext_decode_dense"):   # (CTCEXT_HAS_DENSE; older builds stay loadable for A/B runs)
+        lib.ctcext_dense_validate.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.POINTER(DenseOutputs)]
+        lib.ctcext_dense_validate.restype = ctypes.c_int
+        lib.ctcext_dense_reserve.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs)]
+        lib.ctcext_dense_reserve.restype = ctypes.c_int
+        lib.ctcext_decode_dense.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs), ctypes.POINTER(DenseOutputs)]
+        lib.ctcext_decode_dense.restype = ctypes.c_int
+        lib.ctcext_dense_check.argtypes = [ctypes.c_void_p]
+        lib.ctcext_dense_check.restype = ctypes.c_int
+        lib.ctcext_dense_pack_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_pack_ms.restype = ctypes.c_int
     _lib = lib
     return lib
 

@@ -17,6 +17,10 @@ SparseTensor components of kernels.cc:163-257); ``log_probability`` is
 [batch_size, top_paths] of the input dtype.  Host inputs (numpy, lists, CPU
 torch tensors) give numpy outputs; device (HBM) torch tensors give device
 torch tensors.  Decoding always runs on the GPU through libctcext.so.
+
+``decode_dense`` is the enqueue-only form for GPU logits: padded
+``[B, top_paths, T]`` tensors instead of SparseTensor components, no host
+synchronisation, data-dependent errors deferred to ``dense_check``.
 """
 import collections
 import ctypes
@@ -363,6 +367,140 @@ def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
     a.inputs_stride_t, a.inputs_stride_b = int(st_t), int(st_b)
     return _decode_and_fetch(lib, a, [x, sl], shape, on_device, dev, table_dtype, index, outputs, devices,
                              scorer_table)
+
+
+DenseDecode = collections.namedtuple(
+    "DenseDecode",
+    ["decoded", "decoded_lengths", "alignment", "alignment_lengths", "log_probability", "status"])
+
+
+def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
+                 merge_repeated=False, blank_index=0, blank_label=-1, pad_value=-1,
+                 flags=0, scorer_table=None, out=None):
+    """Decode GPU logits into padded GPU tensors without waiting for anything.
+
+    The call validates what it can on the host, enqueues the whole decode on
+    ``torch.cuda.current_stream()`` and returns: no ``synchronize()``, no
+    ``.item()``, no ``.cpu()``.  It can be queued behind the acoustic model
+    and captured into a ``torch.cuda.graph`` (after one call, or a
+    ``ctcext_dense_reserve``, of the same shape has sized the workspace).
+
+    ``logits`` is a CUDA torch tensor, with the dtypes, strides and in-place
+    rules of ``decode_logits`` (a host tensor raises ``ValueError``: use
+    ``decode_logits`` for those).  ``lengths`` should be an int32 CUDA tensor;
+    any other form is converted, and that conversion copies and may block.
+    ``scorer_table`` must be a CUDA tensor.
+
+    Returns ``DenseDecode(decoded, decoded_lengths, alignment,
+    alignment_lengths, log_probability, status)``: ``decoded`` and
+    ``alignment`` are int64 ``[B, top_paths, T]``, row ``[b, p]`` holding path
+    ``p``'s labels in its first ``decoded_lengths[b, p]`` (``alignment_lengths
+    [b, p]``) elements and ``pad_value`` in the rest; the lengths are int32
+    ``[B, top_paths]``, ``log_probability`` ``[B, top_paths]`` of the compute
+    dtype, ``status`` int32 ``[B]``.  The tensors come from torch's caching
+    allocator on the current stream; ``out`` (a ``DenseDecode`` of contiguous
+    CUDA tensors of those shapes and dtypes) is written instead when given.
+
+    Errors that depend on the data are deferred.  ``status[b]`` is 0 for a
+    good item, else ``CTCEXT_ITEM_*`` bits (``_lib``): such an item has all
+    its rows empty -- lengths 0, rows all ``pad_value``, ``log_probability``
+    ``-inf`` -- and the other items are untouched by it.  ``dense_check()``
+    waits and raises what the synchronous call would have raised.
+    """
+    lib = _lib.load()
+    if not (_is_torch(logits) and logits.is_cuda):
+        raise ValueError("decode_dense takes CUDA torch tensors; use decode_logits for host inputs")
+    import torch
+    formats = {torch.float16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+               torch.bfloat16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_BF16),
+               torch.float32: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+               torch.float64: (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+    if logits.dtype not in formats:
+        _type_error("logits", str(logits.dtype).replace("torch.", ""), "float16, bfloat16, float32, float64")
+    code, fmt = formats[logits.dtype]
+    x = logits.detach()
+    if x.dim() == 3:
+        copy, shape, st_t, st_b = logits_layout(tuple(x.shape), x.stride(), batch_first)
+        if copy:
+            x = x.contiguous()
+    else:   # the C ABI raises the reference's "inputs is not a 3-Tensor"
+        x = x.contiguous()
+        shape, st_t, st_b = tuple(x.shape), 0, 0
+    dev = x.device
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    sl = _lengths_device(lengths, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if not stream:   # torch's legacy default stream: the null stream itself, not the decoder's own
+        flags = int(flags) | _lib.CTCEXT_FLAG_DENSE_NULL_STREAM
+    a = _args(x.data_ptr(), shape, code, True, sl.data_ptr(), tuple(sl.shape), beam_width, top_paths,
+              merge_repeated, blank_index, blank_label, flags, stream)
+    a.inputs_format = fmt
+    a.inputs_stride_t, a.inputs_stride_b = int(st_t), int(st_b)
+    fdt = torch.float32 if code == _lib.CTCEXT_F32 else torch.float64
+    tab = None
+    if scorer_table is not None:
+        if not (_is_torch(scorer_table) and scorer_table.is_cuda):
+            raise ValueError("decode_dense: scorer_table must be a CUDA torch tensor")
+        C = int(shape[2]) if len(shape) == 3 else 0
+        tab = scorer_table.detach().to(device=dev, dtype=fdt).contiguous()
+        if tuple(tab.shape) != (C + 1, C):
+            raise ValueError("scorer_table must be [num_classes + 1, num_classes] = [%d, %d], got %s"
+                             % (C + 1, C, tuple(tab.shape)))
+        a.scorer = _lib.CTCEXT_SCORER_BIGRAM
+        a.scorer_table = tab.data_ptr()
+    # every check that needs no data, on the host, before anything is allocated
+    rc = lib.ctcext_validate(ctypes.byref(a))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    T, B, P = int(shape[0]), int(shape[1]), int(top_paths)
+    want = (((B, P, T), torch.int64), ((B, P), torch.int32), ((B, P, T), torch.int64), ((B, P), torch.int32),
+            ((B, P), fdt), ((B,), torch.int32))
+    if out is None:
+        with torch.cuda.device(dev):
+            out = DenseDecode(*[torch.empty(s, dtype=dt, device=dev) for s, dt in want])
+    else:
+        out = DenseDecode(*out)
+        for name, t, (s, dt) in zip(DenseDecode._fields, out, want):
+            if not (_is_torch(t) and t.is_cuda and t.device == dev and tuple(t.shape) == s and t.dtype == dt
+                    and t.is_contiguous()):
+                raise ValueError("out.%s must be a contiguous %s tensor of shape %s on %s"
+                                 % (name, str(dt).replace("torch.", ""), s, dev))
+    o = _lib.DenseOutputs()
+    (o.decoded, o.decoded_length, o.alignment, o.alignment_length, o.log_probability,
+     o.status) = [t.data_ptr() for t in out]
+    o.pad_value = int(pad_value)
+    dec = get_decoder(index)
+    rc = lib.ctcext_decode_dense(dec.handle, ctypes.byref(a), ctypes.byref(o))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    dec.last_stats = dec.stats()
+    # x, sl and tab may be temporaries: they were allocated on this stream, and
+    # the caching allocator hands their memory out again in stream order
+    del x, sl, tab
+    return out
+
+
+def dense_check(device=None):
+    """Wait for the calling thread's last ``decode_dense`` on ``device``
+    (None: the current one) and report it as the synchronous call would have:
+    raises the same ``OpError`` subclass with the same message (a bad scorer
+    table, ``sequence_length(b) <= max_time``, a helper hand-over timeout,
+    "Less leaves in the beam search than requested.", in that order), prints
+    the reference's "No label seq available" lines, and returns the stats dict
+    with every counter filled."""
+    index = _device_index(device)
+    if index is None:
+        index = _current_device()
+    dec = getattr(_tls, "decoders", {}).get(int(index))
+    if dec is None:   # no handle yet on this thread: no dense call either
+        raise FailedPreconditionError("ctcext_dense_check without a ctcext_decode_dense",
+                                      _lib.CTCEXT_FAILED_PRECONDITION)
+    rc = dec.lib.ctcext_dense_check(dec.handle)
+    dec.last_stats = dec.stats()
+    if rc != _lib.CTCEXT_OK:
+        _raise(dec.lib, rc)
+    _print_no_label(dec.last_stats["no_label_paths"])
+    return dec.last_stats
 
 
 def _lengths_device(sequence_length, dev):

@@ -369,6 +369,87 @@ int ctcext_stream_reset(ctcext_stream* s, const int32_t* items, int64_t n);
 /* Close every stream before ctcext_destroy of its decoder. */
 void ctcext_stream_close(ctcext_stream* s);
 
+/* ---------------------------------------------------------------------------
+ * Dense, enqueue-only decode.  The outputs are padded device tensors of
+ * static shape instead of SparseTensor components whose sizes depend on the
+ * data, and every check that needs data runs on the device, so the call only
+ * enqueues: a caller with the logits on the GPU queues the decode behind the
+ * kernels that produce them and carries on, and the call can be captured into
+ * a HIP graph.  Errors that depend on data are deferred: they arrive per item
+ * in status[], and as a status code and message from ctcext_dense_check.
+ * New entry points and structs only (CTCEXT_ABI_VERSION is unchanged; detect
+ * them by CTCEXT_HAS_DENSE at build time or by symbol at run time).  One
+ * device: a handle of ctcext_create_sharded with more than one device answers
+ * CTCEXT_UNIMPLEMENTED. */
+#define CTCEXT_HAS_DENSE 1
+
+/* One more ctcext_decode_args.flags bit, read by ctcext_decode_dense and
+ * ctcext_dense_reserve only: with stream == NULL the work goes onto the null
+ * (legacy default) stream itself instead of the decoder's own stream, so that
+ * it is ordered behind work a framework queued there, without a sync. */
+enum { CTCEXT_FLAG_DENSE_NULL_STREAM = 512 };
+
+/* status[b] bits; 0 = the item's rows are its hypotheses. */
+enum { CTCEXT_ITEM_LENGTH = 1,         /* sequence_length(b) > max_time: item not decoded */
+       CTCEXT_ITEM_FEW_LEAVES = 2,     /* fewer leaves than top_paths (decoder.h:240-243) */
+       CTCEXT_ITEM_HELPER_TIMEOUT = 4, /* two-wave hand-over wait ran out (never in a correct run) */
+       CTCEXT_ITEM_TABLE = 8 };        /* bigram table holds an entry > 0 or NaN (every item) */
+
+/* Device pointers, all of them.  Row [b][p] of decoded / alignment holds path
+ * p's label sequence in label order in its first decoded_length[b][p] /
+ * alignment_length[b][p] elements and pad_value in the rest.  An item with
+ * any status bit has all its top_paths rows empty: lengths 0, rows all
+ * pad_value, log_probability -inf; the other items are untouched by it.
+ * decoded and alignment need 8-byte alignment only. */
+typedef struct {
+  int64_t* decoded;           /* [batch][top_paths][max_time], label order, padded */
+  int32_t* decoded_length;    /* [batch][top_paths] */
+  int64_t* alignment;         /* [batch][top_paths][max_time] */
+  int32_t* alignment_length;  /* [batch][top_paths] */
+  void*    log_probability;   /* [batch][top_paths] of dtype */
+  int32_t* status;            /* [batch] CTCEXT_ITEM_* bits, 0 = good */
+  int64_t  pad_value;         /* written past each row's length */
+} ctcext_dense_outputs;
+
+/* Host only, no HIP call: every check of ctcext_validate that needs no data,
+ * with the same messages in the same order, then (CTCEXT_INVALID_ARGUMENT)
+ *   "ctcext_decode_dense needs device inputs"   (inputs_on_device == 0)
+ *   "null dense output pointer"                 (batch_size > 0 only) */
+int ctcext_dense_validate(const ctcext_decode_args* args, const ctcext_dense_outputs* out);
+/* Grows the handle's workspace to what ctcext_decode_dense of these arguments
+ * needs (the pointers in args are not read); launches nothing.  May allocate
+ * and block. */
+int ctcext_dense_reserve(ctcext_decoder* dec, const ctcext_decode_args* args);
+/* Validates on the host (ctcext_dense_validate), then enqueues on one stream
+ * (args->stream; NULL: the decoder's own, or the null stream with
+ * CTCEXT_FLAG_DENSE_NULL_STREAM): a prologue that checks the lengths and the
+ * bigram table on the device, the pre-pass, decode and traceback of
+ * ctcext_decode, and the padded pack.  A call whose workspace already fits (a
+ * ctcext_dense_reserve or an earlier call of the same or a larger shape)
+ * makes no allocation, no free, no host-blocking HIP call and no
+ * device-to-host copy.  The flags are ctcext_decode's; there is never a
+ * re-decode (a helper hand-over timeout is CTCEXT_ITEM_HELPER_TIMEOUT).
+ * ctcext_fetch after it answers CTCEXT_FAILED_PRECONDITION.  ctcext_stats
+ * after it: tier, kernel, helper, record_bytes, ring_frames; the counters 0. */
+int ctcext_decode_dense(ctcext_decoder* dec, const ctcext_decode_args* args, const ctcext_dense_outputs* out);
+/* Waits for the stream of the last ctcext_decode_dense, fills every
+ * ctcext_stats counter, and returns what ctcext_decode would have returned
+ * for the same inputs, message included; the first match wins:
+ *   CTCEXT_ITEM_TABLE          CTCEXT_INVALID_ARGUMENT    "beam scorer table entries must be log-probabilities (<= 0)"
+ *   lowest b with _LENGTH      CTCEXT_FAILED_PRECONDITION "sequence_length(b) <= max_time" (the numbers)
+ *   any _HELPER_TIMEOUT        CTCEXT_INTERNAL            "decode kernel: a helper-wave hand-over wait timed out"
+ *   any _FEW_LEAVES            CTCEXT_INVALID_ARGUMENT    "Less leaves in the beam search than requested."
+ * Without a preceding ctcext_decode_dense (or after a later ctcext_decode or
+ * stream push on the handle): CTCEXT_FAILED_PRECONDITION.  It reads the
+ * handle's workspace, not the caller's status[]; after the replay of a graph
+ * that captured the call (and the caller's wait for the stream it replayed
+ * on) it reports that replay. */
+int ctcext_dense_check(ctcext_decoder* dec);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE, the time of the pack kernel of the
+ * last ctcext_decode_dense in ms, after its ctcext_dense_check (the other
+ * kernels' times are in ctcext_stats).  0 for a call replayed from a graph. */
+int ctcext_dense_pack_ms(ctcext_decoder* dec, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
