@@ -11,6 +11,7 @@ import torch
 
 import ctcext_amd
 import oracle
+import range_inputs
 from ctcext_amd import _lib, ops
 from test_gpu_kernel_matrix import SMALL
 
@@ -67,6 +68,8 @@ def _assert_empty(out, items, pad):
 
 
 def _inputs(rng, kind, T, B, C, dtype=np.float32):
+    if kind in ("logsoftmax", "edges"):   # the whole float range (tests/range_inputs.py)
+        return range_inputs.family(rng, kind, T, B, C, dtype)
     x = rng.standard_normal((T, B, C))
     if kind == "ties":
         x = np.round(x * 2) / 2
@@ -79,7 +82,9 @@ def _kw(kind, C):
     # merge_repeated both ways, a non-zero blank, a blank_label that is not the default
     return {"normal": dict(merge_repeated=False, blank_index=0, blank_label=C),
             "ties": dict(merge_repeated=True, blank_index=C // 2, blank_label=C + 3),
-            "neg_inf": dict(merge_repeated=True, blank_index=0, blank_label=-2)}[kind]
+            "neg_inf": dict(merge_repeated=True, blank_index=0, blank_label=-2),
+            "logsoftmax": dict(merge_repeated=True, blank_index=C // 2, blank_label=C + 3),
+            "edges": dict(merge_repeated=False, blank_index=0, blank_label=C)}[kind]
 
 
 def _table(rng, C, dtype):
@@ -131,6 +136,31 @@ def test_dense_matches_oracle(name, monkeypatch):
         # after a dense call there is nothing for ctcext_fetch
         with pytest.raises(ctcext_amd.FailedPreconditionError):
             ctcext_amd.get_decoder(0).fetch([[0], [0], [0], [0], [0], [0]], 0, True)
+
+
+@pytest.mark.parametrize("kind", ["logsoftmax", "edges"])
+@pytest.mark.parametrize("name", ["two_wave", "large_c"])
+def test_dense_numeric_range(name, kind, monkeypatch):
+    """log_softmax outputs, and terms at expf's underflow bound and in its
+    subnormal band, through the enqueue-only call: a small-C and a large-C
+    kernel family."""
+    (T, C, W, P), dtype, helper_env, flags, bigram, kernel = PARITY[name]
+    monkeypatch.delenv("CTCEXT_HELPER", raising=False)
+    rng = range_inputs.rng_for("dense/%s/%s" % (name, kind))
+    B = 3
+    sl = np.array([T, max(T - 3, 1), T // 2], np.int32)
+    kw = _kw(kind, C)
+    x = _inputs(rng, kind, T, B, C, dtype)
+    range_inputs.assert_census(kind, np.concatenate([x[:n, b] for b, n in enumerate(sl)]))
+    ref = oracle.decode(x, sl, W, P, **kw)
+    out = ctcext_amd.decode_dense(torch.as_tensor(x, device=DEV), torch.as_tensor(sl, device=DEV), W, P,
+                                  batch_first=False, pad_value=PAD, flags=flags, **kw)
+    _assert_dense(out, to_dense(ref, B, P, T, PAD))
+    st = ctcext_amd.dense_check()
+    assert st["kernel"]["launched"], st
+    for key, v in kernel.items():
+        assert st["kernel"][key] == v, (name, kind, key, st["kernel"])
+    assert st["literal_nonfinite"] == 0, st
 
 
 def test_dense_bf16_vocabulary_slice_in_place():

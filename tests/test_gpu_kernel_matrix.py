@@ -17,6 +17,12 @@ limit: the widest beam of the tier and one past it, the two-wave layouts'
 last fitting class counts, the record ring behind a run-time-W layout.  LDS
 accesses past the allocation do not fault, so a disagreement between the
 kernel's carve and decode_lds_bytes shows only as wrong outputs, here.
+
+The last part decodes the families of tests/range_inputs.py (the whole float
+range: expf's and exp's subnormal band and underflow bound, one dominant
+class, logits near 1e6..3e7, overflowing differences, subnormals) through
+every instantiation the small shapes reach, and through one-frame decodes
+whose log-probabilities are x_l - norm itself.
 """
 import zlib
 
@@ -27,6 +33,7 @@ import ctcext_amd
 from ctcext_amd import _lib
 from parity_util import compare
 import oracle
+import range_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -114,7 +121,17 @@ for _name in ("f32_hw_rn1_wc128_small", "f32_hw_rn1_wc128_big", "f32_hw_rn2_wc25
 
 KINDS = {"normal": dict(merge_repeated=False, blank_index=0),
          "ties": dict(merge_repeated=True, blank_index=None),    # (None: C // 2, a non-zero blank)
-         "neg_inf": dict(merge_repeated=True, blank_index=0)}
+         "neg_inf": dict(merge_repeated=True, blank_index=0),
+         # the families of range_inputs (test_instantiation_numeric_range)
+         "logsoftmax": dict(merge_repeated=True, blank_index=None),
+         "edges": dict(merge_repeated=False, blank_index=0),
+         "banded": dict(merge_repeated=False, blank_index=0),
+         "onehot": dict(merge_repeated=True, blank_index=None),
+         "offset": dict(merge_repeated=False, blank_index=0),
+         "huge": dict(merge_repeated=True, blank_index=None),
+         "subnormal": dict(merge_repeated=False, blank_index=0),
+         "peaked": dict(merge_repeated=True, blank_index=None)}
+BASE_KINDS = ("neg_inf", "normal", "ties")   # what every shape of a cell runs
 
 _observed = set()
 
@@ -128,6 +145,8 @@ def _stats():
 
 
 def _inputs(rng, kind, T, C, dtype):
+    if kind in range_inputs.FAMILIES:
+        return range_inputs.family(rng, kind, T, 2, C, NP[dtype])
     x = rng.standard_normal((T, 2, C))
     if kind == "ties":
         x = np.round(x * 2) / 2
@@ -174,7 +193,7 @@ def _run_cell(name, monkeypatch, kinds=None, want_ref=True):
             # the shape is inside the LDS tier by the library's own limit
             assert W <= ctcext_amd.get_decoder(0).lib.ctcext_max_beam_width(C, CODE[dtype]), (C, W)
         tab = _bigram_table(rng, C, dtype) if scorer == "bigram" else None
-        for kind in kinds or own_kinds or sorted(KINDS):
+        for kind in kinds or own_kinds or BASE_KINDS:
             kw = dict(KINDS[kind])
             if kw["blank_index"] is None:
                 kw["blank_index"] = C // 2
@@ -281,3 +300,100 @@ def test_ring_dropped_when_the_layout_fills_the_lds():
     W = ctcext_amd.get_decoder(0).lib.ctcext_max_beam_width(33000, _lib.CTCEXT_F32)
     st = _edge_case(33000, W, F32, flags=_lib.CTCEXT_FLAG_RING_MIN)
     assert st["tier"] == 0 and st["ring_frames"] == 0, st
+
+
+# ---- the whole float range through every instantiation of the small shapes
+
+# the cells built from SMALL (24 one-wave, six two-wave) and the four
+# global-state ones; not the run-time-W cells, whose class counts add nothing here
+RANGE_CELLS = sorted(n for n, c in CELLS.items() if c[1][0] in list(SMALL.values()) + [(30, 20, 380, 5), (10, 8, 40, 3)])
+RANGE_KINDS = tuple(k for k in range_inputs.FAMILIES if k != "banded")
+assert len(RANGE_CELLS) == 34
+
+
+def _live_rows(x, sl):
+    return np.concatenate([x[:n, b] for b, n in enumerate(sl)])
+
+
+@pytest.mark.parametrize("kind", RANGE_KINDS)
+@pytest.mark.parametrize("name", RANGE_CELLS)
+def test_instantiation_numeric_range(name, kind, monkeypatch):
+    """As _run_cell: all seven outputs are the oracle's, the log-probabilities
+    bit for bit, and the kernel that ran is the cell's (the family did not
+    divert the call).  The all-finite families must also stay off the literal
+    path's non-finite replay: no logit and no total of theirs is non-finite,
+    so the fast path is the code under test."""
+    row, shapes, helper_env, flags, _ = CELLS[name]
+    tier, dtype, scorer = row[:3]
+    if helper_env is None:
+        monkeypatch.delenv("CTCEXT_HELPER", raising=False)
+    else:
+        monkeypatch.setenv("CTCEXT_HELPER", helper_env)
+    (T, C, W, P), = shapes
+    rng = range_inputs.rng_for("%s/%s" % (name, kind))
+    sl = np.array([T, max(T - 3, 1)], np.int32)
+    tab = _bigram_table(rng, C, dtype) if scorer == "bigram" else None
+    kw = dict(KINDS[kind])
+    if kw["blank_index"] is None:
+        kw["blank_index"] = C // 2
+    x = _inputs(rng, kind, T, C, dtype)
+    range_inputs.assert_census(kind, _live_rows(x, sl))
+    try:
+        out, ref = _decode_both(x, sl, W, P, kw, tab, flags)
+    except (oracle.OracleError, ctcext_amd.OpError) as e:
+        raise AssertionError("%s %s: %s" % (name, kind, e))
+    st = _stats()
+    k = st["kernel"]
+    assert k["launched"] and _stat_row(k) == row, (name, kind, k)
+    assert st["tier"] == tier
+    compare(out, ref, P, lp_exact=True)
+    assert np.isfinite(ref.log_probability).all()
+    if kind == "peaked" and scorer == "base":   # (a bigram table's entries move the totals off 0)
+        # merged alignments added log1pf(a subnormal expf), itself subnormal,
+        # to a total of 0 (the double kernels add the same float term): a best
+        # path whose log-probability is a sum of those, above 0
+        lp = np.asarray(ref.log_probability)[:, 0]
+        assert ((lp > 0) & (lp < 1e-30)).any(), (name, lp)
+    if kind != "huge":
+        assert st["literal_nonfinite"] == 0, (name, kind, st)
+
+
+@pytest.mark.parametrize("dtype,kind", [(d, k) for d in (F32, F64) for k in range_inputs.FAMILIES
+                                        if (d, k) != (F64, "banded")])   # (banded: expf_t_core / expf_t_le0, float only)
+@pytest.mark.parametrize("C", [8, 29, 64])
+def test_one_frame_log_probability_is_x_minus_norm(C, dtype, kind, monkeypatch):
+    """T = 1, W = C: the leaves are the labels and the empty path, each
+    log-probability x_l - norm itself.  Pins ctcx_row_norm (the decode's own
+    normaliser, C <= 64) at the class counts ctcext_row_facts cannot reach;
+    32 items so that every condition of the family's census is met."""
+    monkeypatch.delenv("CTCEXT_HELPER", raising=False)
+    B, W, P = 32, C, min(C, 5)
+    rng = range_inputs.rng_for("one_frame/%d/%s/%s" % (C, dtype, kind))
+    x = range_inputs.family(rng, kind, 1, B, C, NP[dtype])
+    kw = dict(KINDS[kind])
+    if kw["blank_index"] is None:
+        kw["blank_index"] = C // 2
+    if kind == "huge":
+        # a label whose x_l - norm overflows to -inf is no leaf, and one item
+        # with fewer than P leaves fails the whole call on both sides: keep the
+        # items with P labels left (a condition on the inputs, from the host)
+        with np.errstate(over="ignore"):
+            p = x[0] - oracle.row_norm(x[0])[:, None]
+        p[:, kw["blank_index"]] = -np.inf
+        x = np.ascontiguousarray(x[:, (p > -np.inf).sum(axis=1) >= P])
+        B = x.shape[1]
+        assert B >= 4, (C, dtype, B)
+    range_inputs.assert_census(kind, x)
+    sl = np.ones(B, np.int32)
+    try:
+        ref = oracle.decode(x, sl, W, P, **kw)
+        out = ctcext_amd.ctc_ext_beam_search_decoder(x, sl, W, P, **kw)
+    except (oracle.OracleError, ctcext_amd.OpError) as e:
+        raise AssertionError("C=%d %s %s: %s" % (C, dtype, kind, e))
+    compare(out, ref, P, lp_exact=True)
+    if kind != "huge":
+        # the best path's log-probability by its definition
+        rows = x[0]
+        want = (rows - oracle.row_norm(rows)[:, None]).max(axis=1)
+        np.testing.assert_array_equal(np.asarray(ref.log_probability)[:, 0], want)
+        assert _stats()["literal_nonfinite"] == 0, _stats()

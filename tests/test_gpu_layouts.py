@@ -12,6 +12,7 @@ import ctcext_amd
 from ctcext_amd import _lib
 from parity_util import compare, to_numpy
 import oracle
+import range_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -156,16 +157,23 @@ def _special(kind, half, C):
         x = (np.sign(x) * rng.integers(1, 8, size=x.shape) * tiny).astype(np.float32)
     elif kind == "ties":
         x = (np.round(x * 2) / 2).astype(np.float32)   # a 0.5 grid: exact in both formats, heavy ties
+    elif kind in ("logsoftmax", "edges"):
+        # the whole float range, rounded to the half type (bf16's grid
+        # straddles expf's underflow bound at -103.5 / -104; fp16 turns the
+        # family's -1e30 into -inf)
+        x = range_inputs.family(range_inputs.rng_for("layouts/%s/%d" % (kind, C)), kind, T, B, C, np.float32)
     xh = torch.from_numpy(x).to(HALVES[half])
     wide = xh.float().numpy()
     if kind == "tiny":
         assert (wide != 0).all() and (np.abs(wide) < (2.0 ** -14 if half == "fp16" else 2.0 ** -126)).all()
+    if kind in ("logsoftmax", "edges"):   # finite terms below the bound survive the rounding
+        assert range_inputs.census(wide)["below"] >= 1
     return xh, wide, np.array([T, T - 1, T, T - 5], np.int32)
 
 
 @pytest.mark.parametrize("half", sorted(HALVES))
 @pytest.mark.parametrize("C,W", [(6, 8), (72, 16), (1000, 16)])
-@pytest.mark.parametrize("kind", ["nonfinite", "tiny", "ties"])
+@pytest.mark.parametrize("kind", ["nonfinite", "tiny", "ties", "logsoftmax", "edges"])
 def test_special_values(kind, C, W, half):
     """Against the oracle and against this library's own float32 decode of the
     widened tensor: the same literal-path decisions, the same outputs."""
@@ -175,6 +183,8 @@ def test_special_values(kind, C, W, half):
         ref, rerr = oracle.decode(wide, sl, W, P, **KW), None
     except oracle.OracleError as e:
         ref, rerr = None, str(e)
+    if kind in ("logsoftmax", "edges"):
+        assert rerr is None, rerr   # (an error on both sides would stand in for a comparison)
     dec = ctcext_amd.get_decoder(0)
 
     def run(fn):

@@ -15,7 +15,14 @@ NaN / +inf rows included, and rows past an item's length are left alone.
 Rows of more than 8192 classes run ctcx_row_prep: with more than 64 KB of
 dynamic LDS from C = 16384, with the row exactly filling its LDS stage at
 C * sizeof(T) = 128 KB, and reading the row from global memory past that;
-ctcext_stats.kernel says which of them ran."""
+ctcext_stats.kernel says which of them ran.
+
+The last part feeds every path the families of range_inputs (softmax terms in
+expf's / exp's subnormal-result band, at and below the underflow bound, sums
+near 1, one dominant class, logits near 1e6..3e7, overflowing differences,
+subnormals): the normal rows above keep every term within [-30, 0] or at
+-inf.  The census of each input is asserted, so a case cannot pass without
+the values it exists for."""
 import ctypes
 import os
 import sys
@@ -27,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ctc-beam-search-op_amd"))
 
 import oracle  # noqa: E402  (tests/conftest.py puts oracle/ on the path)
+import range_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -251,3 +259,62 @@ def test_row_facts_f64_header_and_block_maxima(C):
     x[1, 0, C // 5] = np.nan
     x[0, 2, 1] = np.inf
     _check_f64(x, C, 0, seq_len=[4, 0, 2])
+
+
+# ---- the whole float range (tests/range_inputs.py)
+
+# every pre-pass path and the NV boundary widths: (C, the pre-pass that must run)
+RANGE_F32 = sorted(set(F32_PATHS) | {(1020, "facts_fused"), (2048, "facts_norm"), (3072, "facts_norm")})
+
+
+@pytest.mark.parametrize("kind", range_inputs.FAMILIES)
+@pytest.mark.parametrize("C,path", RANGE_F32)
+def test_row_facts_numeric_range_f32(C, path, kind):
+    rng = range_inputs.rng_for("prepass/f32/%d/%s" % (C, kind))
+    for blank in (0, C - 1):
+        x = range_inputs.family(rng, kind, 2, 3, C, np.float32)
+        range_inputs.assert_census(kind, x, wide_rows=C >= 1000)
+        _check_f32(x, C, blank)
+        assert _run.prepass == path, (C, kind, _run.prepass)
+
+
+def test_row_facts_numeric_range_mixed_wave():
+    """ctcx_row_norm_v4 (facts_norm widths) sums one row per lane and picks
+    expf_t_core or expf_t_le0 per 16-term batch by a wave-wide ballot: 8 x 8
+    live rows fill a wave, rows of every family share it, and the banded rows
+    keep the batches of their lower classes on the core path with subnormal
+    results while the upper ones take the le0 path."""
+    C, T, B = 1056, 8, 8
+    rng = range_inputs.rng_for("prepass/mixed_wave")
+    x = range_inputs.family(rng, "banded", T, B, C, np.float32)
+    range_inputs.assert_census("banded", x)
+    _check_f32(x, C, 0)
+    assert _run.prepass == "facts_norm"
+    # rows of different kinds in one wave: every fourth row stays banded
+    for i, kind in enumerate(k for k in range_inputs.FAMILIES if k != "banded"):
+        rows = [r for r in range(T * B) if r % 4 and r % 7 == i]
+        other = range_inputs.family(rng, kind, T, B, C, np.float32)
+        x.reshape(T * B, C)[rows] = other.reshape(T * B, C)[rows]
+    range_inputs.assert_census("banded", x[:, 0])     # (rows 0, 8, ...: r % 4 == 0)
+    _check_f32(x, C, C - 1)
+    assert _run.prepass == "facts_norm"
+
+
+@pytest.mark.parametrize("kind", ["logsoftmax", "edges", "onehot", "huge", "subnormal"])
+@pytest.mark.parametrize("C", sorted(F64_PATHS))
+def test_row_facts_numeric_range_f64(C, kind):
+    rng = range_inputs.rng_for("prepass/f64/%d/%s" % (C, kind))
+    x = range_inputs.family(rng, kind, 2, 3, C, np.float64)
+    cs = range_inputs.assert_census(kind, x, wide_rows=C >= 1000)
+    lo, hi = range_inputs.LOG_NEAR_ONE
+    s = range_inputs.row_sums64(x)
+    if kind == "logsoftmax":
+        # log's near-1 branch proper (a sum in the interval that is not 1:
+        # the runner-up of a scale-120 row lies 3 to 37 below its maximum)
+        # and its == 1.0 early return (norm == max), at every width
+        assert ((s >= lo) & (s < hi) & (s != 1.0)).any(), (C, s)
+        assert cs["norm_is_max"] >= 1, (C, cs)
+    elif kind == "onehot":
+        assert (s == 1.0).all(), (C, s)
+    _check_f64(x, C, 5)
+    assert _run.prepass == F64_PATHS[C]

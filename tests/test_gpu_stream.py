@@ -17,6 +17,7 @@ import ctcext_amd
 from ctcext_amd import _lib
 from parity_util import compare, oracle_or_error
 import oracle
+import range_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +27,9 @@ DEAD = _lib.CTCEXT_FLAG_TEST_HELPER_DEAD
 NP = {"f32": np.float32, "f64": np.float64}
 KINDS = {"normal": dict(merge_repeated=False, blank_index=0),
          "ties": dict(merge_repeated=True, blank_index=None)}   # (None: C // 2, a non-zero blank)
+# the whole float range (tests/range_inputs.py), test_family_chunked_numeric_range
+RANGE_KINDS = {"logsoftmax": dict(merge_repeated=True, blank_index=None),
+               "edges": dict(merge_repeated=False, blank_index=0)}
 M_LEAVES = "Less leaves in the beam search than requested."
 
 # id -> ((T, C, W, P), dtype, scorer, CTCEXT_HELPER or None, flags,
@@ -53,6 +57,8 @@ def _stat_row(k):
 
 
 def _inputs(rng, kind, T, B, C, dtype=np.float32):
+    if kind in RANGE_KINDS:
+        return range_inputs.family(rng, kind, T, B, C, dtype)
     x = rng.standard_normal((T, B, C))
     if kind == "ties":
         x = np.round(x * 2) / 2
@@ -62,7 +68,7 @@ def _inputs(rng, kind, T, B, C, dtype=np.float32):
 
 
 def _kw(kind, C):
-    kw = dict(KINDS[kind])
+    kw = dict(KINDS[kind] if kind in KINDS else RANGE_KINDS[kind])
     if kw["blank_index"] is None:
         kw["blank_index"] = C // 2
     return kw
@@ -97,12 +103,27 @@ def test_family_chunked_matches_oracle(name, kind, monkeypatch):
     """1. Every kernel family's stream build: pushes of 1, 1, 1, 1, 5 and the
     rest; after the 1st, 4th, 5th and last the result is the oracle's of the
     prefix, and the kernel that ran is the family's, as a stream build."""
+    _chunked_family(name, kind, monkeypatch)
+
+
+@pytest.mark.parametrize("kind", sorted(RANGE_KINDS))
+@pytest.mark.parametrize("name", ["sq_small", "sq_big", "f64", "gstate_f32"])
+def test_family_chunked_numeric_range(name, kind, monkeypatch):
+    """1, on log_softmax outputs and on terms at expf's / exp's underflow bound
+    and in the subnormal band: the state saved between pushes carries totals
+    of that range, and the last push's result is the one-shot decode's."""
+    _chunked_family(name, kind, monkeypatch)
+
+
+def _chunked_family(name, kind, monkeypatch):
     (T, C, W, P), dtype, scorer, env, flags, row = FAMILIES[name]
     _set_helper(monkeypatch, env)
     rng = np.random.default_rng(zlib.crc32(("%s/%s" % (name, kind)).encode()))
     B = 3
     x = _inputs(rng, kind, T, B, C, NP[dtype])
     sl = np.array([T, T - 3, T // 2], np.int32)
+    if kind in RANGE_KINDS:
+        range_inputs.assert_census(kind, np.concatenate([x[:n, b] for b, n in enumerate(sl)]))
     kw = _kw(kind, C)
     tab = (-np.abs(rng.standard_normal((C + 1, C))) * 2).astype(NP[dtype]) if scorer == "bigram" else None
     with ctcext_amd.StreamDecoder(B, C, W, P, T, dtype=NP[dtype], scorer_table=tab, flags=flags, **kw) as s:

@@ -6,10 +6,12 @@
 //
 //   hipcc -O2 -ffp-contract=off -std=c++17 tools/check_glibc_math.cpp -o /tmp/chk -lpthread
 //   /tmp/chk            # all three functions, all 2^32 inputs
-//   /tmp/chk sample     # every 97th input (CI-sized)
+//   /tmp/chk sample     # every 97th input (CI-sized; tests/test_cpu_glibc_math.py runs this form)
+//   /tmp/chk [sample] N # ... on N threads (default: the hardware's, 16 at most)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <atomic>
 #include <thread>
@@ -26,8 +28,12 @@ static bool same(float a, float b) {
 }
 
 int main(int argc, char** argv) {
-  const uint64_t stride = (argc > 1 && !strcmp(argv[1], "sample")) ? 97 : 1;
-  const int nthr = (int)std::thread::hardware_concurrency();
+  const bool sample = argc > 1 && !strcmp(argv[1], "sample");
+  const uint64_t stride = sample ? 97 : 1;
+  const char* thr_arg = argc > (sample ? 2 : 1) ? argv[sample ? 2 : 1] : nullptr;
+  int nthr = thr_arg ? atoi(thr_arg) : (int)std::thread::hardware_concurrency();
+  if (!thr_arg && nthr > 16) nthr = 16;
+  if (nthr < 1) nthr = 1;
   static uint64_t tab[32];
   for (int i = 0; i < 32; ++i) tab[i] = ctcx::gm::exp2f_tab(i);
   std::atomic<uint64_t> bad[4];

@@ -7,7 +7,8 @@
 //        near-1 polynomial range [1 - 2^-4, 1 + 2^-4], subnormals, random bits.
 //
 //   hipcc -O2 -ffp-contract=off -std=c++17 tools/check_glibc_math_f64.cpp -o /tmp/chk64 -lpthread
-//   /tmp/chk64 [samples_per_domain]      (default 20,000,000)
+//   /tmp/chk64 [samples_per_domain [threads]]      (default 20,000,000 samples; the hardware's threads, 16 at
+//                                                   most; tests/test_cpu_glibc_math.py runs 2,000,000)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -37,7 +38,9 @@ static double bits(uint64_t u) {
 
 int main(int argc, char** argv) {
   const uint64_t n = argc > 1 ? strtoull(argv[1], nullptr, 10) : 20000000ull;
-  const int nthr = (int)std::thread::hardware_concurrency();
+  int nthr = argc > 2 ? atoi(argv[2]) : (int)std::thread::hardware_concurrency();
+  if (argc <= 2 && nthr > 16) nthr = 16;
+  if (nthr < 1) nthr = 1;
   struct Dom { const char* name; int fn; };   // fn 0 = exp, 1 = log
   const Dom doms[] = {{"exp [-50,0]", 0}, {"exp [-750,0]", 0}, {"exp |x|<2^-50", 0}, {"exp [-1100,1100]", 0},
                       {"exp random bits", 0}, {"log [1,8192]", 1}, {"log near 1", 1}, {"log subnormal", 1},
