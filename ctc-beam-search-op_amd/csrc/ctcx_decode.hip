@@ -2803,6 +2803,125 @@ __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, i
   }
 }
 
+// The same chunk in two passes, for the chunks after the frame's first: those
+// are sparse (cfg3, T = 1500: ~6.5 scan steps of 64 offers per chunk of up to
+// 64), and gather_small_scored scores every scanned offer in full before it
+// knows which are wanted.  Pass 1 (per scan step) reads only what the want
+// test needs -- the branch's label, total and blank-ending total, the row
+// value and the branch child (sq_score's walk: it runs only where the branch
+// has children) -- applies the same brkM / kb / gstop, chunk-fills and resume
+// rules, and stages one packed word (sq_pack: branch, child + 1, label) per
+// wanted offer in the slot's value plane, as the large-C path stages its
+// entries; nothing reads the plane before the chunk is published.  Pass 2
+// (once per chunk) scores the staged offers, lane r the r-th, and writes the
+// slot: the same entries, fields and order as gather_small_scored gives for
+// the same bottom.  The score s is the same expression in both passes.
+template <typename T, bool CT = false>
+__device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, int nb, T norm, T bottom, int& i0,
+                                                    int& li0, bool& gstop, CTCX_LDS u32x4* qa, CTCX_LDS float* qp,
+                                                    int& cqn, const GQ& gq) {
+  const int lane = threadIdx.x & 63;
+  const int Cm1 = cx.C - 1, blank = cx.blank;
+  const float rcp = 1.0f / (float)Cm1;
+  CTCX_LDS uint32_t* sc = (CTCX_LDS uint32_t*)qp;
+  cqn = 0;
+  const int sp_i0 = i0;
+  const bool sp_mid = li0 != 0;
+  while (cqn < 64 && i0 < nb) {   // pass 1: filter
+    CTCX_HPC(cx, 31, 1);
+    const int x = li0 + lane;
+    int q = (int)((float)x * rcp);
+    q -= (q * Cm1 > x) ? 1 : 0;
+    q += ((q + 1) * Cm1 <= x) ? 1 : 0;
+    const int iv = i0 + q;
+    const bool v = iv < nb;
+    const int i = v ? iv : i0;
+    const int li = v ? x - q * Cm1 : 0;
+    const int l = li + (li >= blank ? 1 : 0);
+    const int bl = sel(cx.lab, buf)[i];
+    const T bt = sel(cx.ot, buf)[i];
+    const T bob = sel(cx.ob, buf)[i];
+    const T p = cx.row[l] - norm;
+    const T s = p + ((l == bl) ? bob : bt);
+    int cw = -1;
+    if constexpr (CT) {
+      if (v && ((gq.cmask[i] >> (l & 63)) & 1ull)) cw = gq.ctab[i * 64 + l];
+    } else
+    for (int k = v ? cx.head[i] : -1; __ballot(k >= 0);) {
+      CTCX_HPC(cx, 27, 1);
+      int nk = -1;
+      if (k >= 0) {
+        const int lk = sel(cx.lab, buf)[k];
+        const int sk = cx.sib[k];
+        if (lk == l) cw = k;
+        else nk = sk;
+      }
+      k = nk;
+    }
+    // a turn starting in this step (label index 0) and closed at this bottom
+    const uint64_t brkM = __ballot(v && li == 0 && !(bt > bottom));
+    const int kb = brkM ? (int)__builtin_ctzll(brkM) : 64;
+    const bool want = v && ((s > bottom) || cw >= 0) && lane < kb;
+    uint64_t wM = __ballot(want);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(wM >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wM, 0u));
+    const int room = 64 - cqn;
+    int adv;   // offers of the step passed over
+    if (__builtin_popcountll(wM) > room) {   // the chunk fills: resume after its last offer
+      wM = __ballot(want && rank < room);
+      adv = 64 - __builtin_clzll(wM);
+    } else {
+      adv = kb;
+      if (kb < 64) gstop = true;
+    }
+    if ((wM >> lane) & 1ull) sc[cqn + rank] = sq_pack(i, cw, l);
+    cqn += __builtin_popcountll(wM);
+    // (i0, li0) += adv offers
+    const int xa = li0 + adv;
+    int qa2 = (int)((float)xa * rcp);
+    qa2 -= (qa2 * Cm1 > xa) ? 1 : 0;
+    qa2 += ((qa2 + 1) * Cm1 <= xa) ? 1 : 0;
+    i0 += qa2;
+    li0 = xa - qa2 * Cm1;
+    if (gstop) break;
+  }
+  if (cqn == 0) return;
+  // pass 2: score.  The turn-start lane is the chunk position of the branch's
+  // first staged offer (the entries are in branch order), unless the branch
+  // began before the span.
+  wsync<true>();
+  const bool v = lane < cqn;
+  const uint32_t e = v ? sc[lane] : 0u;
+  const uint32_t ep = sc[(v && lane > 0) ? lane - 1 : 0];
+  const int i = (int)(e & 255u);
+  const int cw = (int)((e >> 8) & 511u) - 1;
+  const int l = sq_label_small(e);
+  const uint64_t fm = __ballot(v && (lane == 0 || (int)(ep & 255u) != i)) & lowmask(lane + 1);
+  const int tl = 63 - (int)__builtin_clzll(fm | 1ull);
+  const int bl = sel(cx.lab, buf)[i];
+  const int bflg = sel(cx.flg, buf)[i];
+  const T bt = sel(cx.ot, buf)[i];
+  const T bob = sel(cx.ob, buf)[i];
+  const T bcb = sel(cx.cb, buf)[i], bcn = sel(cx.cn, buf)[i];
+  const T p = cx.row[l] - norm;
+  const T s = p + ((l == bl) ? bob : bt);
+  const T NI = ninf<T>();
+  const bool recv_fresh = cw >= 0 ? (sel(cx.ot, buf)[cw] == NI) : true;
+  const T rs_blank = ((bflg & F_ROOT) && recv_fresh) ? T(0) : NI;
+  Best<T> cd{T(0), kBpNone, false};
+  cd.push(((bflg & F_HB) ? bcb : rs_blank) + p, (bflg & F_HB) ? (((uint32_t)i << 1) | 0u) : kBpRestart);
+  if (l != bl) cd.push(((bflg & F_HN) ? bcn : NI) + p, (bflg & F_HN) ? (((uint32_t)i << 1) | 1u) : kBpRestart);
+  wsync<true>();   // every lane has read its neighbour's staged word
+  if (v) {
+    u32x4 ev;
+    ev.x = __builtin_bit_cast(unsigned, (float)s);
+    ev.y = __builtin_bit_cast(unsigned, (float)bt);
+    ev.z = sq_pack_sl(i, cw, l, (sp_mid && i == sp_i0) ? -1 : tl);
+    ev.w = cd.bp;
+    qa[lane] = ev;
+    qp[lane] = (float)cd.p;
+  }
+}
+
 // The scored gather queue's helper (SQ kernels): as help_gather_chunks, up to
 // kSqLead chunks ahead of wave 0, each chunk's offers scored (sq_score).
 // small C: two ahead (cfg3 decode 124.9 -> 123.4 ms, same box); large C: one
@@ -2854,6 +2973,10 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
 #ifdef CTCX_SQ_NOFILTER   // (diagnostics: every offer gathered, no closed turn found here)
     bottom = ninf<T>();
 #endif
+    // (diagnostics, small C: the frame's first chunk in three spans -- to the
+    // control words read, the scan step, the publish: counters 16..18, which
+    // the scored kernels leave free)
+    [[maybe_unused]] const uint64_t hs1 = CTCX_HTIME();
     const int slot = c & q.sm;
     const int s_i0 = i0, s_l0 = li0;
     int cqn = 0;
@@ -2890,9 +3013,13 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
     } else {
       // the frame's first chunk: the first scan step's offers only, so wave 0
       // starts after one step instead of a full chunk (the helper gathers the
-      // next chunk meanwhile)
-      gather_small_scored<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, kSqFirst1 && c == 0, q);
+      // next chunk meanwhile).  Its offers are dense and wave 0 waits for it:
+      // scored as it is scanned.  The later chunks are sparse: filtered, then
+      // scored (gather_small_sparse).
+      if (kSqFirst1 && c == 0) gather_small_scored<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, true, q);
+      else gather_small_sparse<T, kCtab>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, q);
     }
+    [[maybe_unused]] const uint64_t hs2 = CTCX_HTIME();
     if (lane == 0) {
       q.h[slot * 4 + 0] = cqn;
       q.h[slot * 4 + 1] = s_i0;
@@ -2901,6 +3028,11 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
     }
     __hip_atomic_store(&m[kCtlReady], c + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (c == 0) CTCX_HPC(cx, 25, CTCX_HTIME() - hg0);
+    if (!BIG && c == 0) {
+      CTCX_HPC(cx, 16, hs1 - hg0);
+      CTCX_HPC(cx, 17, hs2 - hs1);
+      CTCX_HPC(cx, 18, CTCX_HTIME() - hs2);
+    }
     CTCX_HPC(cx, 30, 1);
     if (cqn == 0 || gstop) break;   // the last chunk of the frame
   }
@@ -4564,7 +4696,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
             if ((RN == 1 || RN == 2) && W >= 2) heap_sentinels(he, W, RN == 2 ? 256 : 128);   // the mask-form sift's geometry
             st = kTopHeap;
 #ifdef CTCX_FASTLOOP_PROF
-            if (pc) pc[14] += __builtin_amdgcn_s_memtime() - q4;
+            if (pc) pc[23] += __builtin_amdgcn_s_memtime() - q4;   // (make_heap: 14 is the first-chunk wait)
 #endif
           } else if (n == W) {
             return 2;   // filled mid-frame: the lazy peek is replayed literally

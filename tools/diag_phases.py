@@ -3,7 +3,12 @@
 Needs the counters build (the product library compiles them out):
   make -C ctc-beam-search-op_amd/csrc phases
   CTCEXT_LIB_PATH=$PWD/tools/libctcext_phases.so python tools/diag_phases.py B T W P [C]
-(add -DCTCX_FASTLOOP_PROF to the phases build for the per-event split)."""
+(add -DCTCX_FASTLOOP_PROF to the phases build for the per-event split; that
+build alone times make_heap, in counter 23).
+
+Counter 14 is wave 0's wait for the frame's first chunk (a part of the queue
+wait, counter 19), printed once.  In the small-C scored kernels the gather
+counters 16..18 are the helper's first chunk in three spans."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ctc-beam-search-op_amd"))
 import numpy as np
@@ -25,14 +30,17 @@ if rc != 0:
 m = buf.astype(np.float64).mean(0)
 fr = m[7]
 names = ["rowload", "recursion", "grow", "extract", "commit", "literal", "heap events", "frames",
-         "scoring", "eventloop", "score:pre-skip", "chunks", "asm calls", "asm loop", "makeheap", "flush",
+         "scoring", "eventloop", "score:pre-skip", "chunks", "asm calls", "asm loop", "first-chunk wait", "flush",
          "gather (C>64)", "gather: window steps | C<=64: child-walk steps", "gather: windows | C<=64: child walk",
          "gather: top set",
          "gather: branch select", "gather: branches", "gather: S branches", "gather: select+S test+S hot"]
 CYC = {0, 1, 2, 3, 4, 5, 8, 9, 10, 13, 14, 15, 16, 18, 19, 20, 23}
 print("B=%d T=%d W=%d P=%d C=%d decode_ms=%.1f" % (B, T, W, P, C, d.last_stats["decode_kernel_ms"]))
+sq_small = C <= 64 and m[30] > 0   # the small-C scored helper ran: 16..18 are its first-chunk spans
+if os.environ.get("CTCX_DIAG_FASTLOOP"):   # (a build with -DCTCX_FASTLOOP_PROF)
+    names[23] = "makeheap"
 for k in range(24):
-    if k == 7:
+    if k == 7 or (sq_small and k in (16, 17, 18)):
         continue
     print("  %-10s %12.0f %s/frame" % (names[k], m[k] / fr, "cycles" if k in CYC else "count"))
 if m[6] > 0:
@@ -48,8 +56,8 @@ for b in o[-3:][::-1]:
 print("  mean heap events/frame %.1f, max %.1f" % (buf[:, 6].mean() / fr, buf[:, 6].max() / fr))
 # two-wave kernels (cfg2/cfg3 class): the score-table wait and where the waves ran
 if True:
-    print("  HW table / queue wait %.0f cycles/frame, %.2f s_sleep rounds/frame (first chunk: %.0f cycles)"
-          % (m[19] / fr, m[20] / fr, m[14] / fr))
+    print("  HW table / queue wait %.0f cycles/frame, %.2f s_sleep rounds/frame (after the first chunk: %.0f cycles)"
+          % (m[19] / fr, m[20] / fr, (m[19] - m[14]) / fr))
     w0, w1 = buf[:, 21].astype(np.int64), buf[:, 22].astype(np.int64)
     simd0, simd1 = (w0 >> 4) & 3, (w1 >> 4) & 3
     cu0, cu1 = (w0 >> 8) & 15, (w1 >> 8) & 15
@@ -64,6 +72,12 @@ for k, name in hn.items():
     print("  %-26s %10.0f cycles/frame" % (name, m[k] / fr))
 print("  helper chunks %.2f/frame, scan steps %.2f/frame, child-walk steps %.2f/frame"
       % (m[30] / fr, m[31] / fr, m[27] / fr))
+if m[31] > 0:
+    busy = m[24] - m[26]
+    print("  helper busy (gather minus waits for wave 0) %.0f cycles/frame, %.0f per scan step" % (busy / fr, busy / m[31]))
+if sq_small:
+    print("  helper first chunk: entry to control words read %.0f, scan step %.0f, publish %.0f cycles/frame"
+          % (m[16] / fr, m[17] / fr, m[18] / fr))
 if os.environ.get("CTCX_DIAG_EXTP"):   # (a build with -DCTCX_PHASE_EXTP: the extract's stop)
     h = buf[:, 27].astype(np.uint64)
     cnt = [int(((h >> np.uint64(16 * k)) & np.uint64(0xFFFF)).sum()) for k in range(4)]
