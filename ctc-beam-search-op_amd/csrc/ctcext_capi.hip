@@ -20,6 +20,7 @@
 #include "../../include/ctcext.h"
 #define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
+#include "ctcx_stable.h"
 
 namespace ctcx {
 template <typename T>
@@ -1204,7 +1205,10 @@ struct ctcext_stream {
   void* gstate = nullptr;
   void* sctab = nullptr;
   void* cum = nullptr;       // [B] int32: frames per item including the running push (the traceback's lengths)
+  void* stable_cache = nullptr;   // [B] CtcxStableCache: the frontier of each item's last ctcext_stream_stable answer
   DevBuf x, xw, sl, norm, prep;
+  DevBuf stable_out, stable_flags;   // ctcext_stream_stable: its outputs; position flags of beams past its LDS variant
+  HostBuf h_stable;                  // ... and the outputs' pinned landing buffer (one copy per query)
   std::vector<int64_t> frames;
 };
 
@@ -1269,11 +1273,12 @@ extern "C" int ctcext_stream_validate_chunk(const ctcext_stream_args* a, const c
 }
 
 static void stream_free(ctcext_stream* st) {
-  void* ps[] = {st->state[0], st->state[1], st->rec, st->gstate, st->sctab, st->cum};
+  void* ps[] = {st->state[0], st->state[1], st->rec, st->gstate, st->sctab, st->cum, st->stable_cache};
   for (void* p : ps)
     if (p) (void)hipFree(p);
-  DevBuf* bufs[] = {&st->x, &st->xw, &st->sl, &st->norm, &st->prep};
+  DevBuf* bufs[] = {&st->x, &st->xw, &st->sl, &st->norm, &st->prep, &st->stable_out, &st->stable_flags};
   for (DevBuf* b : bufs) b->release();
+  st->h_stable.release();
   delete st;
 }
 
@@ -1341,6 +1346,8 @@ static int stream_open_t(ctcext_stream* st) {
   }
   HIP_OR_FAIL(hipMalloc(&st->rec, (size_t)st->rec_bytes * (size_t)(B * F * W) + 256));
   HIP_OR_FAIL(hipMalloc(&st->cum, 4 * (size_t)B + 256));
+  HIP_OR_FAIL(hipMalloc(&st->stable_cache, sizeof(CtcxStableCache) * (size_t)B + 256));
+  HIP_OR_FAIL(hipMemsetAsync(st->stable_cache, 0, sizeof(CtcxStableCache) * (size_t)B + 256, s));
   HIP_OR_FAIL(hipStreamSynchronize(s));
   st->frames.assign((size_t)B, 0);
   return CTCEXT_OK;
@@ -1404,6 +1411,8 @@ extern "C" int ctcext_stream_reset(ctcext_stream* st, const int32_t* items, int6
   for (int64_t i = 0; i < cnt; ++i) {
     const int64_t b = items ? items[i] : i;
     HIP_OR_FAIL(hipMemsetAsync((char*)st->state[st->cur] + (size_t)b * (size_t)st->stride, 0, sizeof(CtcxStreamHdr), s));
+    // ... and its stable-prefix frontier goes with the utterance
+    HIP_OR_FAIL(hipMemsetAsync((CtcxStableCache*)st->stable_cache + b, 0, sizeof(CtcxStableCache), s));
   }
   HIP_OR_FAIL(hipStreamSynchronize(s));
   for (int64_t i = 0; i < cnt; ++i) st->frames[(size_t)(items ? items[i] : i)] = 0;
@@ -1638,6 +1647,126 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
   d->T = a.max_frames; d->C = a.num_classes; d->W = a.beam_width; d->P = P;
   root.s = s;
   for (int p = 0; p < P; ++p) sizes[p] = d->sizes[p];
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The stable prefix of a stream (ctcext.h, "Streaming: the stable prefix"):
+// ctcx_stable.hip's kernel over the committed state headers, the records and
+// the per-item frontier cache; and the naive host walk the tests hold it to.
+
+extern "C" int ctcext_stream_stable(ctcext_stream* st, int32_t* decoded_length, int64_t* stable_frames,
+                                    int64_t* walked) {
+  if (!st || !decoded_length || !stable_frames) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size;
+  if (B == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  Dev& root = st->dec->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.own_stream;
+  // outputs: stable_frames [B] int64 | walked [B] int64 | decoded_length [B] int32
+  HIP_OR_FAIL(st->stable_out.ensure(20 * (size_t)B + 16));
+  HIP_OR_FAIL(st->h_stable.ensure(20 * (size_t)B + 16));
+  CtcxStableParams p{};
+  p.state = (const char*)st->state[st->cur];
+  p.stride = st->stride;
+  p.rec = st->rec;
+  p.Tmax = a.max_frames; p.B = B;
+  p.W = a.beam_width; p.rec_fmt = st->rec_fmt; p.merge = a.merge_repeated ? 1 : 0;
+  p.cache = (CtcxStableCache*)st->stable_cache;
+  p.stable_frames = (int64_t*)st->stable_out.p;
+  p.walked = p.stable_frames + B;
+  p.decoded_length = (int32_t*)(p.walked + B);
+  if (!ctcx_stable_in_lds(p.W, p.rec_fmt)) {
+    HIP_OR_FAIL(st->stable_flags.ensure(2 * (size_t)B * (size_t)p.W + 16));
+    p.flags = (uint8_t*)st->stable_flags.p;
+  }
+  HIP_OR_FAIL(ctcx_launch_stable(p, s));
+  HIP_OR_FAIL(hipMemcpyAsync(st->h_stable.p, st->stable_out.p, 20 * (size_t)B, hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  const int64_t* h = (const int64_t*)st->h_stable.p;
+  memcpy(stable_frames, h, 8 * (size_t)B);
+  if (walked) memcpy(walked, h + B, 8 * (size_t)B);
+  memcpy(decoded_length, h + 2 * B, 4 * (size_t)B);
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_stable_reference(ctcext_stream* st, int32_t* decoded_length, int64_t* stable_frames) {
+  if (!st || !decoded_length || !stable_frames) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size, F = a.max_frames;
+  const int W = a.beam_width;
+  if (B == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  Dev& root = st->dec->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.own_stream;
+  const int fmt = st->rec_fmt;
+  const size_t rw = (size_t)st->rec_bytes / 4;
+  std::vector<uint32_t> rec;
+  std::vector<int> pos;
+  for (int64_t b = 0; b < B; ++b) {
+    CtcxStreamHdr hdr;
+    HIP_OR_FAIL(hipMemcpyAsync(&hdr, (const char*)st->state[st->cur] + (size_t)b * (size_t)st->stride, sizeof(hdr),
+                               hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipStreamSynchronize(s));
+    decoded_length[b] = 0;
+    stable_frames[b] = 0;
+    const int64_t n = hdr.frames, m = hdr.nb;
+    if (n <= 0 || m <= 0) continue;
+    if (n > F || m > W) return fail(CTCEXT_INTERNAL, "stream header outside the stream's shape");
+    rec.resize((size_t)n * (size_t)W * rw);
+    HIP_OR_FAIL(hipMemcpyAsync(rec.data(), (const char*)st->rec + (size_t)b * (size_t)F * (size_t)W * rw * 4,
+                               rec.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OR_FAIL(hipStreamSynchronize(s));
+    auto at = [&](int64_t t, int k, uint32_t& link, int& lab) {
+      ctcx::rec_link_label(rec.data() + ((size_t)t * (size_t)W + (size_t)k) * rw, fmt, link, lab);
+    };
+    // every live chain to frame 0; the newest frame that holds them all on one position
+    pos.resize((size_t)m);
+    for (int64_t i = 0; i < m; ++i) pos[(size_t)i] = (int)i;
+    int64_t f = -1;
+    int ks = 0;
+    for (int64_t t = n - 1; t >= 0; --t) {
+      bool one = true;
+      for (int64_t i = 1; i < m; ++i) one = one && pos[(size_t)i] == pos[0];
+      if (one && f < 0) {
+        f = t;
+        ks = pos[0];
+      }
+      for (int64_t i = 0; i < m; ++i) {
+        uint32_t link;
+        int lab;
+        at(t, pos[(size_t)i], link, lab);
+        if ((link >> 1) >= (uint32_t)W) return fail(CTCEXT_INTERNAL, "record link outside the beam");
+        pos[(size_t)i] = (int)(link >> 1);
+      }
+    }
+    if (f < 0) continue;
+    // the decoded walk from (f, ks) to frame 0
+    int len = 0, prev = -1, k = ks;
+    for (int64_t t = f; t >= 0; --t) {
+      uint32_t link;
+      int lab;
+      at(t, k, link, lab);
+      if (link & 1u) {
+        if (!a.merge_repeated || lab != prev) ++len;
+        prev = lab;
+      }
+      k = (int)(link >> 1);
+    }
+    decoded_length[b] = len;
+    stable_frames[b] = f + 1;
+  }
   g_err.clear();
   return CTCEXT_OK;
 }

@@ -47,6 +47,9 @@ CTCEXT_KERNEL_STREAM = 0x8000   # ctcext_stats.kernel: a stream build of the dec
 DENSE_SYMBOLS = ("ctcext_dense_validate", "ctcext_dense_reserve", "ctcext_decode_dense", "ctcext_dense_check",
                  "ctcext_dense_pack_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + DENSE_SYMBOLS
+# the stable prefix of a stream (CTCEXT_HAS_STREAM_STABLE)
+STREAM_STABLE_SYMBOLS = ("ctcext_stream_stable", "ctcext_stream_stable_reference")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_STABLE_SYMBOLS
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
 CTCEXT_ITEM_FEW_LEAVES = 2       # fewer leaves than top_paths
@@ -208,6 +211,14 @@ def load():
         lib.ctcext_stream_reset.restype = ctypes.c_int
         lib.ctcext_stream_close.argtypes = [ctypes.c_void_p]
         lib.ctcext_stream_close.restype = None
+    if hasattr(lib, "ctcext_stream_stable"):   # (CTCEXT_HAS_STREAM_STABLE; older builds stay loadable for A/B runs)
+        # (stream, int32 decoded_length[B], int64 stable_frames[B], int64 walked[B] or NULL)
+        lib.ctcext_stream_stable.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+        lib.ctcext_stream_stable.restype = ctypes.c_int
+        lib.ctcext_stream_stable_reference.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                                       ctypes.POINTER(ctypes.c_int64)]
+        lib.ctcext_stream_stable_reference.restype = ctypes.c_int
     if hasattr(lib, "ctcext_decode_dense"):   # (CTCEXT_HAS_DENSE; older builds stay loadable for A/B runs)
         lib.ctcext_dense_validate.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.POINTER(DenseOutputs)]
         lib.ctcext_dense_validate.restype = ctypes.c_int

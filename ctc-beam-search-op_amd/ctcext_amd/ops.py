@@ -596,6 +596,9 @@ def _host_empty():
     return np.empty
 
 
+StablePrefix = collections.namedtuple("StablePrefix", ["decoded_length", "frames"])
+
+
 class StreamDecoder:
     """Streaming decode: push the logits of a batch in chunks of frames and
     read, after each push, the hypotheses of everything pushed so far --
@@ -604,6 +607,7 @@ class StreamDecoder:
         s = StreamDecoder(batch_size, num_classes, beam_width, top_paths, max_frames)
         for chunk in chunks:              # [B, t, C] each (batch_first), t may vary
             out = s.push(chunk, lengths)  # lengths: frames of this chunk per item (None: all t)
+            fin = s.stable()              # fin.decoded_length[b] leading labels of item b are final
         s.reset([1])                      # item 1 starts a new utterance; the others go on
         s.close()                         # or use it as a context manager
 
@@ -719,6 +723,43 @@ class StreamDecoder:
         if rc != _lib.CTCEXT_OK:
             _raise(self.lib, rc)
 
+    # -- the stable prefix ---------------------------------------------------
+    def stable(self, walked=False):
+        """How much of the decoded output is final: ``StablePrefix(decoded_length,
+        frames)``, numpy int32 / int64 ``[batch_size]``.  The first
+        ``decoded_length[b]`` labels of item b's decoded row are the same in
+        every path of this push and of every later push, until the item is
+        reset; ``frames[b]`` is the frame frontier behind them (all live beam
+        entries share their history up to frame ``frames[b] - 1``).  Neither
+        decreases between resets.  The alignment outputs get no such
+        guarantee.  With ``walked=True`` also returns, as a second value, the
+        record frames the query's convergence walk visited per item (int64)."""
+        self._check_open()
+        B = int(self._args.batch_size)
+        n = np.zeros((B,), np.int32)
+        f = np.zeros((B,), np.int64)
+        w = np.zeros((B,), np.int64)
+        if self.handle:   # (a stream before its first push: zeros)
+            rc = self.lib.ctcext_stream_stable(self.handle, _ptr(n, ctypes.c_int32), _ptr(f, ctypes.c_int64),
+                                               _ptr(w, ctypes.c_int64) if walked else None)
+            if rc != _lib.CTCEXT_OK:
+                _raise(self.lib, rc)
+        res = StablePrefix(n, f)
+        return (res, w) if walked else res
+
+    def _stable_reference(self):
+        """Tests: ``stable()``'s two numbers by the naive host walk over a
+        copy of the records (every live chain to frame 0, no cache)."""
+        self._check_open()
+        B = int(self._args.batch_size)
+        n = np.zeros((B,), np.int32)
+        f = np.zeros((B,), np.int64)
+        if self.handle:
+            rc = self.lib.ctcext_stream_stable_reference(self.handle, _ptr(n, ctypes.c_int32), _ptr(f, ctypes.c_int64))
+            if rc != _lib.CTCEXT_OK:
+                _raise(self.lib, rc)
+        return StablePrefix(n, f)
+
     # -- push ---------------------------------------------------------------
     def push(self, chunk, lengths=None, *, batch_first=True, results=True, outputs="auto", flags=0):
         """Decode ``chunk`` (``[B, t, C]`` with ``batch_first``, else ``[t, B, C]``)
@@ -818,6 +859,10 @@ class StreamDecoder:
                              outputs == "device" or (outputs == "auto" and on_device))
         _print_no_label(dec.last_stats["no_label_paths"])
         return out
+
+
+def _ptr(arr, ctype):
+    return arr.ctypes.data_as(ctypes.POINTER(ctype))
 
 
 def _device_index(device):

@@ -370,6 +370,48 @@ int ctcext_stream_reset(ctcext_stream* s, const int32_t* items, int64_t n);
 void ctcext_stream_close(ctcext_stream* s);
 
 /* ---------------------------------------------------------------------------
+ * Streaming: the stable prefix.  How much of a stream's decoded output is
+ * final: a front end emits those labels once and redraws only the tail.  New
+ * entry points only (CTCEXT_ABI_VERSION is unchanged; detect them by
+ * CTCEXT_HAS_STREAM_STABLE at build time or by symbol at run time).
+ *
+ * Definition.  Item b has n = frames[b] frames pushed.  Its live set is the
+ * beam records of frame n - 1 at positions 0..m-1, m being the beam size after
+ * that frame (the records the last committed push wrote for it).  Every record
+ * names its source position in the frame before (link >> 1); follow that from
+ * every live position one frame back at a time.
+ *   stable_frames[b]  = f + 1, where f is the newest frame at which all chains
+ *                       sit on one position k*; 0 when the chains never meet,
+ *                       and when n == 0.
+ *   decoded_length[b] = the number of labels the decoded walk (the one that
+ *                       fills decoded_values) emits on the single chain from
+ *                       record (f, k*) down to frame 0, the merge_repeated
+ *                       rule applied as it is there.
+ * Every hypothesis a later push can return descends from a live entry, so the
+ * first decoded_length[b] elements of item b's decoded row are identical in
+ * every path of this push and of every later push, until the item is reset;
+ * and neither number decreases between resets.
+ *
+ * The ALIGNMENT outputs get no such guarantee.  An alignment candidate chain
+ * can restart at any frame (ctc_beam_entry.h:204-213), and the 4-byte record
+ * of the two-wave kernels folds "restarted" and "absent" into one code, so
+ * the live alignment states cannot be enumerated from the records; the query
+ * leaves them out instead of approximating them.
+ *
+ * The stream keeps, per item, the frontier of its last answer; a query walks
+ * only the frames above it, a push does not touch it, and ctcext_stream_reset
+ * clears it for the items it names. */
+#define CTCEXT_HAS_STREAM_STABLE 1
+/* Host arrays of [batch]; walked may be NULL.  Synchronous, on the decoder's own stream.
+ * walked[b]: record frames the convergence walk visited in this call.
+ * Null s or a null required pointer: CTCEXT_INVALID_ARGUMENT, "null argument".
+ * A stream with no push yet answers zeros. */
+int ctcext_stream_stable(ctcext_stream* s, int32_t* decoded_length, int64_t* stable_frames, int64_t* walked);
+/* Diagnostics (tests): the same two numbers computed on the host from a copy of the item
+ * records, by the naive method -- every live chain walked to frame 0, no cache, no early stop. */
+int ctcext_stream_stable_reference(ctcext_stream* s, int32_t* decoded_length, int64_t* stable_frames);
+
+/* ---------------------------------------------------------------------------
  * Dense, enqueue-only decode.  The outputs are padded device tensors of
  * static shape instead of SparseTensor components whose sizes depend on the
  * data, and every check that needs data runs on the device, so the call only

@@ -11,7 +11,21 @@ row is one push: the stream build of the kernel (no record ring, image saved
 once) against the default one; the one-shot call is timed with and without
 its record ring, since a stream writes every record.
 
-    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--out FILE]
+With --stable every multi-push row is run a second time with
+StreamDecoder.stable() after every push (the query's time inside the push's),
+in the same session, and the row records the frames its convergence walks
+visited in total (walked, summed over items and pushes).  --input chooses the
+logits: "gaussian", the bench's, whose chains may never meet (the worst case:
+a query walks back to its last frontier, which stays at frame 0 while they do
+not); "peaky": the same noise with 8.0 added to one class per (t, b) row, the
+blank with probability 0.7 and a uniformly drawn label otherwise (a confident
+model: every frame's winner has probability ~0.985); or "twohot": every class
+near -40 but two per row, one at 0 and one at -0.5, so that each frame is a
+near-even choice between two continuations and the beam's entries are the
+variants of the last few frames.  A library without the query (an older build
+through CTCEXT_LIB_PATH) prints the other rows only.
+
+    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--input gaussian|peaky|twohot] [--out FILE]
 
 Prints one table and one JSON line.  It is a report, not a check, and it does
 not touch bench.py.
@@ -48,17 +62,48 @@ def one_shot(x, sl, flags=0):
     return ctcext_amd.decode_logits(x, sl, W, P, batch_first=False, outputs="device", flags=flags, **KW)
 
 
-def streamed(x, chunk):
+def streamed(x, chunk, stable=False, info=None):
     with ctcext_amd.StreamDecoder(B, C, W, P, T, **KW) as s:
         s.push(x[:0], batch_first=False, results=False)   # opens the stream: its allocations are not timed
         ms = 0.0
         out = None
+        walked = 0
+        last = None
+
+        def step(t0, t1):
+            nonlocal walked, last
+            o = s.push(x[t0:t1], batch_first=False, results=t1 == T, outputs="device")
+            if stable:
+                last, w = s.stable(walked=True)
+                walked += int(w.sum())
+            return o
         for t0 in range(0, T, chunk):
             t1 = min(t0 + chunk, T)
-            dt, out = _timed(lambda: s.push(x[t0:t1], batch_first=False, results=t1 == T, outputs="device"))
+            dt, out = _timed(lambda: step(t0, t1))
             ms += dt
         kernel = s.last_stats["kernel"]
+        if info is not None and stable:
+            info["walked"] = walked
+            info["decoded_length_mean"] = float(last.decoded_length.mean())
+            info["stable_frames_mean"] = float(last.frames.mean())
     return ms, out, kernel
+
+
+def make_input(kind):
+    rng = np.random.default_rng(20251015)
+    x = rng.standard_normal((T, B, C), dtype=np.float32)
+    if kind == "peaky":
+        cls = np.where(rng.random((T, B)) < 0.7, KW["blank_index"], rng.integers(1, C, size=(T, B)))
+        np.put_along_axis(x, cls[..., None], np.take_along_axis(x, cls[..., None], 2) + 8.0, 2)
+    elif kind == "twohot":
+        x -= 40.0
+        c0 = rng.integers(0, C, size=(T, B))
+        c1 = (c0 + rng.integers(1, C, size=(T, B))) % C
+        np.put_along_axis(x, c0[..., None], 0.0, 2)
+        np.put_along_axis(x, c1[..., None], -0.5, 2)
+    elif kind != "gaussian":
+        raise SystemExit("--input must be gaussian, peaky or twohot")
+    return torch.as_tensor(x, device="cuda:0")
 
 
 def _same(a, b):
@@ -73,11 +118,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--chunks", default="1500,100,10")
+    ap.add_argument("--stable", action="store_true", help="also run each multi-push row with stable() after every push")
+    ap.add_argument("--input", default="gaussian", help="gaussian (the bench's logits), peaky or twohot")
     ap.add_argument("--out", default=None, help="also write the table and the JSON line here")
     args = ap.parse_args()
     chunks = [int(c) for c in args.chunks.split(",")]
-    rng = np.random.default_rng(20251015)
-    x = torch.as_tensor(rng.standard_normal((T, B, C), dtype=np.float32), device="cuda:0")
+    x = make_input(args.input)
+    with_stable = args.stable and hasattr(_lib.load(), "ctcext_stream_stable")
     sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
     ref = one_shot(x, sl)   # warm-up: workspace, kernels
     rows = {}
@@ -85,24 +132,37 @@ def main():
     rows["one-shot, no ring"] = [_timed(lambda: one_shot(x, sl, _lib.CTCEXT_FLAG_NO_RING))[0]
                                  for _ in range(args.runs)]
     kernel = None
+    stable_info = {}
     for c in chunks:
         ms, out, kernel = streamed(x, c)   # warm-up
         if not _same(out, ref):
             raise SystemExit("chunk size %d: the streamed result differs from the one-shot one" % c)
         rows["stream, %d-frame pushes" % c] = [streamed(x, c)[0] for _ in range(args.runs)]
+        if with_stable and c < T:
+            # (alternating with the plain row would be fairer still; the two lists are taken back to back)
+            name = "stream, %d-frame pushes + stable()" % c
+            streamed(x, c, True)   # warm-up
+            stable_info[name] = {}
+            rows[name] = [streamed(x, c, True, stable_info[name])[0] for _ in range(args.runs)]
     base = statistics.median(rows["one-shot"])
-    lines = ["%-28s %9s %9s %9s %8s %10s" % ("B=256 T=1500 C=29 W=128 P=3", "median ms", "min", "max", "vs 1-shot",
-                                              "per push")]
-    res = {"shape": [B, T, C, W, P], "runs": args.runs, "stream_kernel": kernel, "rows": {}}
+    lines = ["%-40s %9s %9s %9s %8s %10s %9s" % ("B=256 T=1500 C=29 W=128 P=3, %s" % args.input, "median ms", "min", "max",
+                                                  "vs 1-shot", "per push", "walked")]
+    res = {"shape": [B, T, C, W, P], "input": args.input, "runs": args.runs, "stream_kernel": kernel, "rows": {}}
     for name, v in rows.items():
         med = statistics.median(v)
         n = 1
         if name.startswith("stream"):
             n = -(-T // int(name.split()[1].split("-")[0]))
         per = "" if n == 1 else "%+.3f ms" % ((med - base) / n)
-        lines.append("%-28s %9.2f %9.2f %9.2f %7.1f%% %10s" % (name, med, min(v), max(v), 100 * (med / base - 1), per))
+        info = stable_info.get(name, {})
+        lines.append("%-40s %9.2f %9.2f %9.2f %7.1f%% %10s %9s" % (name, med, min(v), max(v), 100 * (med / base - 1), per,
+                                                                  info.get("walked", "")))
         res["rows"][name] = {"median_ms": round(med, 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3),
                              "pushes": n}
+        res["rows"][name].update(info)
+        if info:   # what the query costs per push: against the same pushes without it
+            plain = statistics.median(rows[name.replace(" + stable()", "")])
+            res["rows"][name]["query_ms_per_push"] = round((med - plain) / n, 4)
     text = "\n".join(lines) + "\n" + json.dumps(res)
     print(text)
     if args.out:
