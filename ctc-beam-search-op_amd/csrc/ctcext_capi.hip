@@ -21,6 +21,7 @@
 #define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
 #include "ctcx_stable.h"
+#include "ctcx_stream_dense.h"
 
 namespace ctcx {
 template <typename T>
@@ -1210,6 +1211,23 @@ struct ctcext_stream {
   DevBuf stable_out, stable_flags;   // ctcext_stream_stable: its outputs; position flags of beams past its LDS variant
   HostBuf h_stable;                  // ... and the outputs' pinned landing buffer (one copy per query)
   std::vector<int64_t> frames;
+  // The enqueue-only push (ctcext_stream_push_dense): every buffer it touches
+  // is the stream's own, none the decoder's, so that two streams of one
+  // decoder can have pushes in flight at once.  It shares norm, prep, xw and
+  // stable_flags above with the synchronous entry points, which wait first.
+  struct {
+    bool used = false;         // a push has been enqueued: the host's frames may be behind (stream_settle)
+    hipStream_t s = nullptr;   // the HIP stream of the last one
+    int kernel = 0;            // ctcext_stats.kernel of the last one
+    int32_t flags = 0;         // its chunk flags
+    bool results = false;      // it had hypothesis outputs
+    double commit_ms = 0;
+    hipEvent_t ev[5] = {};     // CTCEXT_FLAG_PROFILE: around prologue + pre-pass, decode, commit, the rest
+    DevBuf item, top_pos, top_kind, logp, seq, len;
+    DevBuf sl, pre, fin, acc, walked;   // [B] each: sanitised lengths, status before / after the decode,
+                                        // the deferred record (CtcxStreamAcc), stable's walked
+    HostBuf land;              // the check's landing buffer: frames | acc | ItemOut | top_kind
+  } dn;
 };
 
 // The stream's attributes as the one-shot argument struct, for the shared
@@ -1279,7 +1297,43 @@ static void stream_free(ctcext_stream* st) {
   DevBuf* bufs[] = {&st->x, &st->xw, &st->sl, &st->norm, &st->prep, &st->stable_out, &st->stable_flags};
   for (DevBuf* b : bufs) b->release();
   st->h_stable.release();
+  DevBuf* dbufs[] = {&st->dn.item, &st->dn.top_pos, &st->dn.top_kind, &st->dn.logp, &st->dn.seq, &st->dn.len,
+                     &st->dn.sl, &st->dn.pre, &st->dn.fin, &st->dn.acc, &st->dn.walked};
+  for (DevBuf* b : dbufs) b->release();
+  st->dn.land.release();
+  for (auto& ev : st->dn.ev)
+    if (ev) (void)hipEventDestroy(ev);
   delete st;
+}
+
+// Landing layout of an enqueue-only stream's check (dn.land): the committed
+// frames [B] int32, the deferred record [B], the items' counters [B], and the
+// last push's top_kind [B][P].
+static size_t land_acc_off(int64_t B) { return (4 * (size_t)B + 15) & ~(size_t)15; }
+static size_t land_item_off(int64_t B) { return land_acc_off(B) + sizeof(CtcxStreamAcc) * (size_t)B; }
+static size_t land_kind_off(int64_t B) { return land_item_off(B) + sizeof(ctcx::ItemOut) * (size_t)B; }
+
+// Waits for the enqueue-only pushes of st (if it ever had one: a captured push
+// may have been replayed since) and brings the committed frames down into the
+// host mirror.  The deferred status stays on the device for ctcext_stream_check.
+static int stream_settle(ctcext_stream* st) {
+  if (!st->dn.used) return CTCEXT_OK;
+  const int64_t B = st->a.batch_size;
+  if (B == 0) return CTCEXT_OK;
+  const int P = st->a.top_paths;
+  char* h = (char*)st->dn.land.p;
+  hipStream_t s = st->dn.s;
+  // (CtcxStreamHdr.frames, the header's first word, of every item: right whichever form of push wrote it last)
+  HIP_OR_FAIL(hipMemcpy2DAsync(h, 4, st->state[st->cur], (size_t)st->stride, 4, (size_t)B, hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipMemcpyAsync(h + land_acc_off(B), st->dn.acc.p, sizeof(CtcxStreamAcc) * (size_t)B,
+                             hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipMemcpyAsync(h + land_item_off(B), st->dn.item.p, sizeof(ctcx::ItemOut) * (size_t)B,
+                             hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipMemcpyAsync(h + land_kind_off(B), st->dn.top_kind.p, 4 * (size_t)(B * P), hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  const int32_t* fr = (const int32_t*)h;
+  for (int64_t b = 0; b < B; ++b) st->frames[(size_t)b] = fr[b];
+  return CTCEXT_OK;
 }
 
 // The DecodeParams of a push (or, with no chunk yet, of the kernel query at open).
@@ -1385,11 +1439,18 @@ extern "C" void ctcext_stream_close(ctcext_stream* st) {
   Dev& root = st->dec->devs[0];
   (void)hipSetDevice(root.device);
   if (root.own_stream) (void)hipStreamSynchronize(root.own_stream);
+  if (st->dn.used) (void)hipStreamSynchronize(st->dn.s);   // enqueue-only pushes still in flight
   stream_free(st);
 }
 
 extern "C" int ctcext_stream_frames(ctcext_stream* st, int64_t* frames) {
   if (!st || !frames) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (st->dn.used) {   // enqueue-only pushes: the counts live on the device until waited for
+    DeviceGuard guard;
+    HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+    const int rc = stream_settle(st);
+    if (rc != CTCEXT_OK) return rc;
+  }
   for (size_t b = 0; b < st->frames.size(); ++b) frames[b] = st->frames[b];
   return CTCEXT_OK;
 }
@@ -1406,6 +1467,10 @@ extern "C" int ctcext_stream_reset(ctcext_stream* st, const int32_t* items, int6
   Dev& root = st->dec->devs[0];
   HIP_OR_FAIL(hipSetDevice(root.device));
   hipStream_t s = root.own_stream;
+  {
+    const int rc = stream_settle(st);
+    if (rc != CTCEXT_OK) return rc;
+  }
   // frames = 0 in the committed header: the item's next push runs Reset()
   const int64_t cnt = items ? n : B;
   for (int64_t i = 0; i < cnt; ++i) {
@@ -1601,6 +1666,8 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
   Dev& root = d->devs[0];
   HIP_OR_FAIL(hipSetDevice(root.device));
   hipStream_t s = c->stream ? (hipStream_t)c->stream : root.own_stream;
+  rc = stream_settle(st);
+  if (rc != CTCEXT_OK) return rc;
   // the chunk's lengths are read on the host, as ctcext_decode reads sequence_length
   std::vector<int32_t> hcl((size_t)B, (int32_t)c->chunk_time);
   if (B > 0 && c->chunk_length) {
@@ -1669,6 +1736,10 @@ extern "C" int ctcext_stream_stable(ctcext_stream* st, int32_t* decoded_length, 
   Dev& root = st->dec->devs[0];
   HIP_OR_FAIL(hipSetDevice(root.device));
   hipStream_t s = root.own_stream;
+  {
+    const int rc = stream_settle(st);
+    if (rc != CTCEXT_OK) return rc;
+  }
   // outputs: stable_frames [B] int64 | walked [B] int64 | decoded_length [B] int32
   HIP_OR_FAIL(st->stable_out.ensure(20 * (size_t)B + 16));
   HIP_OR_FAIL(st->h_stable.ensure(20 * (size_t)B + 16));
@@ -1710,6 +1781,10 @@ extern "C" int ctcext_stream_stable_reference(ctcext_stream* st, int32_t* decode
   Dev& root = st->dec->devs[0];
   HIP_OR_FAIL(hipSetDevice(root.device));
   hipStream_t s = root.own_stream;
+  {
+    const int rc = stream_settle(st);
+    if (rc != CTCEXT_OK) return rc;
+  }
   const int fmt = st->rec_fmt;
   const size_t rw = (size_t)st->rec_bytes / 4;
   std::vector<uint32_t> rec;
@@ -1768,5 +1843,336 @@ extern "C" int ctcext_stream_stable_reference(ctcext_stream* st, int32_t* decode
     stable_frames[b] = f + 1;
   }
   g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Streaming: enqueue-only push (ctcext.h, "Streaming: enqueue-only push").
+// ctcx_stream_dense.hip's prologue takes the decisions ctcext_stream_push takes
+// on the host from the chunk's lengths; the decode reads state[cur] and writes
+// state[cur ^ 1] as there; ctcx_stream_commit copies every item whose
+// hand-over held back over state[cur], so cur never changes in this path and
+// a push is the same chain of launches over the same addresses every time.
+
+// What needs no data, on the host: a is a validated stream's attributes.
+static int check_push_dense(const ctcext_stream_args* a, const ctcext_chunk* c, const ctcext_stream_dense_outputs* o) {
+  if (!a || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!a->on_device) return fail(CTCEXT_INVALID_ARGUMENT, "ctcext_stream_push_dense needs device chunks");
+  if (c->flags & ~(CTCEXT_FLAG_TEST_HELPER_DEAD | CTCEXT_FLAG_PROFILE | CTCEXT_FLAG_DENSE_NULL_STREAM))
+    return fail(CTCEXT_INVALID_ARGUMENT,
+                "chunk flags: CTCEXT_FLAG_TEST_HELPER_DEAD, _PROFILE and _DENSE_NULL_STREAM only");
+  const int rc = check_chunk(a, c, nullptr);
+  if (rc != CTCEXT_OK) return rc;
+  if (o && a->batch_size > 0) {
+    const void* hyp[] = {o->decoded, o->decoded_length, o->alignment, o->alignment_length, o->log_probability};
+    int nh = 0;
+    for (const void* q : hyp) nh += q ? 1 : 0;
+    if (!o->status || (nh != 0 && nh != 5) || (!o->stable_length) != (!o->stable_frames))
+      return fail(CTCEXT_INVALID_ARGUMENT, "null dense output pointer");
+    if (nh == 5 && (((uintptr_t)o->decoded | (uintptr_t)o->alignment) & 7))
+      return fail(CTCEXT_INVALID_ARGUMENT, "dense outputs decoded and alignment need 8-byte alignment");
+  }
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_dense_validate(const ctcext_stream_args* a, const ctcext_chunk* c,
+                                            const ctcext_stream_dense_outputs* o) {
+  int rc = ctcext_stream_validate(a);
+  if (rc == CTCEXT_OK) rc = check_push_dense(a, c, o);
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+// Grows the stream's own workspace to what a push of Tc frames touches
+// (grow-only: nothing is allocated or freed when it already fits).
+static int stream_dense_ensure(ctcext_stream* st, int64_t Tc) {
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size, C = a.num_classes, F = a.max_frames;
+  const int W = a.beam_width, P = a.top_paths;
+  const size_t ts = a.dtype == CTCEXT_F64 ? 8 : 4;
+  auto& n = st->dn;
+  HIP_OR_FAIL(n.item.ensure(sizeof(ctcx::ItemOut) * (size_t)B));
+  HIP_OR_FAIL(n.top_pos.ensure(4 * (size_t)(B * P)));
+  HIP_OR_FAIL(n.top_kind.ensure(4 * (size_t)(B * P)));
+  HIP_OR_FAIL(n.logp.ensure(ts * (size_t)(B * P)));
+  HIP_OR_FAIL(n.seq.ensure(4 * (size_t)(B * P * 2 * F) + 16));
+  HIP_OR_FAIL(n.len.ensure(4 * (size_t)(B * P * 2)));
+  HIP_OR_FAIL(n.sl.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(n.pre.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(n.fin.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(n.walked.ensure(8 * (size_t)B));
+  HIP_OR_FAIL(n.land.ensure(land_kind_off(B) + 4 * (size_t)(B * P) + 16));
+  if (!n.acc.p) {   // (sized by the batch alone: allocated once, and empty from then on until a push writes it)
+    HIP_OR_FAIL(n.acc.ensure(sizeof(CtcxStreamAcc) * (size_t)B));
+    HIP_OR_FAIL(hipMemset(n.acc.p, 0, sizeof(CtcxStreamAcc) * (size_t)B));
+  }
+  if (!ctcx_stable_in_lds(W, st->rec_fmt)) HIP_OR_FAIL(st->stable_flags.ensure(2 * (size_t)B * (size_t)W + 16));
+  if (!n.ev[0])
+    for (auto& ev : n.ev) HIP_OR_FAIL(hipEventCreate(&ev));
+  if (Tc > 0) {
+    HIP_OR_FAIL(st->norm.ensure(ts * (size_t)(Tc * B)));
+    // (half chunks of a float stream on the global-state tier are widened into workspace first)
+    if (st->gs && ts == 4) HIP_OR_FAIL(st->xw.ensure(4 * (size_t)(Tc * B * C) + 16));
+    if (!st->gs && C > 64) HIP_OR_FAIL(st->prep.ensure(ctcx::prep_row_bytes(C, (int)ts) * (size_t)(Tc * B)));
+  }
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_reserve(ctcext_stream* st, int64_t max_chunk_time) {
+  if (!st) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!st->a.on_device) return fail(CTCEXT_INVALID_ARGUMENT, "ctcext_stream_push_dense needs device chunks");
+  if (max_chunk_time < 0) return fail(CTCEXT_INVALID_ARGUMENT, "inputs has a negative dimension");
+  if (st->a.batch_size == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  const int rc = stream_dense_ensure(st, max_chunk_time);
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+template <typename T>
+static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const int32_t* reset,
+                               const ctcext_stream_dense_outputs* o, hipStream_t s) {
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size, C = a.num_classes, F = a.max_frames, Tc = c->chunk_time;
+  const int W = a.beam_width, P = a.top_paths;
+  const int ts = (int)sizeof(T);
+  const bool prof = (c->flags & CTCEXT_FLAG_PROFILE) != 0;
+  const bool results = o && o->decoded;
+  auto& n = st->dn;
+  int* note = ctcx_launch_note();
+  note[0] = note[1] = note[2] = 0;
+
+  // the chunk's element strides, as stream_push_t takes them
+  int xfmt = c->inputs_format;
+  int64_t st_t = c->inputs_stride_t ? c->inputs_stride_t : B * C;
+  int64_t st_b = c->inputs_stride_b ? c->inputs_stride_b : C;
+  if (Tc <= 1 && B <= 1) st_t = st_b = C;
+  else if (Tc <= 1) st_t = st_b * B;
+  else if (B <= 1) st_b = st_t * Tc;
+  const void* x = c->inputs;
+  const int32_t* const sl = (const int32_t*)n.sl.p;
+  char* const committed = (char*)st->state[st->cur];
+  char* const other = (char*)st->state[st->cur ^ 1];
+
+  if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[0], s));
+  CtcxStreamPrologueParams pp{};
+  pp.chunk_length = c->chunk_length;
+  pp.reset = reset;
+  pp.state = committed;
+  pp.stride = st->stride;
+  pp.cache = (CtcxStableCache*)st->stable_cache;
+  pp.sl = (int32_t*)n.sl.p;
+  pp.cum = (int32_t*)st->cum;
+  pp.pre = (int32_t*)n.pre.p;
+  pp.acc = (CtcxStreamAcc*)n.acc.p;
+  pp.chunk_time = Tc; pp.max_frames = F; pp.B = B;
+  HIP_OR_FAIL(ctcx_launch_stream_prologue(pp, s));
+  if (Tc > 0) {   // the pre-pass over the chunk's rows, on the sanitised lengths
+    if (st->gs && xfmt != CTCEXT_IN_NATIVE) {
+      HIP_OR_FAIL(ctcx::launch_widen_rows(x, xfmt, (float*)st->xw.p, Tc, B, C, st_t, st_b, s));
+      x = st->xw.p;
+      xfmt = CTCEXT_IN_NATIVE;
+      st_t = B * C;
+      st_b = C;
+    }
+    if (!st->gs && C > 64)
+      HIP_OR_FAIL(ctcx::launch_row_prep<T>(x, xfmt, sl, (char*)st->prep.p, (T*)st->norm.p, Tc, B, C, st_t, st_b,
+                                           a.blank_index, s));
+    else
+      HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, xfmt, sl, (T*)st->norm.p, Tc, B, C, st_t, st_b, s));
+  }
+  if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[1], s));
+
+  ctcx::DecodeParams<T> p = stream_decode_params<T>(st);
+  p.x = (const T*)x;
+  p.xfmt = xfmt;
+  p.norm = (const T*)st->norm.p;
+  p.seq_len = sl;
+  p.xst_t = st_t; p.xst_b = st_b;
+  p.item = (ctcx::ItemOut*)n.item.p;
+  p.top_pos = (int32_t*)n.top_pos.p;
+  p.top_kind = (int32_t*)n.top_kind.p;
+  p.log_prob = (T*)n.logp.p;
+  p.prep = (const char*)st->prep.p;
+  p.test_flags = (c->flags & CTCEXT_FLAG_TEST_HELPER_DEAD) ? ctcx::kTestHelperDead : 0;
+  CtcxStreamParams sp{};
+  sp.in = committed;
+  sp.out = other;
+  sp.stride = st->stride;
+  sp.image_bytes = st->image_bytes;
+  if (st->gs) HIP_OR_FAIL(ctcx_gstate_stream_launch_decode(&p, &sp, ts == 8, st->scored, s));
+  else HIP_OR_FAIL(ctcx_stream_launch_decode(&p, &sp, ts == 8, s));
+  if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[2], s));
+
+  CtcxStreamCommitParams cp{};
+  cp.committed = committed;
+  cp.written = other;
+  cp.stride = st->stride;
+  cp.copy_bytes = (int64_t)((ctcx_stream_hdr_bytes(P) + (size_t)st->image_bytes + 15) & ~(size_t)15);
+  cp.item = p.item; cp.top_pos = p.top_pos; cp.top_kind = p.top_kind; cp.log_prob = n.logp.p;
+  cp.pre = pp.pre; cp.cum = pp.cum; cp.acc = pp.acc;
+  cp.status_ws = (int32_t*)n.fin.p;
+  cp.status = o ? o->status : nullptr;
+  cp.frames = o ? o->frames : nullptr;
+  cp.B = B; cp.P = P; cp.f64 = ts == 8;
+  cp.few_leaves = results ? 1 : 0;
+  HIP_OR_FAIL(ctcx_launch_stream_commit(cp, s));
+  if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[3], s));
+
+  if (o && o->stable_length) {   // ctcext_stream_stable's launch, over the state just committed, into the caller's buffers
+    CtcxStableParams q{};
+    q.state = committed;
+    q.stride = st->stride;
+    q.rec = st->rec;
+    q.Tmax = F; q.B = B;
+    q.W = W; q.rec_fmt = st->rec_fmt; q.merge = a.merge_repeated ? 1 : 0;
+    q.cache = (CtcxStableCache*)st->stable_cache;
+    q.stable_frames = o->stable_frames;
+    q.walked = (int64_t*)n.walked.p;
+    q.decoded_length = o->stable_length;
+    if (!ctcx_stable_in_lds(W, q.rec_fmt)) q.flags = (uint8_t*)st->stable_flags.p;
+    HIP_OR_FAIL(ctcx_launch_stable(q, s));
+  }
+  if (results) {
+    // the walks of every frame so far, from the records the stream keeps, then ctcx_pack_dense with rows of max_frames
+    ctcx::TraceParams tp{};
+    tp.rec = p.rec; tp.item = p.item; tp.seq_len = (const int32_t*)st->cum; tp.top_pos = p.top_pos;
+    tp.top_kind = p.top_kind;
+    tp.Tmax = F; tp.B = B; tp.W = W; tp.P = P; tp.merge = a.merge_repeated ? 1 : 0;
+    tp.blank_label = a.blank_label;
+    tp.rec_fmt = st->rec_fmt;
+    tp.foff = nullptr;
+    tp.seq = (int32_t*)n.seq.p;
+    tp.len = (int32_t*)n.len.p;
+    tp.len_stride = B;
+    HIP_OR_FAIL(ctcx::launch_traceback(tp, s));
+    ctcx::PackDenseParams pd{};
+    pd.seq = tp.seq;
+    pd.len = tp.len;
+    pd.item = p.item;
+    pd.pre = pp.pre;
+    pd.log_prob = n.logp.p;
+    pd.Tmax = F; pd.B = B; pd.P = P; pd.f64 = ts == 8;
+    pd.pad_value = o->pad_value;
+    pd.decoded = o->decoded; pd.alignment = o->alignment;
+    pd.decoded_length = o->decoded_length; pd.alignment_length = o->alignment_length;
+    pd.out_log_prob = o->log_probability;
+    pd.status = o->status;
+    pd.status_ws = (int32_t*)n.fin.p;
+    HIP_OR_FAIL(ctcx::launch_pack_dense(pd, s));
+  }
+  if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[4], s));
+  n.kernel = note[0] | (note[1] << 12) | (note[2] << 16);
+  n.results = results;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_push_dense(ctcext_stream* st, const ctcext_chunk* c, const int32_t* reset,
+                                        const ctcext_stream_dense_outputs* o) {
+  if (!st || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ctcext_stream_args& a = st->a;
+  int rc = check_push_dense(&a, c, o);
+  if (rc != CTCEXT_OK) return rc;
+  if (a.batch_size == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  Dev& root = st->dec->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  // (the null stream itself with the flag: dense_begin)
+  hipStream_t s = c->stream ? (hipStream_t)c->stream
+                  : (c->flags & CTCEXT_FLAG_DENSE_NULL_STREAM) ? (hipStream_t) nullptr : root.own_stream;
+  rc = stream_dense_ensure(st, c->chunk_time);   // (nothing to grow after a reserve or a push of this size)
+  if (rc != CTCEXT_OK) return rc;
+  rc = a.dtype == CTCEXT_F32 ? stream_push_dense_t<float>(st, c, reset, o, s)
+                             : stream_push_dense_t<double>(st, c, reset, o, s);
+  // (whatever was enqueued before a failing launch is waited for like a whole push)
+  st->dn.used = true;
+  st->dn.s = s;
+  st->dn.flags = c->flags;
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+extern "C" int ctcext_stream_check(ctcext_stream* st) {
+  if (!st) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  auto& n = st->dn;
+  const ctcext_stream_args& a = st->a;
+  const int64_t B = a.batch_size;
+  const int P = a.top_paths;
+  if (!n.used || B == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  int rc = stream_settle(st);
+  if (rc != CTCEXT_OK) return rc;
+  const char* h = (const char*)n.land.p;
+  const CtcxStreamAcc* acc = (const CtcxStreamAcc*)(h + land_acc_off(B));
+  const ctcx::ItemOut* io = (const ctcx::ItemOut*)(h + land_item_off(B));
+  const int32_t* kinds = (const int32_t*)(h + land_kind_off(B));
+
+  ctcext_stats sv{};
+  sv.tier = st->gs ? 1 : 0;
+  sv.record_bytes = st->rec_bytes;
+  sv.helper = st->helper;
+  sv.kernel = n.kernel;
+  n.commit_ms = 0;
+  if (n.flags & CTCEXT_FLAG_PROFILE) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, n.ev[0], n.ev[1]) == hipSuccess) sv.norm_kernel_ms = ms;
+    if (hipEventElapsedTime(&ms, n.ev[1], n.ev[2]) == hipSuccess) sv.decode_kernel_ms = ms;
+    if (hipEventElapsedTime(&ms, n.ev[2], n.ev[3]) == hipSuccess) n.commit_ms = ms;
+    if (hipEventElapsedTime(&ms, n.ev[3], n.ev[4]) == hipSuccess) sv.traceback_ms = ms;
+    (void)hipGetLastError();
+  }
+  int32_t any = 0;
+  int64_t first_len = -1, first_cap = -1;
+  for (int64_t b = 0; b < B; ++b) {   // (the counters travel in the item's header: cumulative)
+    sv.literal_frames += io[b].literal_steps;
+    sv.literal_nonfinite += io[b].why_nonfinite;
+    sv.literal_fill += io[b].why_fill;
+    sv.duplicate_frames += io[b].dup_frames;
+    sv.records_written += io[b].records;
+    any |= acc[b].status;
+    if ((acc[b].status & CTCEXT_ITEM_LENGTH) && first_len < 0) first_len = b;
+    if ((acc[b].status & CTCEXT_ITEM_CAPACITY) && first_cap < 0) first_cap = b;
+  }
+  st->dec->stats = sv;
+  if (!any) {
+    if (n.results)
+      for (int64_t q = 0; q < B * P; ++q) st->dec->stats.no_label_paths += (kinds[q] < 0) ? 1 : 0;
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  // the messages are built before the record is cleared (its landing copy stays)
+  const int64_t len_chunk = first_len >= 0 ? acc[first_len].len_chunk : 0;
+  const int32_t cap_total = first_cap >= 0 ? acc[first_cap].cap_total : 0;
+  HIP_OR_FAIL(hipMemsetAsync(n.acc.p, 0, sizeof(CtcxStreamAcc) * (size_t)B, n.s));
+  HIP_OR_FAIL(hipStreamSynchronize(n.s));
+  // the synchronous push's own order: the lengths, the capacity, the hand-over, the leaves
+  if (first_len >= 0)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "sequence_length(" + std::to_string(first_len) + ") <= " + std::to_string(len_chunk));
+  if (first_cap >= 0)
+    return fail(CTCEXT_INVALID_ARGUMENT, "stream capacity exceeded: item " + std::to_string(first_cap) +
+                                             " would hold " + std::to_string(cap_total) + " frames of max_frames " +
+                                             std::to_string(a.max_frames));
+  if (any & CTCEXT_ITEM_HELPER_TIMEOUT)
+    return fail(CTCEXT_INTERNAL, "decode kernel: a helper-wave hand-over wait timed out");
+  return fail(CTCEXT_INVALID_ARGUMENT, "Less leaves in the beam search than requested.");
+}
+
+extern "C" int ctcext_stream_commit_ms(ctcext_stream* st, double* ms) {
+  if (!st || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!st->dn.used || !(st->dn.flags & CTCEXT_FLAG_PROFILE))
+    return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE enqueue-only push checked yet");
+  *ms = st->dn.commit_ms;
   return CTCEXT_OK;
 }

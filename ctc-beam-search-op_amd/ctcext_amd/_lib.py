@@ -50,6 +50,11 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + DENSE_SYMBOLS
 # the stable prefix of a stream (CTCEXT_HAS_STREAM_STABLE)
 STREAM_STABLE_SYMBOLS = ("ctcext_stream_stable", "ctcext_stream_stable_reference")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_STABLE_SYMBOLS
+# the enqueue-only push of a stream (CTCEXT_HAS_STREAM_DENSE)
+STREAM_DENSE_SYMBOLS = ("ctcext_stream_dense_validate", "ctcext_stream_reserve", "ctcext_stream_push_dense",
+                        "ctcext_stream_check", "ctcext_stream_commit_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_DENSE_SYMBOLS
+CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
 CTCEXT_ITEM_FEW_LEAVES = 2       # fewer leaves than top_paths
@@ -99,6 +104,16 @@ class DenseOutputs(ctypes.Structure):
     _fields_ = [("decoded", ctypes.c_void_p), ("decoded_length", ctypes.c_void_p),
                 ("alignment", ctypes.c_void_p), ("alignment_length", ctypes.c_void_p),
                 ("log_probability", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("pad_value", ctypes.c_int64)]
+
+
+class StreamDenseOutputs(ctypes.Structure):
+    """ctcext_stream_dense_outputs: the padded device outputs of ctcext_stream_push_dense."""
+    _fields_ = [("decoded", ctypes.c_void_p), ("decoded_length", ctypes.c_void_p),
+                ("alignment", ctypes.c_void_p), ("alignment_length", ctypes.c_void_p),
+                ("log_probability", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("frames", ctypes.c_void_p),
+                ("stable_length", ctypes.c_void_p), ("stable_frames", ctypes.c_void_p),
                 ("pad_value", ctypes.c_int64)]
 
 
@@ -230,6 +245,20 @@ def load():
         lib.ctcext_dense_check.restype = ctypes.c_int
         lib.ctcext_dense_pack_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_pack_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_stream_push_dense"):   # (CTCEXT_HAS_STREAM_DENSE; older builds stay loadable for A/B runs)
+        lib.ctcext_stream_dense_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(Chunk),
+                                                     ctypes.POINTER(StreamDenseOutputs)]
+        lib.ctcext_stream_dense_validate.restype = ctypes.c_int
+        lib.ctcext_stream_reserve.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        lib.ctcext_stream_reserve.restype = ctypes.c_int
+        # (stream, chunk, int32 reset[B] on the device or NULL, outputs or NULL)
+        lib.ctcext_stream_push_dense.argtypes = [ctypes.c_void_p, ctypes.POINTER(Chunk), ctypes.c_void_p,
+                                                 ctypes.POINTER(StreamDenseOutputs)]
+        lib.ctcext_stream_push_dense.restype = ctypes.c_int
+        lib.ctcext_stream_check.argtypes = [ctypes.c_void_p]
+        lib.ctcext_stream_check.restype = ctypes.c_int
+        lib.ctcext_stream_commit_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_stream_commit_ms.restype = ctypes.c_int
     _lib = lib
     return lib
 

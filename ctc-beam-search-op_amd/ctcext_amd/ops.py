@@ -597,6 +597,10 @@ def _host_empty():
 
 
 StablePrefix = collections.namedtuple("StablePrefix", ["decoded_length", "frames"])
+StreamDense = collections.namedtuple(
+    "StreamDense",
+    ["decoded", "decoded_lengths", "alignment", "alignment_lengths", "log_probability", "status", "frames",
+     "stable_length", "stable_frames"])
 
 
 class StreamDecoder:
@@ -772,6 +776,37 @@ class StreamDecoder:
             raise ValueError("outputs must be 'auto', 'host' or 'device'")
         lib = self.lib
         a = self._args
+        c, x, sl, on_device, dev, index = self._chunk(chunk, lengths, batch_first, flags)
+        if not self.handle:
+            # host-side checks of the first chunk before the stream opens
+            a.on_device = 1 if on_device else 0
+            rc = lib.ctcext_stream_validate_chunk(ctypes.byref(a), ctypes.byref(c))
+            if rc != _lib.CTCEXT_OK:
+                _raise(lib, rc)
+            self._open(on_device, index)
+        dec = self.dec
+        if on_device and not c.stream:
+            import torch
+            torch.cuda.current_stream(dev).synchronize()   # (see _decode_and_fetch)
+        P = int(a.top_paths)
+        sizes = (_lib.PathSizes * max(P, 1))() if results else None
+        rc = lib.ctcext_stream_push(self.handle, ctypes.byref(c), sizes)
+        self.last_stats = dec.last_stats = dec.stats()
+        if rc != _lib.CTCEXT_OK:
+            _raise(lib, rc)
+        del x, sl
+        if not results:
+            return None
+        szs = [(s.num_decoded, s.max_decoded, s.num_alignment, s.max_alignment) for s in sizes]
+        out = _fetch_outputs(dec, szs, int(a.batch_size), P, a.dtype,
+                             outputs == "device" or (outputs == "auto" and on_device))
+        _print_no_label(dec.last_stats["no_label_paths"])
+        return out
+
+    def _chunk(self, chunk, lengths, batch_first, flags):
+        """The ``ctcext_chunk`` of one push: ``(c, x, sl, on_device, dev, index)``,
+        x and sl being the tensors or arrays c points into."""
+        a = self._args
         allowed = "float16, bfloat16, float32" if a.dtype == _lib.CTCEXT_F32 else "float64"
         if _is_torch(chunk):
             import torch
@@ -834,31 +869,123 @@ class StreamDecoder:
             raise FailedPreconditionError("len(sequence_length) != batch_size.  len(sequence_length):  %d batch_size: %d"
                                           % (sl.shape[0] if len(sl.shape) else 0, a.batch_size),
                                           _lib.CTCEXT_FAILED_PRECONDITION)
+        return c, x, sl, on_device, dev, index
+
+    # -- the enqueue-only push -----------------------------------------------
+    def push_dense(self, chunk, lengths=None, *, reset=None, batch_first=True, results=True, stable=False,
+                   pad_value=-1, flags=0):
+        """``push`` without waiting for anything: the chunk is decoded on
+        ``torch.cuda.current_stream()`` behind whatever produced it, and the
+        call returns padded CUDA tensors of static shape.  No ``synchronize()``,
+        no ``.item()``, no ``.cpu()``; after ``reserve(t)`` (or one push of that
+        size) it can be captured into a ``torch.cuda.graph`` and replayed once
+        per chunk with new data in the same tensors.
+
+        ``chunk`` is a CUDA tensor; ``lengths`` and ``reset`` should be int32
+        CUDA tensors of ``[B]`` (other forms are converted on the device).
+        ``reset[b] != 0`` starts a new utterance in item b with this chunk: the
+        continuous-batching slot swap without a host round trip.
+
+        Returns ``StreamDense(decoded, decoded_lengths, alignment,
+        alignment_lengths, log_probability, status, frames, stable_length,
+        stable_frames)``.  The first five are ``decode_dense``'s with rows
+        ``max_frames`` wide, the hypotheses of everything pushed so far, and
+        None with ``results=False`` (no traceback, no pack).  ``status`` int32
+        ``[B]`` holds this push's ``CTCEXT_ITEM_*`` bits (0: good) and
+        ``frames`` int32 ``[B]`` the frames per item after it.
+        ``stable_length`` int32 / ``stable_frames`` int64 ``[B]`` are
+        ``stable()``'s two numbers after this push, None without ``stable=True``.
+
+        Errors that depend on the data are deferred: a length above the chunk's
+        frames (``CTCEXT_ITEM_LENGTH``) or past ``max_frames``
+        (``CTCEXT_ITEM_CAPACITY``) and a helper hand-over timeout leave that item
+        as it was before the push, with empty rows; the other items advance.
+        ``check()`` waits and raises what ``push`` would have raised.
+
+        Successive pushes are ordered by the torch stream they are made on;
+        pushes of one ``StreamDecoder`` made on different streams are the
+        caller's to order."""
+        self._check_open()
+        if not (_is_torch(chunk) and chunk.is_cuda):
+            raise ValueError("push_dense takes CUDA torch tensors; use push for host chunks")
+        import torch
+        lib = self.lib
+        a = self._args
+        c, x, sl, on_device, dev, index = self._chunk(chunk, lengths, batch_first, flags)
+        B, P, F = int(a.batch_size), int(a.top_paths), int(a.max_frames)
+        rs = None
+        if reset is not None:
+            rs = _lengths_device(reset, dev)
+            if tuple(rs.shape) != (B,):
+                raise ValueError("reset must have shape [batch_size] = [%d], got %s" % (B, tuple(rs.shape)))
+        if not c.stream:   # torch's legacy default stream: the null stream itself, not the decoder's own
+            c.flags |= _lib.CTCEXT_FLAG_DENSE_NULL_STREAM
         if not self.handle:
-            # host-side checks of the first chunk before the stream opens
-            a.on_device = 1 if on_device else 0
-            rc = lib.ctcext_stream_validate_chunk(ctypes.byref(a), ctypes.byref(c))
+            a.on_device = 1
+            rc = lib.ctcext_stream_dense_validate(ctypes.byref(a), ctypes.byref(c), None)
             if rc != _lib.CTCEXT_OK:
                 _raise(lib, rc)
-            self._open(on_device, index)
-        dec = self.dec
-        if on_device and not c.stream:
-            import torch
-            torch.cuda.current_stream(dev).synchronize()   # (see _decode_and_fetch)
-        P = int(a.top_paths)
-        sizes = (_lib.PathSizes * max(P, 1))() if results else None
-        rc = lib.ctcext_stream_push(self.handle, ctypes.byref(c), sizes)
-        self.last_stats = dec.last_stats = dec.stats()
+            self._open(True, index)
+        fdt = torch.float32 if a.dtype == _lib.CTCEXT_F32 else torch.float64
+        with torch.cuda.device(dev):
+            def empty(shape, dt):
+                return torch.empty(shape, dtype=dt, device=dev)
+            hyp = ([empty((B, P, F), torch.int64), empty((B, P), torch.int32), empty((B, P, F), torch.int64),
+                    empty((B, P), torch.int32), empty((B, P), fdt)] if results else [None] * 5)
+            status, frames = empty((B,), torch.int32), empty((B,), torch.int32)
+            st = [empty((B,), torch.int32), empty((B,), torch.int64)] if stable else [None, None]
+        out = StreamDense(*(hyp + [status, frames] + st))
+        o = _lib.StreamDenseOutputs()
+        (o.decoded, o.decoded_length, o.alignment, o.alignment_length, o.log_probability, o.status, o.frames,
+         o.stable_length, o.stable_frames) = [None if t is None else t.data_ptr() for t in out]
+        o.pad_value = int(pad_value)
+        rc = lib.ctcext_stream_push_dense(self.handle, ctypes.byref(c), None if rs is None else rs.data_ptr(),
+                                          ctypes.byref(o))
         if rc != _lib.CTCEXT_OK:
             _raise(lib, rc)
-        del x, sl
-        if not results:
-            return None
-        szs = [(s.num_decoded, s.max_decoded, s.num_alignment, s.max_alignment) for s in sizes]
-        out = _fetch_outputs(dec, szs, int(a.batch_size), P, a.dtype,
-                             outputs == "device" or (outputs == "auto" and on_device))
-        _print_no_label(dec.last_stats["no_label_paths"])
+        # x, sl and rs may be temporaries: they were allocated on this stream, and
+        # the caching allocator hands their memory out again in stream order
+        del x, sl, rs
         return out
+
+    def reserve(self, max_chunk_time):
+        """Size the stream's workspace for ``push_dense`` of chunks of up to
+        ``max_chunk_time`` frames (may allocate and block; launches nothing).
+        Opens the stream for CUDA chunks if no push has yet."""
+        self._check_open()
+        if not self.handle:
+            self._open(True, self._device if self._device is not None else _current_device())
+        rc = self.lib.ctcext_stream_reserve(self.handle, int(max_chunk_time))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+
+    def check(self):
+        """Wait for the ``push_dense`` calls made so far and report them as
+        ``push`` would have: raises the same ``OpError`` subclass with the same
+        message for the first of -- a length above its chunk's frames (lowest
+        item), the stream's capacity exceeded (lowest item), a helper hand-over
+        timeout, "Less leaves in the beam search than requested." -- over all
+        pushes since the previous ``check()``, which it then forgets.  Returns
+        the stats dict (cumulative counters, as after ``push``)."""
+        self._check_open()
+        if not self.handle:
+            return self.last_stats
+        rc = self.lib.ctcext_stream_check(self.handle)
+        self.last_stats = self.dec.last_stats = self.dec.stats()
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        _print_no_label(self.last_stats["no_label_paths"])
+        return self.last_stats
+
+    def commit_ms(self):
+        """Diagnostics: the commit kernel's time in ms of the last ``push_dense``
+        made with ``flags=CTCEXT_FLAG_PROFILE``, after its ``check()``."""
+        self._check_open()
+        ms = ctypes.c_double()
+        rc = self.lib.ctcext_stream_commit_ms(self.handle, ctypes.byref(ms))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        return ms.value
 
 
 def _ptr(arr, ctype):

@@ -492,6 +492,103 @@ int ctcext_dense_check(ctcext_decoder* dec);
  * kernels' times are in ctcext_stats).  0 for a call replayed from a graph. */
 int ctcext_dense_pack_ms(ctcext_decoder* dec, double* ms);
 
+/* ---------------------------------------------------------------------------
+ * Streaming: enqueue-only push.  ctcext_stream_push in the manner of
+ * ctcext_decode_dense: the push enqueues onto one HIP stream and returns, its
+ * outputs are padded device tensors of static shape, and every decision that
+ * needs data (the chunk's lengths, the stream's capacity, whether an item's
+ * hand-over held, a slot's reset) is taken on the device.  A push is a fixed
+ * chain of launches over fixed addresses, so it can be captured into a HIP
+ * graph and replayed once per chunk.  The hypotheses after each push are, bit
+ * for bit, ctcext_decode's of everything pushed so far for that item.
+ * New entry points and structs only (CTCEXT_ABI_VERSION is unchanged; detect
+ * them by CTCEXT_HAS_STREAM_DENSE at build time or by symbol at run time).
+ *
+ * Every buffer such a push touches belongs to the ctcext_stream, none to the
+ * decoder: two streams of one decoder may have pushes in flight at once.
+ * Successive pushes of one stream object are ordered by the HIP stream they
+ * are enqueued on; pushes of one stream object enqueued on different HIP
+ * streams are the caller's to order (events).  The synchronous entry points
+ * (ctcext_stream_push, _frames, _reset, _stable, _stable_reference) first wait
+ * for the enqueue-only pushes of that stream object and refresh the host's
+ * frame counts, without clearing the deferred status, so the two forms can be
+ * mixed -- except that a captured push must not be replayed after a
+ * synchronous push (which swaps the stream's two state buffers). */
+#define CTCEXT_HAS_STREAM_DENSE 1
+
+/* One more status[b] bit: the chunk would take the item past max_frames. */
+enum { CTCEXT_ITEM_CAPACITY = 16 };
+
+/* Device pointers, all of them.  The five hypothesis pointers as in
+ * ctcext_dense_outputs with rows max_frames wide (8-byte alignment only); all
+ * five NULL: no traceback and no pack, status / frames / stable_* only. */
+typedef struct {
+  int64_t* decoded;           /* [batch][top_paths][max_frames], label order, padded */
+  int32_t* decoded_length;    /* [batch][top_paths] */
+  int64_t* alignment;         /* [batch][top_paths][max_frames] */
+  int32_t* alignment_length;  /* [batch][top_paths] */
+  void*    log_probability;   /* [batch][top_paths] of dtype */
+  int32_t* status;            /* [batch] CTCEXT_ITEM_* bits of THIS push, 0 = good */
+  int32_t* frames;            /* [batch] frames per item after this push (may be NULL) */
+  int32_t* stable_length;     /* [batch] } both or neither: ctcext_stream_stable's decoded_length */
+  int64_t* stable_frames;     /* [batch] } and stable_frames, after this push */
+  int64_t  pad_value;         /* written past each row's length */
+} ctcext_stream_dense_outputs;
+
+/* Host only, no HIP call: ctcext_stream_validate, then (CTCEXT_INVALID_ARGUMENT)
+ *   "ctcext_stream_push_dense needs device chunks"      (on_device == 0)
+ *   "chunk flags: CTCEXT_FLAG_TEST_HELPER_DEAD, _PROFILE and _DENSE_NULL_STREAM only"
+ * the chunk checks of ctcext_stream_validate_chunk that need no data, and for
+ * out != NULL and batch_size > 0
+ *   "null dense output pointer"     (status; some but not all of the hypothesis
+ *                                    pointers; one of stable_length / stable_frames)
+ *   "dense outputs decoded and alignment need 8-byte alignment" */
+int ctcext_stream_dense_validate(const ctcext_stream_args* args, const ctcext_chunk* chunk,
+                                 const ctcext_stream_dense_outputs* out);
+/* Grows the stream's workspace to what ctcext_stream_push_dense of chunks of
+ * up to max_chunk_time frames needs; launches nothing.  May allocate and block. */
+int ctcext_stream_reserve(ctcext_stream* s, int64_t max_chunk_time);
+/* Validates on the host (ctcext_stream_dense_validate; a null s or chunk:
+ * "null argument"), then enqueues on one stream (chunk->stream; NULL: the
+ * decoder's own, or the null stream with CTCEXT_FLAG_DENSE_NULL_STREAM in
+ * chunk->flags): a prologue, the chunk's pre-pass, the stream build of the
+ * decode kernel, the commit and, as out asks, the stable-prefix query, the
+ * traceback over all frames so far and the padded pack.  A push whose
+ * workspace fits (a ctcext_stream_reserve with max_chunk_time >= chunk_time,
+ * or an earlier push of at least that size) makes no allocation, no free, no
+ * host-blocking HIP call and no device-to-host copy.  out == NULL: decode only.
+ *
+ * reset (device [batch] or NULL): reset[b] != 0 starts a new utterance in
+ * item b with this chunk -- its frames become 0 and its stable-prefix cache
+ * entry is cleared before the chunk's frames are decoded.  A status bit of the
+ * same push does not undo it.
+ * chunk_length NULL: chunk_time for all; a negative length reads as 0.
+ *   length > chunk_time                   CTCEXT_ITEM_LENGTH     } the item gets no frame from this push:
+ *   frames[b] + length > max_frames       CTCEXT_ITEM_CAPACITY   } its state and frames are as before
+ *   a helper-wave hand-over timeout       CTCEXT_ITEM_HELPER_TIMEOUT: likewise, that item only
+ *   fewer leaves than top_paths           CTCEXT_ITEM_FEW_LEAVES: the frames count as pushed
+ *                                         (pushes with hypothesis outputs only)
+ * An item with any bit has all its rows of this push empty (lengths 0, rows
+ * pad_value, log_probability -inf); an item without one has the hypotheses of
+ * its whole prefix, whether or not this push brought it frames. */
+int ctcext_stream_push_dense(ctcext_stream* s, const ctcext_chunk* chunk, const int32_t* reset,
+                             const ctcext_stream_dense_outputs* out);
+/* Waits for the stream of the last enqueue-only push, refreshes the frame
+ * counts ctcext_stream_frames reads, fills ctcext_stats (cumulative counters,
+ * as after ctcext_stream_push) and reports over all enqueue-only pushes since
+ * the previous check; the first match wins, then the record is cleared:
+ *   lowest b that had _LENGTH     CTCEXT_FAILED_PRECONDITION "sequence_length(b) <= chunk_time" (of its first such push)
+ *   lowest b that had _CAPACITY   CTCEXT_INVALID_ARGUMENT    "stream capacity exceeded: item b would hold n frames of max_frames m"
+ *   any _HELPER_TIMEOUT           CTCEXT_INTERNAL            "decode kernel: a helper-wave hand-over wait timed out"
+ *   any _FEW_LEAVES               CTCEXT_INVALID_ARGUMENT    "Less leaves in the beam search than requested."
+ * Without an enqueue-only push on the stream: CTCEXT_OK.  After replays of a
+ * graph that captured a push it reports those replays. */
+int ctcext_stream_check(ctcext_stream* s);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the chunk's flags, the time of the
+ * commit kernel of the last ctcext_stream_push_dense in ms, after its
+ * ctcext_stream_check (the other kernels' times are in ctcext_stats). */
+int ctcext_stream_commit_ms(ctcext_stream* s, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,15 @@ near-even choice between two continuations and the beam's entries are the
 variants of the last few frames.  A library without the query (an older build
 through CTCEXT_LIB_PATH) prints the other rows only.
 
-    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--input gaussian|peaky|twohot] [--out FILE]
+With --dense every schedule is also run through the enqueue-only
+StreamDecoder.push_dense: with hypothesis outputs on the last push alone (as
+the rows above), with them on every push, and (10-frame pushes) as two
+captured pushes replayed from a graph.  Each reports the host time inside the
+calls, the wall time from the first call to the last outputs complete (the
+synchronous rows' summed push times are wall times too: every push waits), and
+the commit kernel's summed time from a CTCEXT_FLAG_PROFILE run of its own.
+
+    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense] [--input gaussian|peaky|twohot] [--out FILE]
 
 Prints one table and one JSON line.  It is a report, not a check, and it does
 not touch bench.py.
@@ -89,6 +97,92 @@ def streamed(x, chunk, stable=False, info=None):
     return ms, out, kernel
 
 
+def streamed_dense(x, chunk, every, profile=False):
+    """The same schedule through push_dense: (host ms inside the calls, wall ms
+    from the first call to the last outputs complete, the last push's outputs,
+    summed commit-kernel ms of a CTCEXT_FLAG_PROFILE run).  every: hypothesis
+    outputs on every push instead of on the last one alone.  A profile run
+    checks after each push to read that push's events: its wall time is not a
+    measurement."""
+    flags = _lib.CTCEXT_FLAG_PROFILE if profile else 0
+    with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", **KW) as s:
+        s.reserve(chunk)   # opens the stream: its allocations are not timed
+        torch.cuda.synchronize()
+        host = commit = 0.0
+        out = None
+        w0 = time.perf_counter()
+        for t0 in range(0, T, chunk):
+            t1 = min(t0 + chunk, T)
+            h0 = time.perf_counter()
+            out = s.push_dense(x[t0:t1], batch_first=False, results=every or t1 == T, flags=flags)
+            host += time.perf_counter() - h0
+            if profile:
+                s.check()
+                commit += s.commit_ms()
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - w0
+        s.check()
+    return host * 1e3, wall * 1e3, out, commit
+
+
+def streamed_graph(x, chunk):
+    """The schedule as two captured pushes of `chunk` frames over static
+    inputs, one without hypothesis outputs replayed for every chunk but the
+    last and one with them for the last: (host ms, wall ms, outputs).  The
+    chunk is copied into the static tensor on the replay stream before each
+    replay, inside both times."""
+    side = torch.cuda.Stream(device="cuda:0")
+    with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", **KW) as s:
+        s.reserve(chunk)
+        xs = torch.zeros((chunk, B, C), device="cuda:0")
+        torch.cuda.synchronize()
+        g0, g1 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g0, stream=side):
+            s.push_dense(xs, batch_first=False, results=False)
+        with torch.cuda.graph(g1, stream=side):
+            out = s.push_dense(xs, batch_first=False, results=True)
+        torch.cuda.synchronize()
+        host = 0.0
+        w0 = time.perf_counter()
+        with torch.cuda.stream(side):
+            for t0 in range(0, T, chunk):
+                xs.copy_(x[t0:t0 + chunk])
+                h0 = time.perf_counter()
+                (g1 if t0 + chunk >= T else g0).replay()
+                host += time.perf_counter() - h0
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - w0
+        s.check()
+    return host * 1e3, wall * 1e3, out
+
+
+def dense_rows(x, sl, chunks, runs):
+    """--dense: name -> {host_ms, wall_ms (medians, min, max), commit_ms}."""
+    ref = ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, **KW)
+    torch.cuda.synchronize()
+
+    def same(out):
+        return all(torch.equal(a, b) for a, b in zip(out[:5], ref[:5]))
+    rows = {}
+    for c in chunks:
+        variants = [("dense, %d-frame pushes" % c, lambda c=c: streamed_dense(x, c, False)[:3]),
+                    ("dense, %d-frame pushes, results every push" % c, lambda c=c: streamed_dense(x, c, True)[:3])]
+        if c == 10 and T % c == 0:
+            variants.append(("dense, %d-frame pushes, captured graph" % c, lambda c=c: streamed_graph(x, c)))
+        for name, fn in variants:
+            if not same(fn()[2]):   # warm-up
+                raise SystemExit("%s: the result differs from the one-shot decode_dense" % name)
+            got = [fn()[:2] for _ in range(runs)]
+            host, wall = [g[0] for g in got], [g[1] for g in got]
+            rows[name] = {"pushes": -(-T // c), "host_ms": round(statistics.median(host), 3),
+                          "wall_ms": round(statistics.median(wall), 3), "wall_min_ms": round(min(wall), 3),
+                          "wall_max_ms": round(max(wall), 3)}
+        commit = streamed_dense(x, c, False, profile=True)[3]
+        rows["dense, %d-frame pushes" % c]["commit_kernel_ms"] = round(commit, 3)
+        rows["dense, %d-frame pushes" % c]["commit_kernel_ms_per_push"] = round(commit / -(-T // c), 4)
+    return rows
+
+
 def make_input(kind):
     rng = np.random.default_rng(20251015)
     x = rng.standard_normal((T, B, C), dtype=np.float32)
@@ -119,6 +213,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--chunks", default="1500,100,10")
     ap.add_argument("--stable", action="store_true", help="also run each multi-push row with stable() after every push")
+    ap.add_argument("--dense", action="store_true", help="also run each schedule through the enqueue-only push_dense")
     ap.add_argument("--input", default="gaussian", help="gaussian (the bench's logits), peaky or twohot")
     ap.add_argument("--out", default=None, help="also write the table and the JSON line here")
     args = ap.parse_args()
@@ -163,6 +258,15 @@ def main():
         if info:   # what the query costs per push: against the same pushes without it
             plain = statistics.median(rows[name.replace(" + stable()", "")])
             res["rows"][name]["query_ms_per_push"] = round((med - plain) / n, 4)
+    if args.dense and hasattr(_lib.load(), "ctcext_stream_push_dense"):
+        # the sums above are the synchronous rows' wall times (each push waits): the yardstick of wall_ms below
+        dense = dense_rows(x, sl, chunks, args.runs)
+        lines.append("%-52s %9s %9s %9s %9s %12s" % ("push_dense (enqueue-only)", "host ms", "wall ms", "min", "max",
+                                                      "commit ms"))
+        for name, v in dense.items():
+            lines.append("%-52s %9.2f %9.2f %9.2f %9.2f %12s" % (name, v["host_ms"], v["wall_ms"], v["wall_min_ms"],
+                                                                v["wall_max_ms"], v.get("commit_kernel_ms", "")))
+        res["dense_rows"] = dense
     text = "\n".join(lines) + "\n" + json.dumps(res)
     print(text)
     if args.out:
