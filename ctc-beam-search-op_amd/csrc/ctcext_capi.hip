@@ -22,6 +22,7 @@
 #include "ctcx_kernels.h"
 #include "ctcx_stable.h"
 #include "ctcx_stream_dense.h"
+#include "ctcx_times.h"
 
 namespace ctcx {
 template <typename T>
@@ -151,7 +152,8 @@ struct Dev {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t s = nullptr;   // stream of the current call
-  hipEvent_t ev[5] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack
+  hipEvent_t ev[7] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
+                             // [5], [6] around the token-times kernel of a dense call
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
   int64_t lo = 0, nb = 0;    // this call's shard [lo, lo + nb)
@@ -183,7 +185,19 @@ struct ctcext_decoder {
     int32_t P = 0, flags = 0;
     double pack_ms = 0;      // CTCEXT_FLAG_PROFILE: the pack kernel's time (ctcext_dense_pack_ms)
     hipStream_t s = nullptr;
+    // what ctcext_dense_token_times reads beside the workspace
+    int64_t C = 0;
+    int32_t blank_index = 0, blank_label = 0, merge = 0;
+    bool times_timed = false;   // events [5], [6] were recorded
   } dense;
+  // what ctcext_fetch_token_times needs of the last synchronous decode or
+  // push beside the walks: the items' frames (host) and the labels' rule
+  struct {
+    std::vector<int32_t> frames;
+    int64_t C = 0;
+    int32_t blank_index = 0, blank_label = 0, merge = 0;
+  } tt;
+  DevBuf tt_frames, tt_start, tt_end, tt_trail;
 };
 
 static void release_dev(Dev& d) {
@@ -260,7 +274,8 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   if (!d) return;
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
-  DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val};
+  DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
+                    &d->tt_trail};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
   d->h_res.release();
@@ -867,6 +882,9 @@ extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args
   d->have = true;
   d->dtype = a->dtype;
   d->T = T_; d->C = a->num_classes; d->W = a->beam_width; d->P = P;
+  d->tt.frames = hsl;
+  d->tt.C = a->num_classes; d->tt.blank_index = a->blank_index; d->tt.blank_label = a->blank_label;
+  d->tt.merge = a->merge_repeated ? 1 : 0;
   root.s = s;
   if (sizes)
     for (int p = 0; p < P; ++p) sizes[p] = d->sizes[p];
@@ -1111,6 +1129,9 @@ extern "C" int ctcext_decode_dense(ctcext_decoder* d, const ctcext_decode_args* 
   d->dense.B = a->batch_size; d->dense.T = a->max_time; d->dense.P = a->top_paths; d->dense.flags = a->flags;
   d->dense.s = s;
   d->dense.pack_ms = 0;
+  d->dense.C = a->num_classes; d->dense.blank_index = a->blank_index; d->dense.blank_label = a->blank_label;
+  d->dense.merge = a->merge_repeated ? 1 : 0;
+  d->dense.times_timed = false;
   g_err.clear();
   return CTCEXT_OK;
 }
@@ -1222,7 +1243,9 @@ struct ctcext_stream {
     int32_t flags = 0;         // its chunk flags
     bool results = false;      // it had hypothesis outputs
     double commit_ms = 0;
-    hipEvent_t ev[5] = {};     // CTCEXT_FLAG_PROFILE: around prologue + pre-pass, decode, commit, the rest
+    bool times_timed = false;  // events [5], [6] were recorded since it
+    hipEvent_t ev[7] = {};     // CTCEXT_FLAG_PROFILE: around prologue + pre-pass, decode, commit, the rest;
+                               // [5], [6] around its token-times kernel
     DevBuf item, top_pos, top_kind, logp, seq, len;
     DevBuf sl, pre, fin, acc, walked;   // [B] each: sanitised lengths, status before / after the decode,
                                         // the deferred record (CtcxStreamAcc), stable's walked
@@ -1712,6 +1735,10 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
   d->have = true;
   d->dtype = a.dtype;
   d->T = a.max_frames; d->C = a.num_classes; d->W = a.beam_width; d->P = P;
+  d->tt.frames.assign((size_t)B, 0);
+  for (int64_t b = 0; b < B; ++b) d->tt.frames[(size_t)b] = (int32_t)st->frames[(size_t)b];
+  d->tt.C = a.num_classes; d->tt.blank_index = a.blank_index; d->tt.blank_label = a.blank_label;
+  d->tt.merge = a.merge_repeated ? 1 : 0;
   root.s = s;
   for (int p = 0; p < P; ++p) sizes[p] = d->sizes[p];
   g_err.clear();
@@ -2068,6 +2095,7 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
   if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[4], s));
   n.kernel = note[0] | (note[1] << 12) | (note[2] << 16);
   n.results = results;
+  n.times_timed = false;
   return CTCEXT_OK;
 }
 
@@ -2174,5 +2202,177 @@ extern "C" int ctcext_stream_commit_ms(ctcext_stream* st, double* ms) {
   if (!st->dn.used || !(st->dn.flags & CTCEXT_FLAG_PROFILE))
     return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE enqueue-only push checked yet");
   *ms = st->dn.commit_ms;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Token times (ctcext.h, "Token times"): ctcx_times.hip's kernel over the walks
+// the traceback left in the workspace -- the decoder's after a dense or a
+// synchronous call, the stream's own after an enqueue-only push.
+
+extern "C" int32_t ctcext_token_times_tile(void) { return kTimesTile; }
+
+extern "C" int ctcext_token_times_validate(int64_t num_classes, int32_t blank_index, int32_t blank_label) {
+  if (blank_label >= 0 && blank_label < num_classes && blank_label != blank_index)
+    return fail(CTCEXT_INVALID_ARGUMENT, "token times need a blank_label that is no class label");
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+static int check_times_out(const ctcext_token_times* o) {
+  if (!o) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if ((o->start == nullptr) != (o->end == nullptr))
+    return fail(CTCEXT_INVALID_ARGUMENT, "token times: start and end come both or neither");
+  if (!o->start && !o->trailing_blank) return fail(CTCEXT_INVALID_ARGUMENT, "token times: no output asked for");
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_token_times(ctcext_decoder* d, const ctcext_token_times* o) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_times_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_token_times without a ctcext_decode_dense");
+  rc = ctcext_token_times_validate(d->dense.C, d->dense.blank_index, d->dense.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (d->dense.B == 0) return CTCEXT_OK;
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  CtcxTimesParams p{};
+  p.seq = (const int32_t*)root.seq.p;
+  p.len = (const int32_t*)root.len.p;
+  p.frames = (const int32_t*)root.dsl.p;
+  p.status = (const int32_t*)root.dstat.p + B;
+  p.Tmax = d->dense.T; p.B = B; p.P = d->dense.P;
+  p.merge = d->dense.merge; p.blank_label = d->dense.blank_label;
+  p.start = o->start; p.end = o->end; p.trailing_blank = o->trailing_blank;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[5], s));
+  HIP_OR_FAIL(ctcx_launch_token_times(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.ev[6], s));
+    d->dense.times_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_token_times(ctcext_stream* st, const ctcext_token_times* o) {
+  if (!st) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_times_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  auto& n = st->dn;
+  const ctcext_stream_args& a = st->a;
+  if (a.batch_size > 0 && (!n.used || !n.results))
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_stream_token_times without a ctcext_stream_push_dense that had hypothesis outputs");
+  rc = ctcext_token_times_validate(a.num_classes, a.blank_index, a.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (a.batch_size == 0) return CTCEXT_OK;
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  hipStream_t s = n.s;
+  CtcxTimesParams p{};
+  p.seq = (const int32_t*)n.seq.p;
+  p.len = (const int32_t*)n.len.p;
+  p.frames = (const int32_t*)st->cum;
+  p.status = (const int32_t*)n.fin.p;
+  p.Tmax = a.max_frames; p.B = a.batch_size; p.P = a.top_paths;
+  p.merge = a.merge_repeated ? 1 : 0; p.blank_label = a.blank_label;
+  p.start = o->start; p.end = o->end; p.trailing_blank = o->trailing_blank;
+  const bool prof = (n.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[5], s));
+  HIP_OR_FAIL(ctcx_launch_token_times(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(n.ev[6], s));
+    n.times_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_fetch_token_times(ctcext_decoder* d, const ctcext_token_times* o, int32_t outputs_on_device) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_times_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_fetch_token_times without a successful ctcext_decode");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "token times need a one-device decoder handle");
+  rc = ctcext_token_times_validate(d->tt.C, d->tt.blank_index, d->tt.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  const int64_t B = d->B, T_ = d->T;
+  const int P = d->P;
+  if (B == 0 || (int64_t)d->tt.frames.size() != B) {
+    if (B != 0) return fail(CTCEXT_INTERNAL, "token times: the frame counts of the last call are missing");
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.s;
+  const size_t rows = (size_t)(B * P), cells = rows * (size_t)T_;
+  HIP_OR_FAIL(d->tt_frames.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(hipMemcpyAsync(d->tt_frames.p, d->tt.frames.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  CtcxTimesParams p{};
+  p.seq = (const int32_t*)root.seq.p;
+  p.len = (const int32_t*)root.len.p;
+  p.frames = (const int32_t*)d->tt_frames.p;
+  p.status = nullptr;   // (a synchronous call with a failing item has failed as a whole)
+  p.Tmax = T_; p.B = B; p.P = P;
+  p.merge = d->tt.merge; p.blank_label = d->tt.blank_label;
+  if (outputs_on_device) {
+    p.start = o->start; p.end = o->end; p.trailing_blank = o->trailing_blank;
+  } else {
+    if (o->start) {
+      HIP_OR_FAIL(d->tt_start.ensure(4 * cells + 16));
+      HIP_OR_FAIL(d->tt_end.ensure(4 * cells + 16));
+      p.start = (int32_t*)d->tt_start.p;
+      p.end = (int32_t*)d->tt_end.p;
+    }
+    if (o->trailing_blank) {
+      HIP_OR_FAIL(d->tt_trail.ensure(4 * rows + 16));
+      p.trailing_blank = (int32_t*)d->tt_trail.p;
+    }
+  }
+  HIP_OR_FAIL(ctcx_launch_token_times(p, s));
+  if (!outputs_on_device) {
+    if (o->start && cells) {
+      HIP_OR_FAIL(hipMemcpyAsync(o->start, p.start, 4 * cells, hipMemcpyDeviceToHost, s));
+      HIP_OR_FAIL(hipMemcpyAsync(o->end, p.end, 4 * cells, hipMemcpyDeviceToHost, s));
+    }
+    if (o->trailing_blank) HIP_OR_FAIL(hipMemcpyAsync(o->trailing_blank, p.trailing_blank, 4 * rows, hipMemcpyDeviceToHost, s));
+  }
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_token_times_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.times_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no token times of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.ev[6]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[5], root.ev[6]));
+  *ms = f;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_token_times_ms(ctcext_stream* st, double* ms) {
+  if (!st || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!st->dn.used || !st->dn.times_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no token times of a CTCEXT_FLAG_PROFILE enqueue-only push");
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  HIP_OR_FAIL(hipEventSynchronize(st->dn.ev[6]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, st->dn.ev[5], st->dn.ev[6]));
+  *ms = f;
   return CTCEXT_OK;
 }

@@ -3,11 +3,13 @@ tracking; a drop-in for prouast/ctc-beam-search-op's
 ``ctc_ext_beam_search_decoder`` (tensorflow_ctc_ext_beam_search_decoder/__init__.py:19).
 """
 from .ops import (CTCExtBeamSearchDecoder, Decoder, DenseDecode, FailedPreconditionError, InternalError,
-                  InvalidArgumentError, OpError, StablePrefix, StreamDecoder, StreamDense, UnimplementedError,
-                  ctc_ext_beam_search_decoder, decode_dense, decode_logits, dense_check, get_decoder)
+                  InvalidArgumentError, OpError, StablePrefix, StreamDecoder, StreamDense, TokenTimes,
+                  UnimplementedError, ctc_ext_beam_search_decoder, decode_dense, decode_logits, dense_check,
+                  dense_token_times, get_decoder, token_times, token_times_row)
 
 __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "StablePrefix", "StreamDense",
            "decode_dense", "dense_check", "DenseDecode",
+           "dense_token_times", "token_times", "token_times_row", "TokenTimes",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

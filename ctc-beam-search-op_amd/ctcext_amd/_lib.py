@@ -54,6 +54,11 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_STABLE_SYMBOLS
 STREAM_DENSE_SYMBOLS = ("ctcext_stream_dense_validate", "ctcext_stream_reserve", "ctcext_stream_push_dense",
                         "ctcext_stream_check", "ctcext_stream_commit_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_DENSE_SYMBOLS
+# token times (CTCEXT_HAS_TOKEN_TIMES)
+TOKEN_TIMES_SYMBOLS = ("ctcext_token_times_validate", "ctcext_token_times_tile", "ctcext_dense_token_times",
+                       "ctcext_stream_token_times", "ctcext_fetch_token_times", "ctcext_token_times_row",
+                       "ctcext_dense_token_times_ms", "ctcext_stream_token_times_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TOKEN_TIMES_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -105,6 +110,11 @@ class DenseOutputs(ctypes.Structure):
                 ("alignment", ctypes.c_void_p), ("alignment_length", ctypes.c_void_p),
                 ("log_probability", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("pad_value", ctypes.c_int64)]
+
+
+class TokenTimesOut(ctypes.Structure):
+    """ctcext_token_times: the outputs of the token-times calls."""
+    _fields_ = [("start", ctypes.c_void_p), ("end", ctypes.c_void_p), ("trailing_blank", ctypes.c_void_p)]
 
 
 class StreamDenseOutputs(ctypes.Structure):
@@ -259,6 +269,28 @@ def load():
         lib.ctcext_stream_check.restype = ctypes.c_int
         lib.ctcext_stream_commit_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_stream_commit_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_token_times"):   # (CTCEXT_HAS_TOKEN_TIMES; older builds stay loadable for A/B runs)
+        lib.ctcext_token_times_validate.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
+        lib.ctcext_token_times_validate.restype = ctypes.c_int
+        lib.ctcext_token_times_tile.argtypes = []
+        lib.ctcext_token_times_tile.restype = ctypes.c_int32
+        lib.ctcext_dense_token_times.argtypes = [ctypes.c_void_p, ctypes.POINTER(TokenTimesOut)]
+        lib.ctcext_dense_token_times.restype = ctypes.c_int
+        lib.ctcext_stream_token_times.argtypes = [ctypes.c_void_p, ctypes.POINTER(TokenTimesOut)]
+        lib.ctcext_stream_token_times.restype = ctypes.c_int
+        lib.ctcext_fetch_token_times.argtypes = [ctypes.c_void_p, ctypes.POINTER(TokenTimesOut), ctypes.c_int32]
+        lib.ctcext_fetch_token_times.restype = ctypes.c_int
+        # (int64 decoded[m], m, int64 alignment[L], L, frames, blank_label, merge_repeated,
+        #  int32 start[m], int32 end[m], int32* trailing_blank)
+        lib.ctcext_token_times_row.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                               ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+        lib.ctcext_token_times_row.restype = ctypes.c_int
+        lib.ctcext_dense_token_times_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_token_times_ms.restype = ctypes.c_int
+        lib.ctcext_stream_token_times_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_stream_token_times_ms.restype = ctypes.c_int
     _lib = lib
     return lib
 

@@ -474,10 +474,119 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
     if rc != _lib.CTCEXT_OK:
         _raise(lib, rc)
     dec.last_stats = dec.stats()
+    dec._times_dense = (B, P, T, dev)   # (dense_token_times' output shapes)
     # x, sl and tab may be temporaries: they were allocated on this stream, and
     # the caching allocator hands their memory out again in stream order
     del x, sl, tab
     return out
+
+
+TokenTimes = collections.namedtuple("TokenTimes", ["start", "end", "trailing_blank"])
+
+
+def _times_lib(lib):
+    if not hasattr(lib, "ctcext_dense_token_times"):
+        raise UnimplementedError("this libctcext.so has no token times (CTCEXT_HAS_TOKEN_TIMES)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+def _thread_decoder(device, what):
+    index = _device_index(device)
+    if index is None:
+        index = _current_device()
+    dec = getattr(_tls, "decoders", {}).get(int(index))
+    if dec is None:   # no handle yet on this thread: no decode either
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    return dec
+
+
+def _times_device(dev, B, P, width):
+    """Uninitialised CUDA outputs of a token-times call and their struct."""
+    import torch
+    with torch.cuda.device(dev):
+        out = TokenTimes(torch.empty((B, P, width), dtype=torch.int32, device=dev),
+                         torch.empty((B, P, width), dtype=torch.int32, device=dev),
+                         torch.empty((B, P), dtype=torch.int32, device=dev))
+    o = _lib.TokenTimesOut()
+    o.start, o.end, o.trailing_blank = [t.data_ptr() for t in out]
+    return out, o
+
+
+def dense_token_times(device=None):
+    """Start and end frames of every decoded token of the calling thread's
+    last ``decode_dense`` on ``device`` (None: the current one), and the blank
+    frames each best path ends in, without waiting for anything: one small
+    kernel enqueued behind the decode, on the stream the decode went to (so it
+    can be captured into the same ``torch.cuda.graph``).
+
+    Returns ``TokenTimes(start, end, trailing_blank)``: int32 CUDA tensors,
+    ``start`` and ``end`` ``[B, top_paths, T]`` and ``trailing_blank``
+    ``[B, top_paths]``.  Token ``i`` of row ``[b, p]`` of ``decoded`` spans
+    frames ``start[b, p, i]`` .. ``end[b, p, i]`` of item b (a token merged by
+    ``merge_repeated`` spans the blanks between its runs).  Tokens the
+    alignment does not reach, and everything past the row's decoded length, are
+    -1; an item with a status bit has rows of -1 and ``trailing_blank`` 0.  The
+    definition (``include/ctcext.h``, "Token times") needs a ``blank_label``
+    that is no class label: ``InvalidArgumentError`` otherwise."""
+    what = "ctcext_dense_token_times without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = _times_lib(dec.lib)
+    shape = getattr(dec, "_times_dense", None)
+    if shape is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev = shape
+    out, o = _times_device(dev, B, P, T)
+    rc = lib.ctcext_dense_token_times(dec.handle, ctypes.byref(o))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def token_times(device=None):
+    """``dense_token_times`` for the synchronous calls: the token times of the
+    hypotheses the calling thread's last ``ctc_ext_beam_search_decoder``,
+    ``decode_logits`` or ``StreamDecoder.push`` on ``device`` returned.  Waits.
+    Rows are ``max_time`` (``max_frames`` after a push) wide.  Returns numpy
+    arrays, or CUDA tensors where that call's outputs were."""
+    what = "ctcext_fetch_token_times without a successful ctcext_decode"
+    dec = _thread_decoder(device, what)
+    lib = _times_lib(dec.lib)
+    shape = getattr(dec, "_times_sync", None)
+    if shape is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, to_device = shape
+    if to_device:
+        import torch
+        out, o = _times_device(torch.device("cuda", dec.device), B, P, T)
+    else:
+        out = TokenTimes(np.empty((B, P, T), np.int32), np.empty((B, P, T), np.int32), np.empty((B, P), np.int32))
+        o = _lib.TokenTimesOut()
+        o.start, o.end, o.trailing_blank = [t.ctypes.data for t in out]
+    rc = lib.ctcext_fetch_token_times(dec.handle, ctypes.byref(o), 1 if to_device else 0)
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def token_times_row(decoded, alignment, frames, blank_label, merge_repeated=False):
+    """The definition of the token times for one row, on the host (no GPU):
+    ``decoded`` and ``alignment`` are one path's label and alignment rows in
+    label order (without padding), ``frames`` the item's frame count.  Returns
+    ``(start, end, trailing_blank)``: int32 arrays of ``len(decoded)`` and an
+    int."""
+    lib = _times_lib(_lib.load())
+    d = np.ascontiguousarray(np.asarray(decoded, dtype=np.int64).reshape(-1))
+    al = np.ascontiguousarray(np.asarray(alignment, dtype=np.int64).reshape(-1))
+    start = np.empty((d.size,), np.int32)
+    end = np.empty((d.size,), np.int32)
+    trailing = ctypes.c_int32()
+    rc = lib.ctcext_token_times_row(_ptr(d, ctypes.c_int64), int(d.size), _ptr(al, ctypes.c_int64), int(al.size),
+                                    int(frames), int(blank_label), 1 if merge_repeated else 0,
+                                    _ptr(start, ctypes.c_int32), _ptr(end, ctypes.c_int32), ctypes.byref(trailing))
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_token_times_row: bad arguments", rc)
+    return start, end, int(trailing.value)
 
 
 def dense_check(device=None):
@@ -570,8 +679,9 @@ def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index
         import torch
         torch.cuda.current_stream(device).synchronize()
     sizes = dec.decode(a)
-    out = _fetch_outputs(dec, sizes, int(shape[1]), int(top_paths), code,
-                         outputs == "device" or (outputs == "auto" and on_device))
+    to_device = outputs == "device" or (outputs == "auto" and on_device)
+    dec._times_sync = (int(shape[1]), int(top_paths), int(shape[0]), to_device)   # (token_times' output shapes)
+    out = _fetch_outputs(dec, sizes, int(shape[1]), int(top_paths), code, to_device)
     del keep
     _print_no_label(dec.last_stats["no_label_paths"])
     return out
@@ -798,8 +908,9 @@ class StreamDecoder:
         if not results:
             return None
         szs = [(s.num_decoded, s.max_decoded, s.num_alignment, s.max_alignment) for s in sizes]
-        out = _fetch_outputs(dec, szs, int(a.batch_size), P, a.dtype,
-                             outputs == "device" or (outputs == "auto" and on_device))
+        to_device = outputs == "device" or (outputs == "auto" and on_device)
+        dec._times_sync = (int(a.batch_size), P, int(a.max_frames), to_device)   # (token_times' output shapes)
+        out = _fetch_outputs(dec, szs, int(a.batch_size), P, a.dtype, to_device)
         _print_no_label(dec.last_stats["no_label_paths"])
         return out
 
@@ -947,6 +1058,38 @@ class StreamDecoder:
         # the caching allocator hands their memory out again in stream order
         del x, sl, rs
         return out
+
+    def token_times_dense(self):
+        """``dense_token_times`` for the last ``push_dense`` with results:
+        ``TokenTimes(start, end, trailing_blank)`` of everything pushed so far,
+        rows ``max_frames`` wide, enqueued behind that push on its stream (so
+        the two can be captured together).  Frames count from the item's last
+        reset.  ``FailedPreconditionError`` after a ``results=False`` push or
+        before any ``push_dense``."""
+        self._check_open()
+        lib = _times_lib(self.lib)
+        a = self._args
+        if not self.handle:
+            raise FailedPreconditionError(
+                "ctcext_stream_token_times without a ctcext_stream_push_dense that had hypothesis outputs",
+                _lib.CTCEXT_FAILED_PRECONDITION)
+        import torch
+        out, o = _times_device(torch.device("cuda", self.dec.device), int(a.batch_size), int(a.top_paths),
+                               int(a.max_frames))
+        rc = lib.ctcext_stream_token_times(self.handle, ctypes.byref(o))
+        if rc != _lib.CTCEXT_OK:
+            _raise(lib, rc)
+        return out
+
+    def token_times_ms(self):
+        """Diagnostics: the token-times kernel's time in ms of the last
+        ``token_times_dense`` after a ``flags=CTCEXT_FLAG_PROFILE`` push.  Waits."""
+        self._check_open()
+        ms = ctypes.c_double()
+        rc = self.lib.ctcext_stream_token_times_ms(self.handle, ctypes.byref(ms))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        return ms.value
 
     def reserve(self, max_chunk_time):
         """Size the stream's workspace for ``push_dense`` of chunks of up to

@@ -589,6 +589,103 @@ int ctcext_stream_check(ctcext_stream* s);
  * ctcext_stream_check (the other kernels' times are in ctcext_stats). */
 int ctcext_stream_commit_ms(ctcext_stream* s, double* ms);
 
+/* ---------------------------------------------------------------------------
+ * Token times: the start and end frame of every decoded token, and the blank
+ * frames the best path ends in, from each path's alignment, on the device.
+ * New entry points and structs only (CTCEXT_ABI_VERSION is unchanged; detect
+ * them by CTCEXT_HAS_TOKEN_TIMES at build time or by symbol at run time).
+ *
+ * Definition.  The inputs are
+ *   frames      the item's frame count (its sanitised length),
+ *   dec[0..m)   one path's decoded row, merge_repeated already applied,
+ *   ali[0..L)   its alignment row; element i is frame frames - L + i, because
+ *               an alignment that restarted is a suffix.
+ * A run is a maximal stretch of equal alignment values other than blank_label.
+ * Runs are matched to tokens from the end:
+ *
+ *   def token_times(dec, ali, frames, blank_label, merge):
+ *       m, L, base = len(dec), len(ali), frames - len(ali)
+ *       start, end, runs, i = [-1] * m, [-1] * m, [], 0
+ *       while i < L:
+ *           j = i
+ *           while j + 1 < L and ali[j + 1] == ali[i]: j += 1
+ *           if ali[i] != blank_label: runs.append((ali[i], base + i, base + j))
+ *           i = j + 1
+ *       trailing = 0
+ *       while trailing < L and ali[L - 1 - trailing] == blank_label: trailing += 1
+ *       j, opened = m - 1, False
+ *       for lab, s, e in reversed(runs):
+ *           if j < 0: break
+ *           if opened and merge and lab == dec[j]:     # an earlier run of the same merged token
+ *               start[j] = s; continue
+ *           if opened: j -= 1; opened = False
+ *           if j < 0 or lab != dec[j]: break           # first mismatch: every earlier token stays -1
+ *           start[j] = s; end[j] = e; opened = True
+ *       return start, end, trailing
+ *
+ * So a token's span runs from the first frame of its first run to the last
+ * frame of its last run; with merge_repeated a merged token spans the blanks
+ * between its runs; tokens the alignment does not reach (the chain restarted,
+ * the path has no label sequence, the item has a status bit) are -1 in both
+ * arrays; the timed tokens are always a suffix of the row and their start
+ * values strictly increase.
+ *
+ * start and end are int32 [batch][top_paths][width], width being max_time
+ * (ctcext_decode_dense, ctcext_decode) or max_frames (a stream); everything
+ * past the row's decoded length is -1, whatever pad_value was.
+ * trailing_blank is int32 [batch][top_paths].
+ *
+ * The definition needs a blank_label that is not a label: a request with
+ * 0 <= blank_label < num_classes and blank_label != blank_index fails, before
+ * any launch, with CTCEXT_INVALID_ARGUMENT
+ *   "token times need a blank_label that is no class label".
+ *
+ * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED), and
+ * stability -- ctcext_stream_stable says which tokens are final, not that
+ * their alignment is, so the times of stable tokens can still move. */
+#define CTCEXT_HAS_TOKEN_TIMES 1
+
+/* Device pointers.  trailing_blank may be NULL; start and end come both or
+ * neither. */
+typedef struct {
+  int32_t* start;           /* [batch][top_paths][width] */
+  int32_t* end;             /* [batch][top_paths][width] */
+  int32_t* trailing_blank;  /* [batch][top_paths] */
+} ctcext_token_times;
+
+/* Host only, no HIP call: the blank_label rule above. */
+int ctcext_token_times_validate(int64_t num_classes, int32_t blank_index, int32_t blank_label);
+/* Elements of a row the kernel covers per step (its carry crosses multiples
+ * of this); for tests. */
+int32_t ctcext_token_times_tile(void);
+/* Enqueues the token-times kernel on the stream of the last
+ * ctcext_decode_dense, behind its pack, over that call's rows (width
+ * max_time).  No allocation, no host-blocking call, no device-to-host copy;
+ * capturable into the same graph as the decode.  Without a preceding
+ * ctcext_decode_dense: CTCEXT_FAILED_PRECONDITION.  An item with a status bit
+ * has rows of -1 and trailing_blank 0. */
+int ctcext_dense_token_times(ctcext_decoder* dec, const ctcext_token_times* out);
+/* The same after a ctcext_stream_push_dense that had hypothesis outputs, over
+ * the stream's own buffers (never the decoder's); rows are max_frames wide.
+ * After a push without hypothesis outputs, or with no enqueue-only push yet:
+ * CTCEXT_FAILED_PRECONDITION. */
+int ctcext_stream_token_times(ctcext_stream* s, const ctcext_token_times* out);
+/* Synchronous; valid whenever ctcext_fetch is (after ctcext_decode, or after a
+ * ctcext_stream_push with sizes).  out's pointers are device pointers with
+ * outputs_on_device, host pointers without.  One-device handles only:
+ * CTCEXT_UNIMPLEMENTED otherwise. */
+int ctcext_fetch_token_times(ctcext_decoder* dec, const ctcext_token_times* out, int32_t outputs_on_device);
+/* Host only, no HIP call: the definition above for one row.  start and end
+ * have m elements (both or neither may be NULL), trailing_blank one (may be
+ * NULL).  Shares no code with the kernel. */
+int ctcext_token_times_row(const int64_t* decoded, int64_t m, const int64_t* alignment, int64_t L, int64_t frames,
+                           int64_t blank_label, int32_t merge_repeated, int32_t* start, int32_t* end,
+                           int32_t* trailing_blank);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's / the chunk's flags,
+ * the time of the last token-times kernel in ms.  Waits for it. */
+int ctcext_dense_token_times_ms(ctcext_decoder* dec, double* ms);
+int ctcext_stream_token_times_ms(ctcext_stream* s, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

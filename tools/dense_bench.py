@@ -16,6 +16,11 @@ Per shape:
 
     python tools/dense_bench.py [--runs 5] [--parent-lib PATH] [--out FILE]
 
+With --times, instead: the token-times kernel (dense_token_times) at cfg3, on
+Gaussian and on peaky inputs (+8 on one class per row, the blank with p = 0.7):
+its HIP-event time under CTCEXT_FLAG_PROFILE beside the pack kernel's of the
+same run and the whole call's (events around decode_dense + dense_token_times).
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -96,6 +101,53 @@ def same(dense, ref, P):
     return torch.equal(dense.log_probability, ref.log_probability) and not bool(dense.status.any())
 
 
+def times_inputs(kind, T, B, C):
+    rng = np.random.default_rng(20261020)
+    x = rng.standard_normal((T, B, C), dtype=np.float32)
+    if kind == "peaky":
+        c = np.where(rng.random((T, B)) < 0.7, 0, rng.integers(1, C, size=(T, B)))
+        np.put_along_axis(x, c[..., None], np.take_along_axis(x, c[..., None], 2) + 8, 2)
+    return torch.as_tensor(x, device="cuda:0")
+
+
+def times_report(args):
+    """--times: one row per input family at cfg3."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    lines = ["%-10s %14s %14s %14s %10s   (median of %d, ms; cfg3 B=%d T=%d C=%d W=%d P=%d)"
+             % ("inputs", "token times", "pack kernel", "whole call", "timed/tok", args.runs, B, T, C, W, P)]
+    res = {"runs": args.runs, "shape": [B, T, C, W, P], "times": {}}
+    for kind in ("gaussian", "peaky"):
+        x = times_inputs(kind, T, B, C)
+        ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, **KW)   # warm-up: workspace, kernels
+        ctcext_amd.dense_token_times()
+        ctcext_amd.dense_check()
+        tt_ms, pack_ms, call_ms = [], [], []
+        for _ in range(args.runs):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, **KW)
+            tt = ctcext_amd.dense_token_times()
+            e1.record()
+            e1.synchronize()
+            ctcext_amd.dense_check()
+            ms = ctypes.c_double()
+            for fn, acc in ((dec.lib.ctcext_dense_token_times_ms, tt_ms), (dec.lib.ctcext_dense_pack_ms, pack_ms)):
+                if fn(dec.handle, ctypes.byref(ms)) != _lib.CTCEXT_OK:
+                    raise SystemExit(dec.lib.ctcext_last_error().decode())
+                acc.append(ms.value)
+            call_ms.append(e0.elapsed_time(e1))
+        tokens = int(out.decoded_lengths.sum())
+        timed = int((tt.start >= 0).sum())
+        lines.append("%-10s %14.4f %14.4f %14.3f %5d/%-5d" % (kind, statistics.median(tt_ms), statistics.median(pack_ms),
+                                                            statistics.median(call_ms), timed, tokens))
+        res["times"][kind] = {"token_times": stat(tt_ms), "pack": stat(pack_ms), "call": stat(call_ms),
+                              "tokens": tokens, "timed": timed, "trailing_blank_max": int(tt.trailing_blank.max())}
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -105,7 +157,17 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--parent-lib", default=None, help="libctcext.so of the parent commit, for (iii)")
     ap.add_argument("--out", default=None, help="also write the tables and the JSON line here")
+    ap.add_argument("--times", action="store_true", help="the token-times kernel's cost at cfg3 instead")
     args = ap.parse_args()
+    if args.times:
+        lines, res = times_report(args)
+        text = "\n".join(lines) + "\n" + json.dumps(res)
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     parent = load_package_with(os.path.abspath(args.parent_lib)) if args.parent_lib else None
     res = {"runs": args.runs, "parent_lib": bool(parent), "shapes": {}}
     lines = []

@@ -33,7 +33,7 @@ calls, the wall time from the first call to the last outputs complete (the
 synchronous rows' summed push times are wall times too: every push waits), and
 the commit kernel's summed time from a CTCEXT_FLAG_PROFILE run of its own.
 
-    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense] [--input gaussian|peaky|twohot] [--out FILE]
+    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense [--times]] [--input gaussian|peaky|twohot] [--out FILE]
 
 Prints one table and one JSON line.  It is a report, not a check, and it does
 not touch bench.py.
@@ -156,6 +156,34 @@ def streamed_graph(x, chunk):
     return host * 1e3, wall * 1e3, out
 
 
+def streamed_times(x, chunk):
+    """--times: the schedule through push_dense with hypothesis outputs and
+    token_times_dense() on every push, under CTCEXT_FLAG_PROFILE, checked after
+    each push to read its events.  Returns per push (token-times kernel ms,
+    traceback + pack ms, the push's kernels' ms in all), and the last outputs."""
+    per = []
+    with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", **KW) as s:
+        s.reserve(chunk)
+        for t0 in range(0, T, chunk):
+            out = s.push_dense(x[t0:min(t0 + chunk, T)], batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE)
+            tt = s.token_times_dense()
+            st = s.check()
+            rest = st["traceback_ms"]
+            per.append((s.token_times_ms(), rest,
+                        st["norm_kernel_ms"] + st["decode_kernel_ms"] + s.commit_ms() + rest))
+    return per, out, tt
+
+
+def times_row(x, chunk, runs):
+    streamed_times(x, chunk)   # warm-up
+    got = [streamed_times(x, chunk)[0] for _ in range(runs)]
+    med = lambda k, sel: round(statistics.median(sel([g[k] for g in r]) for r in got), 4)   # noqa: E731
+    last, mean = (lambda v: v[-1]), (lambda v: sum(v) / len(v))
+    return {"pushes": len(got[0]),
+            "last_push": {"token_times_ms": med(0, last), "traceback_pack_ms": med(1, last), "push_kernels_ms": med(2, last)},
+            "mean_push": {"token_times_ms": med(0, mean), "traceback_pack_ms": med(1, mean), "push_kernels_ms": med(2, mean)}}
+
+
 def dense_rows(x, sl, chunks, runs):
     """--dense: name -> {host_ms, wall_ms (medians, min, max), commit_ms}."""
     ref = ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, **KW)
@@ -215,6 +243,8 @@ def main():
     ap.add_argument("--stable", action="store_true", help="also run each multi-push row with stable() after every push")
     ap.add_argument("--dense", action="store_true", help="also run each schedule through the enqueue-only push_dense")
     ap.add_argument("--input", default="gaussian", help="gaussian (the bench's logits), peaky or twohot")
+    ap.add_argument("--times", action="store_true",
+                    help="with --dense: a row for token_times_dense() after every push of the smallest chunk size")
     ap.add_argument("--out", default=None, help="also write the table and the JSON line here")
     args = ap.parse_args()
     chunks = [int(c) for c in args.chunks.split(",")]
@@ -267,6 +297,16 @@ def main():
             lines.append("%-52s %9.2f %9.2f %9.2f %9.2f %12s" % (name, v["host_ms"], v["wall_ms"], v["wall_min_ms"],
                                                                 v["wall_max_ms"], v.get("commit_kernel_ms", "")))
         res["dense_rows"] = dense
+        if args.times and hasattr(_lib.load(), "ctcext_stream_token_times"):
+            c = min(chunks)
+            tr = times_row(x, c, args.runs)
+            lines.append("token times, %d-frame pushes with results (PROFILE, median of %d runs; ms)  %12s %16s %14s"
+                         % (c, args.runs, "token times", "traceback+pack", "push kernels"))
+            for k in ("last_push", "mean_push"):
+                lines.append("  %-83s %12.4f %16.4f %14.4f" % (k.replace("_", " ") + (" (rows of %d frames)" % T if k == "last_push" else ""),
+                                                              tr[k]["token_times_ms"], tr[k]["traceback_pack_ms"],
+                                                              tr[k]["push_kernels_ms"]))
+            res["times_row"] = tr
     text = "\n".join(lines) + "\n" + json.dumps(res)
     print(text)
     if args.out:
