@@ -2618,6 +2618,30 @@ constexpr bool kCtab = CTCX_CTAB != 0;
 __host__ __device__ constexpr size_t sq_ctab_bytes(int wcap, int C) {
   return (kCtab && C <= 64) ? (size_t)wcap * 8 + (size_t)wcap * 64 : 0;
 }
+// The frame boundary of the scored queue's small-C kernels (SQ && !BIG: float,
+// beams <= 128, C <= 64, base scorer), off wave 0's chain (DESIGN, round 16):
+// CTCX_ROW_PREFETCH: the helper, idle once its ranks are out, loads row t + 1
+// and its normaliser into a second row buffer while wave 0 extracts, and names
+// the frame in kPfRowT; frame t + 1's row stage then only switches buffers.
+// CTCX_EARLY_CHUNK0: with the beam full the helper goes from the row test
+// straight into the gather, so the frame's first chunk is scored beside wave
+// 0's recursion (from a bottom of -inf: any bottom at or below the true one
+// gives a correct chunk), and wave 0 rolls and recurses its 128 branches alone.
+#ifndef CTCX_ROW_PREFETCH
+#define CTCX_ROW_PREFETCH 1
+#endif
+#ifndef CTCX_EARLY_CHUNK0
+#define CTCX_EARLY_CHUNK0 1
+#endif
+constexpr bool kRowPrefetch = CTCX_ROW_PREFETCH != 0;
+constexpr bool kEarlyChunk0 = CTCX_EARLY_CHUNK0 != 0;
+// the second row buffer, then four words: the frame it holds (kPfRowT; -1:
+// none) and that row's normaliser (kPfNorm).  After the children table, so
+// decode_lds_bytes (and with it ctcext_max_beam_width) is what it was.
+[[maybe_unused]] constexpr int kPfRowT = 0, kPfNorm = 1;
+__host__ __device__ constexpr size_t sq_rowpf_bytes(int64_t C) {
+  return (kRowPrefetch && C <= 64) ? ((((size_t)C * 4) + 15) & ~(size_t)15) + 16 : 0;
+}
 // Large C, beams of up to 256 (BIG kernels, WC > 0): GetChild through a
 // (parent, label) -> child hash table instead of a walk down the parent's
 // sibling list (up to one dependent LDS read pair per child of the branch:
@@ -2939,7 +2963,13 @@ constexpr bool kSqFirst1 = CTCX_SQ_FIRST1 != 0;
 #define CTCX_SQ_CAP0 32
 #endif
 constexpr int kSqCap0 = CTCX_SQ_CAP0;   // large C: offers in the frame's first chunk (cfg4: 16, 32, 64 within 0.2%)
-template <typename T, bool BIG>
+// EARLY (kEarlyChunk0): called beside wave 0's recursion with a bottom of
+// -inf.  Chunk 0 is gathered at once; before chunk 1 the helper waits for wave
+// 0's starting bottom (kCtlBot no longer the -inf of the row stage: a frame
+// that stays exact has finite totals only), or chunk 1 would be gathered
+// dense and wave 0 would pay for offers the true bottom rejects.  A frame
+// whose recursion gave a non-finite total ends that wait through kCtlDone.
+template <typename T, bool BIG, bool EARLY = false>
 __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, int nb, T norm, T pmax,
                                                    T bottom) {
   const int lane = threadIdx.x & 63;
@@ -2962,7 +2992,13 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
         done = true;
         break;
       }
-      if (c < ctl_ld(m, kCtlCons) + (BIG ? 1 : kSqLead)) break;
+      if (c < ctl_ld(m, kCtlCons) + (BIG ? 1 : kSqLead)) {
+        if constexpr (EARLY) {
+          if (c == 0 || ctl_ld(m, kCtlBot) != (int)0xff800000u) break;
+        } else {
+          break;
+        }
+      }
       __builtin_amdgcn_s_sleep(CTCX_SLEEP);
     }
     CTCX_HPC(cx, 26, CTCX_HTIME() - hw0);
@@ -3270,6 +3306,104 @@ __device__ CTCX_HELPER_FN_GQ void help_gather_chunks(CTCX_HCTX_GQ cx, GQ q, int 
   if (cbr >= 0) cq_children(cx, buf, nb, cbr, -1);   // the child bitmap starts the next frame clear
 }
 
+// kEarlyChunk0: wave 0's roll and recursion over every branch of a full beam
+// (beams <= 128: branches lane and lane + 64), with no workgroup barrier.
+// CTCX_RECURSE_PAIR: the lane's two branches as one unrolled body -- every
+// read of both (frame-start arrays, the row) ahead of either's writes, so the
+// two chains of LDS reads, lse calls and candidate pushes overlap.  The roll
+// is folded in: recurse_branch overwrites the total, both endings and the
+// flags the roll would write, so the rolled label-ending total is read from
+// the frame-start array and the flags are the roll's 0.  Same arithmetic and
+// order per branch as recurse_branch(i, i, norm, false).  Bit-exact, measured
+// slower (cfg3 114.4 -> 116.3 ms per step, cfg2 41.9 -> 43.2, every pair, same
+// box; the kernel at 254 VGPRs instead of 252; profiles/r16_ab_cfg3.txt): off,
+// wave 0 keeps the loop over its two branches.
+#ifndef CTCX_RECURSE_PAIR
+#define CTCX_RECURSE_PAIR 0
+#endif
+constexpr bool kRecursePair = CTCX_RECURSE_PAIR != 0;
+template <typename T>
+struct RecNew {
+  T nbk, nl, tot, cb, cn;
+  uint32_t bpb, bpn;
+  int flg, lab;
+};
+template <typename T, class SC>
+__device__ __forceinline__ RecNew<T> recurse_rolled(const Ctx<T>& cx, int buf, int i, T norm) {
+  static_assert(!SC::kStateful, "base scorer");
+  const T NI = ninf<T>();
+  const int f = sel(cx.flg, buf)[i];
+  const int L = sel(cx.lab, buf)[i];
+  const bool isroot = (f & F_ROOT) != 0;
+  const T o_t = sel(cx.ot, buf)[i];
+  const bool fresh = (o_t == NI);
+  const T rs_blank = (isroot || ((f & F_PROOT) && fresh)) ? T(0) : NI;
+  T nl = sel(cx.ol, buf)[i];   // (the rolled newp.label)
+  Best<T> bn{T(0), kBpNone, false}, bb{T(0), kBpNone, false};
+  if (!isroot) {
+    const T xl = cx.row[L];
+    const T p = xl - norm;
+    const int P = sel(cx.par, buf)[i];
+    if (P >= 0) {
+      const bool same = (L == sel(cx.lab, buf)[P]);
+      const T prev = same ? sel(cx.ob, buf)[P] : sel(cx.ot, buf)[P];
+      nl = lse(nl, prev, cx.etab) + xl - norm;
+      cand_from(cx, buf, P, 0, p, rs_blank, bn);
+      if (!same) cand_from(cx, buf, P, 1, p, NI, bn);
+      cand_from(cx, buf, i, 1, p, NI, bn);
+    } else {
+      nl += xl - norm;
+      cand_from(cx, buf, i, 1, p, NI, bn);
+    }
+  }
+  const T xb = cx.row[cx.blank];
+  const T nbk = o_t + xb - norm;
+  const T pb = xb - norm;
+  cand_from(cx, buf, i, 0, pb, rs_blank, bb);
+  cand_from(cx, buf, i, 1, pb, NI, bb);
+  RecNew<T> r;
+  r.nbk = nbk; r.nl = nl; r.tot = lse(nbk, nl, cx.etab);
+  r.cb = bb.p; r.bpb = bb.bp; r.cn = bn.p; r.bpn = bn.bp;
+  r.flg = (bb.ok ? F_HB : 0) | (bn.ok ? F_HN : 0);
+  r.lab = L;
+  return r;
+}
+template <typename T>
+__device__ __forceinline__ void recurse_store(const Ctx<T>& cx, int e, const RecNew<T>& r) {
+  cx.eb[e] = r.nbk;
+  cx.el[e] = r.nl;
+  cx.et[e] = r.tot;
+  cx.ecb[e] = r.cb; cx.ebpb[e] = r.bpb;
+  cx.ecn[e] = r.cn; cx.ebpn[e] = r.bpn;
+  cx.eflg[e] = r.flg;
+  cx.ekind[e] = ((uint32_t)e << 1);
+  cx.elab[e] = r.lab;
+  cx.bst[e] = 0;
+  cx.bloom[e] = 0;
+}
+template <typename T, class SC>
+__device__ __forceinline__ void recurse_wave0(const Ctx<T>& cx, int buf, int nb, T norm) {
+  const int lane = threadIdx.x & 63;
+  if constexpr (kRecursePair) {
+    // (nb >= W >= 1: a lane without a branch computes on branch 0 and stores nothing)
+    const int ia = lane, ib = lane + 64;
+    const bool va = ia < nb, vb = ib < nb;
+    const RecNew<T> ra = recurse_rolled<T, SC>(cx, buf, va ? ia : 0, norm);
+    const RecNew<T> rb = recurse_rolled<T, SC>(cx, buf, vb ? ib : 0, norm);
+    if (va) recurse_store<T>(cx, ia, ra);
+    if (vb) recurse_store<T>(cx, ib, rb);
+  } else {
+    for (int i = lane; i < nb; i += 64) {
+      cx.et[i] = sel(cx.ot, buf)[i]; cx.eb[i] = sel(cx.ob, buf)[i]; cx.el[i] = sel(cx.ol, buf)[i];
+      cx.eflg[i] = 0;
+      cx.bst[i] = 0;
+      cx.bloom[i] = 0;
+    }
+    for (int i = lane; i < nb; i += 64) recurse_branch<T, SC>(cx, buf, i, i, norm, false);
+  }
+  wsync<true>();   // (one wave: its LDS operations execute in order)
+}
+
 #ifdef CTCX_SQ_CHECK
 __shared__ int g_sq_dbg[8];   // (diagnostics: the first scored-field mismatch)
 #endif
@@ -3313,16 +3447,50 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   // every offer's score p + base computed the reference's way
   const T pmax = xmax - norm;
 
-  // roll (decoder.h:87-92) + recursion (decoder.h:95-143), threads over branches
-  for (int i = tid; i < nb; i += NT) {
-    cx.et[i] = sel(cx.ot, buf)[i]; cx.eb[i] = sel(cx.ob, buf)[i]; cx.el[i] = sel(cx.ol, buf)[i];
-    cx.eflg[i] = 0;
-    cx.bst[i] = 0;
-    cx.bloom[i] = 0;
+  // The frame's first chunk beside the recursion (kEarlyChunk0; small-C scored
+  // float kernels, beam full: where the helper gathers at all).  Chunk 0 reads
+  // only the frame-start arrays, the row and norm, and the recursion writes
+  // only the e* arrays, so the helper starts its gather here, from a bottom of
+  // -inf, while wave 0 rolls and recurses every branch itself (lanes over i and
+  // i + 64: recurse_branch(i), not literal, reads the frame-start arrays, the
+  // row and entry i's own words, which the same lane has just rolled).
+  // Workgroup barriers executed inside exact_step, per path (nb is uniform
+  // over the workgroup, and the row test above is decided alike by both
+  // waves; a mismatch between the waves would be a hang):
+  //                                  wave 0   wave 1
+  //   bad row (return 1 above)         0        0
+  //   early path (nb >= W)             0        0     <- neither runs the two below
+  //   every other path                 2        2
+  // A non-finite total on the early path: wave 0 returns 1 alone; the helper,
+  // already in its loop, leaves through the kCtlDone the kernel stores next.
+  constexpr bool kEc0 = kEarlyChunk0 && HW && SQ && !BIG && RN == 1 && sizeof(T) == 4 && !SC::kStateful;
+  bool early = false;
+  if constexpr (kEc0) early = nb >= W;
+  if (kEc0 && early) {
+    if constexpr (kEc0) {
+      if (helper_wave()) {
+        help_gather_scored<T, BIG, true>(cx, gq, buf, nb, norm, pmax, NI);
+        if constexpr (kExtRank && !kExtLate) {
+          [[maybe_unused]] const uint64_t hr0 = CTCX_HTIME();
+          help_rank_extract<T>(cx, (CTCX_LDS int*)gq.p, buf);
+          CTCX_HPC(cx, 28, CTCX_HTIME() - hr0);
+        }
+        return 0;   // the kernel takes wave 0's result
+      }
+      recurse_wave0<T, SC>(cx, buf, nb, norm);
+    }
+  } else {
+    // roll (decoder.h:87-92) + recursion (decoder.h:95-143), threads over branches
+    for (int i = tid; i < nb; i += NT) {
+      cx.et[i] = sel(cx.ot, buf)[i]; cx.eb[i] = sel(cx.ob, buf)[i]; cx.el[i] = sel(cx.ol, buf)[i];
+      cx.eflg[i] = 0;
+      cx.bst[i] = 0;
+      cx.bloom[i] = 0;
+    }
+    __syncthreads();
+    for (int i = tid; i < nb; i += NT) recurse_branch<T, SC>(cx, buf, i, i, norm, false);
+    __syncthreads();
   }
-  __syncthreads();
-  for (int i = tid; i < nb; i += NT) recurse_branch<T, SC>(cx, buf, i, i, norm, false);
-  __syncthreads();
   bool nonfinite = false;
   T lmin = pinf<T>();   // (the smallest leaf: the bottom of a full beam)
   for (int i = lane; i < nb; i += 64) {   // (HW: each wave tests every branch, so both decide alike)
@@ -3335,6 +3503,10 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   if constexpr (HW) {
     if (helper_wave()) {
       if constexpr (SQ) {
+        // (kEc0: a full beam took the early path above, so this call is never
+        // reached there.  Compiling it out was measured: the kernel is 2 KB
+        // shorter and cfg3 1.5% slower, 116.1 against 114.4 ms per step --
+        // placement; profiles/r16_ab_prefetch_cfg3.txt.  It stays.)
         if (nb >= W) help_gather_scored<T, BIG>(cx, gq, buf, nb, norm, pmax, wave_min(lmin));
         if constexpr (RN == 1 && kExtRank && (kExtBig || !BIG) && !kExtLate) {
           [[maybe_unused]] const uint64_t hr0 = CTCX_HTIME();
@@ -3375,6 +3547,12 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   if (full) {                     // branch 0's is_candidate() peeks
     front = wave_first_min_to_front(he, n);
     st = kTopBottomKnown;
+    // (kEarlyChunk0: the helper, gathering since before the recursion, waits
+    // for this starting bottom before its second chunk)
+    if constexpr (kEc0)
+      if (early)
+        __hip_atomic_store(&cx.misc[kCtlBot], (int)__builtin_bit_cast(unsigned, (float)front.v), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   T bottom = full ? front.v : NI;
   // the set mode (kSetMode): kernels with the helper's ranks, float beams <= 128
@@ -5601,6 +5779,15 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
   Ring<RT> rg{};
   [[maybe_unused]] Tab tb{};
   [[maybe_unused]] GQ gq{};
+  // kRowPrefetch (small-C scored kernels): the row buffer the frame does not
+  // use, and the words that say which frame's row and normaliser it holds
+#ifndef CTCX_GSTATE
+  constexpr bool kPf = kRowPrefetch && HW && SQ && !BIG && RN == 1 && sizeof(T) == 4 && !SC::kStateful;
+#else
+  constexpr bool kPf = false;
+#endif
+  [[maybe_unused]] CTCX_LDS T* row2 = nullptr;
+  [[maybe_unused]] CTCX_LDS int* pfw = nullptr;
 #ifndef CTCX_GSTATE
   {
     size_t off = (decode_lds_bytes(WC > 0 ? WC : W, C, (int)sizeof(T), SC::kStateful) + 15) & ~(size_t)15;
@@ -5616,6 +5803,11 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
         gq.cmask = (CTCX_LDS uint64_t*)((CTCX_LDS char*)lds + off);
         gq.ctab = (CTCX_LDS uint8_t*)((CTCX_LDS char*)lds + off + (size_t)WC * 8);
         off += sq_ctab_bytes(WC, 0);
+      }
+      if constexpr (kPf) {   // the second row buffer and its words (sq_rowpf_bytes)
+        row2 = (CTCX_LDS T*)((CTCX_LDS char*)lds + off);
+        pfw = (CTCX_LDS int*)((CTCX_LDS char*)lds + off + sq_rowpf_bytes(C) - 16);
+        off += sq_rowpf_bytes(C);
       }
     }
     if (R > 0) rg = ring_carve<RT>((CTCX_LDS char*)lds + off, R, W);
@@ -5678,6 +5870,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     // run out of time, so the failure path runs without a hang)
     cx.misc[kCtlDead] = (HW && (prm.test_flags & kTestHelperDead)) ? 1 : 0;
     cx.misc[15] = 0;
+    if constexpr (kPf) pfw[kPfRowT] = -1;   // no row held: a prefetch never crosses a launch (a stream's push)
 #ifdef CTCX_STREAM
   }
   // (the per-launch words above are set after the load; the rest of Reset()
@@ -5741,9 +5934,24 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     // into x (elements of prm.xfmt); everything below works on the LDS copy
     const int64_t xoff = (int64_t)t * prm.xst_t + (int64_t)b * prm.xst_b;
     const T* xr = prm.x + xoff;
+    [[maybe_unused]] bool pf_hit = false;   // kRowPrefetch: this frame's row is in the other buffer already
 #ifdef CTCX_GSTATE
     cx.row = const_cast<T*>(xr);   // (read in place: the host hands this tier rows of T)
 #else
+    // kRowPrefetch: the helper loaded this frame's row and normaliser during
+    // the last frame's extract (below): switch buffers.  The word is uniform
+    // over the workgroup: written before the barrier that follows exact_step,
+    // read here, after the commit's closing barrier.
+    if constexpr (kPf) {
+      pf_hit = uni(pfw[kPfRowT]) == t;
+      if (pf_hit) {
+        CTCX_LDS T* const r = cx.row;
+        cx.row = row2;
+        row2 = r;
+      }
+    }
+    if (kPf && pf_hit) {
+    } else
     if (sizeof(T) == 4 && prm.xfmt != kInNative) {   // uniform: half-precision rows, widened into the LDS row
       if constexpr (sizeof(T) == 4)
         stage_row_half((CTCX_LDS unsigned*)cx.row, (const uint16_t*)prm.x + xoff, C, prm.xfmt == kInF16, tid, NT);
@@ -5782,7 +5990,8 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
       if (tid == 4) cx.misc[kCtlExt] = 0;
       if (tid == 5) cx.misc[kCtlStop] = 0;
     }
-    const T norm = prm.norm[(int64_t)t * B + b];
+    // (a prefetched frame: its normaliser came with the row; kPf: T is float, a word)
+    const T norm = (kPf && pf_hit) ? ((CTCX_LDS T*)pfw)[kPfNorm] : prm.norm[(int64_t)t * B + b];
     if constexpr (BIG) {
       // the pre-pass record of row (t, b): header, block maxima, top set
       const char* pr = prm.prep + ((int64_t)t * B + b) * (int64_t)prep_row_bytes(C, (int)sizeof(T));
@@ -5833,6 +6042,23 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
         ring_flush<(WC > 0 ? WC : 512) / 64, RT, true>(rg, rstream, foff, pf_t, pf_lo, pf_hi, nullptr, 0, pf_fp, nrec);
         CTCX_HPC(cx, 29, CTCX_HTIME() - hf0);
       }
+#ifndef CTCX_GSTATE
+      if constexpr (kPf) {
+        // the helper, its ranks and flush done while wave 0 extracts: the next
+        // frame's row and normaliser into the buffer this frame does not read
+        // (literal_step and the commit read the current one or none), then the
+        // word that names the frame held.  Only after a frame in which the
+        // helper gathered, and for rows of T (half rows keep their row stage);
+        // row t + 1 exists only below the item's length.
+        if (helper_wave() && !prm.force_literal && !dup && nb >= W && t + 1 < sl && prm.xfmt == kInNative &&
+            ctl_ld(cx.misc, kCtlDead) == 0) {
+          const int64_t xoff1 = (int64_t)(t + 1) * prm.xst_t + (int64_t)b * prm.xst_b;
+          if (lane < C) row2[lane] = prm.x[xoff1 + lane];   // (C <= 64)
+          if (lane == 0) ((CTCX_LDS T*)pfw)[kPfNorm] = prm.norm[(int64_t)(t + 1) * B + b];
+          __hip_atomic_store(&pfw[kPfRowT], t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+#endif
       if constexpr (SQ && RN == 1 && kExtRank && (kExtBig || !BIG) && kExtLate)
         if (helper_wave()) help_rank_extract<T>(cx, (CTCX_LDS int*)gq.p);
       pf_t = -1;
@@ -7579,7 +7805,7 @@ hipError_t launch_decode_c(const DecodeParams<T>& p, hipStream_t s) {
   size_t lds = decode_lds_bytes(WC > 0 ? WC : p.W, p.C, (int)sizeof(T), SC::kStateful);
   if (HW)
     lds = ((lds + 15) & ~(size_t)15) + ((BIG || SQ) ? gq_lds_bytes(SQ, SQ ? sq_slots(WC) : kQSlots) : tab_lds_bytes()) +
-          ((SQ && !BIG) ? sq_ctab_bytes(WC, 0) : 0);
+          ((SQ && !BIG) ? sq_ctab_bytes(WC, 0) + sq_rowpf_bytes(p.C) : 0);
   if (p.ring > 0) lds = ((lds + 15) & ~(size_t)15) + ring_lds_bytes(p.ring, p.W, HW && !BIG ? 4 : 8);
   if (lds > kLdsBytes) return hipErrorInvalidValue;
 #ifdef CTCX_STREAM
@@ -7763,7 +7989,7 @@ size_t pre_ring_lds_bytes(const DecodeParams<T>& p, int hk, int wc) {
   const size_t b = (decode_lds_bytes(wc, p.C, (int)sizeof(T), p.scorer_tab != nullptr) + 15) & ~(size_t)15;
   return hk == 1   ? b + tab_lds_bytes()
          : hk == 2 ? b + gq_lds_bytes(false)
-         : hk == 3 ? b + gq_lds_bytes(true, sq_slots(wc)) + (p.C <= 64 ? sq_ctab_bytes(wc, (int)p.C) : 0)
+         : hk == 3 ? b + gq_lds_bytes(true, sq_slots(wc)) + (p.C <= 64 ? sq_ctab_bytes(wc, (int)p.C) + sq_rowpf_bytes(p.C) : 0)
                    : b;
 }
 // the two-wave kernel this call runs (0: none), given the kind the host chose
