@@ -84,6 +84,13 @@ static int helper_mode_from_env() {
          : hv[0] == '4' ? ctcx::kHelperScoredWide : ctcx::kHelperLegacy;
 }
 
+// CTCEXT_EARLY_RECURSE=0 (diagnostics; read at every launch): the helper wave
+// of the small-C scored kernel stages no recursion for the next frame
+static int32_t early_recurse_flag_from_env() {
+  const char* ev = getenv("CTCEXT_EARLY_RECURSE");
+  return (ev && ev[0] == '0') ? ctcx::kTestNoEarlyRecurse : 0;
+}
+
 #define HIP_OR_FAIL(expr)                                                             \
   do {                                                                                \
     hipError_t e_ = (expr);                                                           \
@@ -572,6 +579,7 @@ static int plan_shard(ctcext_decoder* d, Dev& v, bool root, const ctcext_decode_
   // all follow p.helper
   const int hk = gs ? 0 : ctcx::helper_kind<T>(p, helper_mode);
   p.test_flags = (a->flags & CTCEXT_FLAG_TEST_HELPER_DEAD) ? ctcx::kTestHelperDead : 0;
+  p.test_flags |= early_recurse_flag_from_env();
   // the record ring: asked for, or the default of the score-table two-wave kernel
   const bool ring = (a->flags & (CTCEXT_FLAG_RECORD_RING | CTCEXT_FLAG_RING_MIN)) ||
                     (!(a->flags & CTCEXT_FLAG_NO_RING) && ctcx::helper_rec32(hk, C));
@@ -802,9 +810,10 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
     d->stats.literal_fill += io[b].why_fill;
     d->stats.duplicate_frames += io[b].dup_frames;
     d->stats.records_written += io[b].records;
+    d->stats.early_recursed_frames += ctcx::item_early_frames(io[b]);
   }
   bool dead = false;
-  for (int64_t b = 0; b < B; ++b) dead |= io[b].pad != 0;
+  for (int64_t b = 0; b < B; ++b) dead |= (io[b].pad & ctcx::kItemDeadMask) != 0;
   if (dead) {
     // a two-wave kernel's hand-over wait ran out of time (~1 s; never in a
     // correct run): its items' results are incomplete.  The call is decoded
@@ -1175,6 +1184,7 @@ extern "C" int ctcext_dense_check(ctcext_decoder* d) {
     st.literal_fill += io[b].why_fill;
     st.duplicate_frames += io[b].dup_frames;
     st.records_written += io[b].records;
+    st.early_recursed_frames += ctcx::item_early_frames(io[b]);
     any |= status[b];
     if ((status[b] & CTCEXT_ITEM_LENGTH) && first_len < 0) first_len = b;
   }
@@ -1602,6 +1612,7 @@ static int stream_push_t(ctcext_stream* st, const ctcext_chunk* c, const std::ve
   p.log_prob = (T*)root.logp.p;
   p.prep = (const char*)st->prep.p;
   p.test_flags = (c->flags & CTCEXT_FLAG_TEST_HELPER_DEAD) ? ctcx::kTestHelperDead : 0;
+  p.test_flags |= early_recurse_flag_from_env();
   CtcxStreamParams sp{};
   sp.in = (const char*)st->state[st->cur];
   sp.out = (char*)st->state[st->cur ^ 1];
@@ -1641,7 +1652,7 @@ static int stream_push_t(ctcext_stream* st, const ctcext_chunk* c, const std::ve
 
   const ctcx::ItemOut* io = (const ctcx::ItemOut*)d->h_item.p;
   for (int64_t b = 0; b < B; ++b)
-    if (io[b].pad != 0)   // (the state buffers are not swapped: the stream stays at its pre-push state)
+    if ((io[b].pad & ctcx::kItemDeadMask) != 0)   // (the state buffers are not swapped: the stream stays at its pre-push state)
       return fail(CTCEXT_INTERNAL, "decode kernel: a helper-wave hand-over wait timed out");
   // the push is committed
   st->cur ^= 1;
@@ -1666,6 +1677,7 @@ static int stream_push_t(ctcext_stream* st, const ctcext_chunk* c, const std::ve
     d->stats.literal_fill += io[b].why_fill;
     d->stats.duplicate_frames += io[b].dup_frames;
     d->stats.records_written += io[b].records;
+    d->stats.early_recursed_frames += ctcx::item_early_frames(io[b]);
   }
   if (!sizes) return CTCEXT_OK;
   for (int64_t b = 0; b < B; ++b)
@@ -2026,6 +2038,7 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
   p.log_prob = (T*)n.logp.p;
   p.prep = (const char*)st->prep.p;
   p.test_flags = (c->flags & CTCEXT_FLAG_TEST_HELPER_DEAD) ? ctcx::kTestHelperDead : 0;
+  p.test_flags |= early_recurse_flag_from_env();
   CtcxStreamParams sp{};
   sp.in = committed;
   sp.out = other;
@@ -2168,6 +2181,7 @@ extern "C" int ctcext_stream_check(ctcext_stream* st) {
     sv.literal_fill += io[b].why_fill;
     sv.duplicate_frames += io[b].dup_frames;
     sv.records_written += io[b].records;
+    sv.early_recursed_frames += ctcx::item_early_frames(io[b]);
     any |= acc[b].status;
     if ((acc[b].status & CTCEXT_ITEM_LENGTH) && first_len < 0) first_len = b;
     if ((acc[b].status & CTCEXT_ITEM_CAPACITY) && first_cap < 0) first_cap = b;

@@ -2642,6 +2642,50 @@ constexpr bool kEarlyChunk0 = CTCX_EARLY_CHUNK0 != 0;
 __host__ __device__ constexpr size_t sq_rowpf_bytes(int64_t C) {
   return (kRowPrefetch && C <= 64) ? ((((size_t)C * 4) + 15) & ~(size_t)15) + 16 : 0;
 }
+// CTCX_EARLY_RECURSE (the same kernels; DESIGN, round 17): once its ranks are
+// out and row t + 1 is in the second row buffer, the helper computes frame
+// t + 1's recursion while wave 0 extracts.  The recursion of the branch at
+// position k needs that branch's words, its parent's and the row, not k: the
+// helper works on the final beam as wave 0 publishes it for the ranks (entry
+// j of the heap's copy: total xv[j], slot alias[j]), reads every source by
+// slot, and stages the nine RecNew fields per j, back-pointers as
+// (j << 1) | kind.  The commit, which knows each slot's position, moves the
+// staged words to e*[position] after its last read of e*[sorted[.]], and the
+// next frame's wave 0 skips recurse_wave0.
+// The staging area follows the second row buffer (so decode_lds_bytes and
+// ctcext_max_beam_width are what they were): four words (kErT: the frame the
+// staged words are for, -1: none), then ten planes of wcap words (kErNbk ..
+// kErLab: RecNew's fields; kErPos: the position of entry j, written by the
+// commit).  During the hand-over the gather queue's offer plane (dead between
+// the grow's end and the next frame) holds two maps: slot -> j (kErMapSlot,
+// enc words) and branch -> j of its surviving entry (kErMapBr, wcap words).
+#ifndef CTCX_EARLY_RECURSE
+#define CTCX_EARLY_RECURSE 1
+#endif
+constexpr bool kEarlyRecurse = CTCX_EARLY_RECURSE != 0 && kRowPrefetch && kEarlyChunk0;
+// CTCX_EARLY_BOTTOM: with the recursion in place at a frame's entry the helper
+// knows the starting bottom before it gathers (the smallest placed total).
+// 1: chunk 0 from -inf as before, chunk 1 without the wait for kCtlBot;
+// 2: chunk 0 gathered against the bottom too.  0: the wait as it was.
+// Both bit-exact, both measured slower than 0 in every pair (cfg3 112.8 ->
+// 113.3 / 114.0 ms per step, cfg2 41.64 -> 42.04 / 42.21, same box;
+// profiles/r17_ab_stages_cfg{3,2}.txt).  With the recursion gone wave 0
+// reaches its first-chunk wait as the helper publishes chunk 0 (the wait is 5
+// cycles per frame), and publishes kCtlBot at about the same moment, so the
+// helper's scan of the placed totals ahead of chunk 0 is on wave 0's chain
+// and the wait it removes is already short (no phase split of these two
+// builds was taken).  Off.
+#ifndef CTCX_EARLY_BOTTOM
+#define CTCX_EARLY_BOTTOM 0
+#endif
+constexpr int kEarlyBottom = kEarlyRecurse ? CTCX_EARLY_BOTTOM : 0;
+[[maybe_unused]] constexpr int kErT = 0;
+[[maybe_unused]] constexpr int kErNbk = 0, kErNl = 1, kErTot = 2, kErCb = 3, kErCn = 4, kErBpb = 5, kErBpn = 6,
+                               kErFlg = 7, kErLab = 8, kErPos = 9, kErPlanes = 10;
+[[maybe_unused]] constexpr int kErMapSlot = 0, kErMapBr = 512;   // (word offsets in the offer plane: 3 * 128 + 2 <= 512)
+__host__ __device__ constexpr size_t sq_stage_bytes(int wcap, int64_t C) {
+  return (kEarlyRecurse && C <= 64) ? 16 + (size_t)kErPlanes * (size_t)wcap * 4 : 0;
+}
 // Large C, beams of up to 256 (BIG kernels, WC > 0): GetChild through a
 // (parent, label) -> child hash table instead of a walk down the parent's
 // sibling list (up to one dependent LDS read pair per child of the branch:
@@ -2969,9 +3013,13 @@ constexpr int kSqCap0 = CTCX_SQ_CAP0;   // large C: offers in the frame's first 
 // that stays exact has finite totals only), or chunk 1 would be gathered
 // dense and wave 0 would pay for offers the true bottom rejects.  A frame
 // whose recursion gave a non-finite total ends that wait through kCtlDone.
-template <typename T, bool BIG, bool EARLY = false>
+// KNOWN (kEarlyRecurse, with EARLY): `known` is the frame's starting bottom
+// where the recursion was in place at the frame's entry (the smallest placed
+// total; -inf: not known, wait as above).  Chunk 1 is then gathered against it
+// without the wait for kCtlBot.
+template <typename T, bool BIG, bool EARLY = false, bool KNOWN = false>
 __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, int nb, T norm, T pmax,
-                                                   T bottom) {
+                                                   T bottom, [[maybe_unused]] T known = T(0)) {
   const int lane = threadIdx.x & 63;
   CTCX_LDS int* m = cx.misc;
   if (ctl_ld(m, kCtlDead) != 0) return;
@@ -2993,7 +3041,9 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
         break;
       }
       if (c < ctl_ld(m, kCtlCons) + (BIG ? 1 : kSqLead)) {
-        if constexpr (EARLY) {
+        if constexpr (EARLY && KNOWN) {
+          if (c == 0 || known > ninf<T>() || ctl_ld(m, kCtlBot) != (int)0xff800000u) break;
+        } else if constexpr (EARLY) {
           if (c == 0 || ctl_ld(m, kCtlBot) != (int)0xff800000u) break;
         } else {
           break;
@@ -3006,6 +3056,7 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
     // wave 0's bottom after its last chunk (it only rises)
     const T pb = (T)__builtin_bit_cast(float, (unsigned)ctl_ld(m, kCtlBot));
     bottom = pb > bottom ? pb : bottom;
+    if constexpr (KNOWN) bottom = (c > 0 && known > bottom) ? known : bottom;
 #ifdef CTCX_SQ_NOFILTER   // (diagnostics: every offer gathered, no closed turn found here)
     bottom = ninf<T>();
 #endif
@@ -3404,12 +3455,170 @@ __device__ __forceinline__ void recurse_wave0(const Ctx<T>& cx, int buf, int nb,
   wsync<true>();   // (one wave: its LDS operations execute in order)
 }
 
+// kEarlyRecurse: the next frame's recursion in slot space, on the helper,
+// while wave 0 extracts (DESIGN, round 17).  Called after help_rank_extract
+// and after the row prefetch, in a frame whose final heap wave 0 published
+// (kCtlExt == 1: xv[j], alias[j] for j < W): row (frame t + 1's, in the second
+// row buffer) and norm are the helper's own prefetch.  For entry j at slot
+// e = alias[j] it computes what recurse_rolled(i = the position the commit
+// gives j) computes next frame, from what the commit will put there:
+//   own words            et/eb/el/ecb/ecn/eflg/elab[e]      (put_branch)
+//   flags, parent entry  as parent_of forms them, by slot: a new child's parent
+//     is its source branch, a survivor's the branch par[buf][src], both present
+//     iff that branch's entry is in the final beam (mb: branch -> j); a
+//     survivor whose parent had left the beam finds it among the final beam's
+//     new children by prefix hash (the commit's re-entered parent)
+//   the parent's words   its entry's, eb/et/ecb/ecn/eflg/elab[alias[pj]]
+// Same expressions in the same order as recurse_rolled; back-pointers are
+// staged as (j << 1) | kind and translated to positions by the commit.
+// Reads only what stays as it is from the grow's end to the commit; writes
+// the staging planes and the two maps in the gather queue's offer plane.
+template <typename T, int WC>
+__device__ CTCX_HELPER_FN void help_early_recurse(CTCX_HCTX cx, int buf, const CTCX_LDS T* row, T norm,
+                                                  CTCX_LDS int* sp, CTCX_LDS int* maps) {
+  const int lane = threadIdx.x & 63;
+  const int W = cx.W;
+  const T NI = ninf<T>();
+  CTCX_LDS int* const ms = maps + kErMapSlot;
+  CTCX_LDS int* const mb = maps + kErMapBr;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // (the heap's copy, after kCtlExt)
+  // the maps, and each new child's prefix hash (in registers: the re-entered
+  // parent lookup compares across lanes)
+  mb[lane] = -1;
+  if (lane + 64 < WC) mb[lane + 64] = -1;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+  __builtin_amdgcn_wave_barrier();
+  int es[2], srcs[2];
+  bool isn[2];
+  uint64_t ca[2], cb2[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int j = lane + 64 * h;
+    const bool in = j < W;
+    const int e = in ? cx.alias[j] : 0;
+    const uint32_t kd = cx.ekind[e];
+    const int src = (int)(kd >> 1);
+    es[h] = e;
+    srcs[h] = src;
+    isn[h] = in && (kd & 1u);
+    ca[h] = sel(cx.ha, buf)[src];
+    cb2[h] = sel(cx.hb, buf)[src];
+    if (in) {
+      ms[e] = j;
+      if (!(kd & 1u)) mb[src] = j;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+  // parent entry (pj: its j, -1: none) and next-frame flags, as parent_of
+  int pjs[2], fls[2];
+  uint64_t pa[2] = {0, 0}, pb[2] = {0, 0};
+  bool need[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int j = lane + 64 * h;
+    const bool in = j < W;
+    const int e = es[h], src = srcs[h];
+    const int pf = sel(cx.flg, buf)[src];
+    const int pp = sel(cx.par, buf)[src];
+    int pj, fl;
+    need[h] = false;
+    if (isn[h]) {
+      pj = mb[src];
+      fl = (pf & F_ROOT) ? F_PROOT : 0;
+    } else {
+      pj = pp >= 0 ? mb[pp] : -1;
+      fl = pf & (F_ROOT | F_PROOT);
+      need[h] = in && pp < 0 && !(pf & F_ROOT);
+      if (need[h]) hmix_inv(ca[h], cb2[h], cx.elab[e], pa[h], pb[h]);
+    }
+    pjs[h] = pj;
+    fls[h] = fl | (cx.eflg[e] & (F_HB | F_HN));
+  }
+  // a new child's own hash (a survivor's stays its branch's)
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+    if (isn[h]) hmix(ca[h], cb2[h], cx.elab[es[h]], ca[h], cb2[h]);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    uint64_t m = __ballot(need[h]);
+    while (m) {   // (uniform: one re-entered-parent lookup per round)
+      const int l = (int)__builtin_ctzll(m);
+      m &= m - 1;
+      const uint64_t qa = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pa[h] >> 32), l) << 32) |
+                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pa[h], l);
+      const uint64_t qb = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pb[h] >> 32), l) << 32) |
+                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pb[h], l);
+      const uint64_t h0 = __ballot(isn[0] && ca[0] == qa && cb2[0] == qb);
+      const uint64_t h1 = __ballot(isn[1] && ca[1] == qa && cb2[1] == qb);
+      const int found = h0 ? (int)__builtin_ctzll(h0) : h1 ? 64 + (int)__builtin_ctzll(h1) : -1;
+      if (lane == l) pjs[h] = found;
+    }
+  }
+  // the recursion (recurse_rolled's expressions, sources by slot)
+  const T xb = row[cx.blank];
+  const T pbk = xb - norm;
+#pragma unroll 1
+  for (int h = 0; h < 2; ++h) {
+    const int j = lane + 64 * h;
+    if (j >= W) continue;
+    const int e = h ? es[1] : es[0];
+    const int f = h ? fls[1] : fls[0];
+    const int pj = h ? pjs[1] : pjs[0];
+    const int L = cx.elab[e];
+    const bool isroot = (f & F_ROOT) != 0;
+    const T o_t = cx.et[e];
+    const bool fresh = (o_t == NI);
+    const T rs_blank = (isroot || ((f & F_PROOT) && fresh)) ? T(0) : NI;
+    const T ocb = cx.ecb[e], ocn = cx.ecn[e];
+    T nl = cx.el[e];
+    Best<T> bn{T(0), kBpNone, false}, bb{T(0), kBpNone, false};
+    auto cand = [&](int sf, T scb, T scn, int sj, int kind, T p, T restart, Best<T>& best) {
+      const bool has = (sf & (kind == 0 ? F_HB : F_HN)) != 0;
+      const T base = has ? (kind == 0 ? scb : scn) : restart;
+      best.push(base + p, has ? (((uint32_t)sj << 1) | (uint32_t)kind) : kBpRestart);
+    };
+    if (!isroot) {
+      const T xl = row[L];
+      const T p = xl - norm;
+      if (pj >= 0) {
+        const int pe = cx.alias[pj];
+        const int pfl = cx.eflg[pe];
+        const T pcb = cx.ecb[pe], pcn = cx.ecn[pe];
+        const bool same = (L == cx.elab[pe]);
+        const T prev = same ? cx.eb[pe] : cx.et[pe];
+        nl = lse(nl, prev, cx.etab) + xl - norm;
+        cand(pfl, pcb, pcn, pj, 0, p, rs_blank, bn);
+        if (!same) cand(pfl, pcb, pcn, pj, 1, p, NI, bn);
+        cand(f, ocb, ocn, j, 1, p, NI, bn);
+      } else {
+        nl += xl - norm;
+        cand(f, ocb, ocn, j, 1, p, NI, bn);
+      }
+    }
+    const T nbk = o_t + xb - norm;
+    cand(f, ocb, ocn, j, 0, pbk, rs_blank, bb);
+    cand(f, ocb, ocn, j, 1, pbk, NI, bb);
+    const T tot = lse(nbk, nl, cx.etab);
+    sp[kErNbk * WC + j] = (int)__float_as_uint(nbk);
+    sp[kErNl * WC + j] = (int)__float_as_uint(nl);
+    sp[kErTot * WC + j] = (int)__float_as_uint(tot);
+    sp[kErCb * WC + j] = (int)__float_as_uint(bb.p);
+    sp[kErCn * WC + j] = (int)__float_as_uint(bn.p);
+    sp[kErBpb * WC + j] = (int)bb.bp;
+    sp[kErBpn * WC + j] = (int)bn.bp;
+    sp[kErFlg * WC + j] = (bb.ok ? F_HB : 0) | (bn.ok ? F_HN : 0);
+    sp[kErLab * WC + j] = L;
+  }
+}
+
 #ifdef CTCX_SQ_CHECK
 __shared__ int g_sq_dbg[8];   // (diagnostics: the first scored-field mismatch)
 #endif
 template <typename T, int RN, bool BIG, class SC, bool HW, bool SQ>
 __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, bool last, int P, int* n_out,
-                          int* n_leaves, PhaseCtr pc, Tab tb, GQ gq, bool setm_in = false) {
+                          int* n_leaves, PhaseCtr pc, Tab tb, GQ gq, bool setm_in = false, bool er_hit = false) {
   // SQ: the scored gather queue (two-wave kernels, beams <= 128, any C): with
   // the beam full, every chunk of the grow comes from the helper scored
   static_assert(!SQ || (HW && (RN == 1 || (RN == 2 && BIG))), "SQ kernels");
@@ -3460,7 +3669,14 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   //                                  wave 0   wave 1
   //   bad row (return 1 above)         0        0
   //   early path (nb >= W)             0        0     <- neither runs the two below
+  //   ... its recursion in place       0        0     (kEarlyRecurse, er_hit: wave 0 skips
+  //                                                    recurse_wave0, which has no barrier)
   //   every other path                 2        2
+  // kEarlyRecurse adds no barrier and no wait anywhere: the helper stages
+  // between its ranks and the barrier that follows exact_step in the frame
+  // loop, the commit places between two of its own barriers, and both read
+  // their go-ahead (erw[kErT], er_place, er_hit) as workgroup-uniform values
+  // written before a barrier both waves have passed.
   // A non-finite total on the early path: wave 0 returns 1 alone; the helper,
   // already in its loop, leaves through the kCtlDone the kernel stores next.
   constexpr bool kEc0 = kEarlyChunk0 && HW && SQ && !BIG && RN == 1 && sizeof(T) == 4 && !SC::kStateful;
@@ -3469,7 +3685,26 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   if (kEc0 && early) {
     if constexpr (kEc0) {
       if (helper_wave()) {
-        help_gather_scored<T, BIG, true>(cx, gq, buf, nb, norm, pmax, NI);
+        if constexpr (kEarlyBottom > 0) {
+          // (er_hit: the placed totals are this frame's leaves, so their
+          // minimum is the starting bottom wave 0 will publish; a total that
+          // is not finite sends wave 0 to the literal path, and kCtlDone ends
+          // the gather.  Form 1: chunk 0 from -inf as before, chunk 1 without
+          // the wait; form 2: chunk 0 from the bottom as well.)
+          T b0 = NI;
+          if (er_hit) {
+            T lm = pinf<T>();
+            for (int i = lane; i < nb; i += 64) {
+              const T v = cx.et[i];
+              lm = v < lm ? v : lm;
+            }
+            lm = wave_min(lm);
+            b0 = (lm > NI && lm < pinf<T>()) ? lm : NI;
+          }
+          help_gather_scored<T, BIG, true, true>(cx, gq, buf, nb, norm, pmax, kEarlyBottom == 2 ? b0 : NI, b0);
+        } else {
+          help_gather_scored<T, BIG, true>(cx, gq, buf, nb, norm, pmax, NI);
+        }
         if constexpr (kExtRank && !kExtLate) {
           [[maybe_unused]] const uint64_t hr0 = CTCX_HTIME();
           help_rank_extract<T>(cx, (CTCX_LDS int*)gq.p, buf);
@@ -3477,7 +3712,9 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
         }
         return 0;   // the kernel takes wave 0's result
       }
-      recurse_wave0<T, SC>(cx, buf, nb, norm);
+      // (kEarlyRecurse, er_hit: the last commit put this frame's recursion in
+      // place, from the helper's staging; uniform over the workgroup)
+      if (!(kEarlyRecurse && er_hit)) recurse_wave0<T, SC>(cx, buf, nb, norm);
     }
   } else {
     // roll (decoder.h:87-92) + recursion (decoder.h:95-143), threads over branches
@@ -4964,6 +5201,26 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
       if (lane == 0) __hip_atomic_store(&cx.misc[kCtlExt], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   }
+  // kEarlyRecurse: a full beam whose grow accepted no push never makes the
+  // heap (st stays kTopBottomKnown: the W leaves in branch order, the smallest
+  // in front), so the helper has nothing to rank -- but it can still recurse
+  // the next frame from them.  The same copy, under kCtlExt 3: not ranked
+  // (help_rank_extract returns on any value but 1), staged from.
+  if constexpr (kExt && kEarlyRecurse && kEc0) {
+    if (!ext_rank && st == kTopBottomKnown && full && n == W && W >= kExtMinW) {
+      CTCX_LDS float* xv = (CTCX_LDS float*)cx.newpos;
+#pragma unroll
+      for (int k0 = 0; k0 < 128; k0 += 64) {
+        const int k = k0 + lane;
+        if (k < W) {
+          xv[k] = (float)he[k + 1].v;
+          cx.alias[k] = he[k + 1].s;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      if (lane == 0) __hip_atomic_store(&cx.misc[kCtlExt], 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
   // the grow is over: the helper stops scoring.  Released (LDS only): the
   // helper's acquire after it reads kCtlDone then sees kCtlExt and the copy
   if constexpr (HW) {
@@ -5788,6 +6045,9 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
 #endif
   [[maybe_unused]] CTCX_LDS T* row2 = nullptr;
   [[maybe_unused]] CTCX_LDS int* pfw = nullptr;
+  // kEarlyRecurse (the same kernels): the staging area of the helper's recursion
+  constexpr bool kEr = kEarlyRecurse && kPf;
+  [[maybe_unused]] CTCX_LDS int* erw = nullptr;
 #ifndef CTCX_GSTATE
   {
     size_t off = (decode_lds_bytes(WC > 0 ? WC : W, C, (int)sizeof(T), SC::kStateful) + 15) & ~(size_t)15;
@@ -5808,6 +6068,11 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
         row2 = (CTCX_LDS T*)((CTCX_LDS char*)lds + off);
         pfw = (CTCX_LDS int*)((CTCX_LDS char*)lds + off + sq_rowpf_bytes(C) - 16);
         off += sq_rowpf_bytes(C);
+      }
+      if constexpr (kEr) {   // the staged recursion (sq_stage_bytes): four words, then the planes
+        static_assert(WC == 128 && sq_slots(WC) * 64 * 4 >= kErMapBr + WC && kErMapBr >= 3 * WC + 2, "the maps' room");
+        erw = (CTCX_LDS int*)((CTCX_LDS char*)lds + off);
+        off += sq_stage_bytes(WC, C);
       }
     }
     if (R > 0) rg = ring_carve<RT>((CTCX_LDS char*)lds + off, R, W);
@@ -5847,7 +6112,8 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     if (tid == 0) {
       ItemOut io;
       io.n_leaves = hin.n_leaves; io.literal_steps = hin.literal_steps; io.dup_frames = hin.dup_frames;
-      io.why_nonfinite = hin.why_nonfinite; io.why_fill = hin.why_fill; io.pad = 0; io.records = hin.records;
+      io.why_nonfinite = hin.why_nonfinite; io.why_fill = hin.why_fill; io.pad = kEr ? (hin.pad[0] << 1) : 0;
+      io.records = hin.records;
       prm.item[b] = io;
     }
     return;
@@ -5871,6 +6137,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     cx.misc[kCtlDead] = (HW && (prm.test_flags & kTestHelperDead)) ? 1 : 0;
     cx.misc[15] = 0;
     if constexpr (kPf) pfw[kPfRowT] = -1;   // no row held: a prefetch never crosses a launch (a stream's push)
+    if constexpr (kEr) erw[kErT] = -1;      // ... nor does a staged recursion
 #ifdef CTCX_STREAM
   }
   // (the per-launch words above are set after the load; the rest of Reset()
@@ -5905,8 +6172,13 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
   bool tiefree = false;  // the previous frame's beam had no tie (kSetMode)
   bool dup = false;   // this frame's beam holds an entry twice (literal frames only)
   int n_leaves = 1;
+  // kEarlyRecurse: this frame's recursion is in place already (the last commit
+  // moved the helper's staged words there), and the item's count of such frames
+  [[maybe_unused]] bool er_hit = false;
+  [[maybe_unused]] int early_rec = 0;
 #ifdef CTCX_STREAM
   if (resume) {   // the scalars a frame hands to the next, and the item's counters so far
+    if constexpr (kEr) early_rec = uni(hin.pad[0]);
     buf = uni(hin.buf); nb = uni(hin.nb); dup = uni(hin.dup) != 0; tiefree = uni(hin.tiefree) != 0;
     n_leaves = uni(hin.n_leaves); literal_steps = uni(hin.literal_steps); dup_frames = uni(hin.dup_frames);
     why_nf = uni(hin.why_nonfinite); why_fill = uni(hin.why_fill); nrec_all = (int64_t)uni64((uint64_t)hin.records);
@@ -6026,7 +6298,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
 #ifndef CTCX_GSTATE   // the global-state tier replays every frame literally
     if (!prm.force_literal && !dup)
       why = exact_step<T, RN, BIG, SC, HW, SQ>(cx, buf, nb, norm, last, prm.P, &n, &nl_fast, prof ? pc : PhaseCtr{nullptr}, tb, gq,
-                                               pass == 0 && tiefree);
+                                               pass == 0 && tiefree, kEr && er_hit);
 #endif
     if constexpr (HW) {
       // wave 0's result for both waves; the helper stops if the grow ended
@@ -6056,6 +6328,25 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
           if (lane < C) row2[lane] = prm.x[xoff1 + lane];   // (C <= 64)
           if (lane == 0) ((CTCX_LDS T*)pfw)[kPfNorm] = prm.norm[(int64_t)(t + 1) * B + b];
           __hip_atomic_store(&pfw[kPfRowT], t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+          // kEarlyRecurse: frame t + 1's recursion from the final beam, in the
+          // rest of wave 0's extract (help_early_recurse).  The row and norm it
+          // reads are the two stores above (one wave: its LDS operations
+          // execute in order).  Only where wave 0 published the final heap
+          // (kCtlExt == 1: the frame's grow ran to its end on the heap); erw's
+          // word names the frame like kPfRowT, and is read after the barrier
+          // below, so the helper adds no wait of its own.
+          if constexpr (kEr) {
+            const int ext = ctl_ld(cx.misc, kCtlExt);   // (1: the final heap; 3: a beam no push changed)
+            if (!(prm.test_flags & kTestNoEarlyRecurse) && (ext == 1 || ext == 3)) {
+              [[maybe_unused]] const uint64_t he0 = CTCX_HTIME();
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+              __builtin_amdgcn_wave_barrier();
+              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+              help_early_recurse<T, WC>(cx, buf, row2, ((CTCX_LDS T*)pfw)[kPfNorm], erw + 4, (CTCX_LDS int*)gq.a);
+              __hip_atomic_store(&erw[kErT], t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+              CTCX_HPC(cx, 23, CTCX_HTIME() - he0);   // (wave 0 leaves counter 23 alone in this kernel)
+            }
+          }
         }
       }
 #endif
@@ -6088,6 +6379,15 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     __syncthreads();
     uint64_t t2 = prof ? __builtin_amdgcn_s_memtime() : 0;
     const bool ok = (why == 0);
+    // kEarlyRecurse: the helper staged the next frame's recursion from this
+    // frame's final beam (its word, written before the barrier above, names
+    // frame t + 1), and the frame stayed on the exact path: the commit below
+    // moves the staged words into place.  Uniform over the workgroup.
+    [[maybe_unused]] bool er_place = false;
+    if constexpr (kEr) {
+      early_rec += (er_hit && ok) ? 1 : 0;
+      er_place = ok && uni(erw[kErT]) == t + 1;
+    }
     why_nf += (why == 1); why_fill += (why == 2);
     dup_frames += dup ? 1 : 0;
     bool dup_next = false;
@@ -6142,6 +6442,17 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
       if (!dup_next) cx.alias[k] = k;
       else if (cx.alias[k] != k) continue;
       if (!(kd & 1u)) cx.newpos[kd >> 1] = k;
+    }
+    // kEarlyRecurse: the position of each staged entry (slot -> j is the
+    // helper's map in the gather queue's offer plane, untouched until the next
+    // frame's first chunk)
+    [[maybe_unused]] int erj = 0;   // (n <= WC == NT: position tid is this thread's only one)
+    if constexpr (kEr) {
+      static_assert(!kEr || WC == NT, "one position per thread");
+      if (er_place && tid < n) {
+        erj = ((CTCX_LDS int*)gq.a)[kErMapSlot + cx.sorted[tid]] & (WC - 1);
+        erw[4 + kErPos * WC + erj] = tid;
+      }
     }
     for (int q = tid; q < cx.hts; q += NT) cx.htab[q] = -1;
     __syncthreads();
@@ -6255,6 +6566,32 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     }
     if (R > 0 && tid == 0) rg.rn[t & (R - 1)] = n;
     __syncthreads();
+    // kEarlyRecurse: the staged recursion into place, as recurse_store would
+    // leave entry k next frame.  Every read of e*[sorted[.]] above is behind
+    // the barrier; nothing below reads an e* array, bst or bloom.  The two
+    // back-pointers name entries by j: through the position map.
+    if constexpr (kEr) {
+      er_hit = er_place;
+      if (er_place) {
+        const CTCX_LDS int* sp = erw + 4;
+        if (tid < n) {
+          const int k = tid, j = erj;
+          uint32_t qb = (uint32_t)sp[kErBpb * WC + j], qn = (uint32_t)sp[kErBpn * WC + j];
+          if (qb < kBpRestart) qb = ((uint32_t)sp[kErPos * WC + ((qb >> 1) & (WC - 1))] << 1) | (qb & 1u);
+          if (qn < kBpRestart) qn = ((uint32_t)sp[kErPos * WC + ((qn >> 1) & (WC - 1))] << 1) | (qn & 1u);
+          cx.eb[k] = __uint_as_float((uint32_t)sp[kErNbk * WC + j]);
+          cx.el[k] = __uint_as_float((uint32_t)sp[kErNl * WC + j]);
+          cx.et[k] = __uint_as_float((uint32_t)sp[kErTot * WC + j]);
+          cx.ecb[k] = __uint_as_float((uint32_t)sp[kErCb * WC + j]); cx.ebpb[k] = qb;
+          cx.ecn[k] = __uint_as_float((uint32_t)sp[kErCn * WC + j]); cx.ebpn[k] = qn;
+          cx.eflg[k] = sp[kErFlg * WC + j];
+          cx.ekind[k] = ((uint32_t)k << 1);
+          cx.elab[k] = sp[kErLab * WC + j];
+          cx.bst[k] = 0;
+          cx.bloom[k] = 0;
+        }
+      }
+    }
     buf = nx;
     nb = n;
     dup = dup_next;
@@ -6364,6 +6701,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     ho.buf = buf; ho.nb = nb; ho.dup = dup ? 1 : 0; ho.tiefree = tiefree ? 1 : 0;
     ho.n_leaves = n_leaves; ho.literal_steps = literal_steps; ho.dup_frames = dup_frames;
     ho.why_nonfinite = why_nf; ho.why_fill = why_fill; ho.records = nrec_all;
+    if constexpr (kEr) ho.pad[0] = early_rec;
     *(CtcxStreamHdr*)st_out = ho;
   }
 #ifndef CTCX_GSTATE
@@ -6402,6 +6740,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
 #endif
     // HW kernels: a hand-over wait that gave up (the host fails the call)
     io.pad = HW ? __hip_atomic_load(&cx.misc[kCtlDead], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+    if constexpr (kEr) io.pad = (io.pad & 1) | (early_rec << 1);   // (item_early_frames)
     prm.item[b] = io;
   }
 }
@@ -7757,7 +8096,7 @@ __global__ __launch_bounds__(256) void ctcx_pack_dense(PackDenseParams pp) {
   const int p = (int)(bpp - b * pp.P);
   const int64_t T_ = pp.Tmax;
   int32_t st = pp.pre[b];
-  if (pp.item[b].pad != 0) st |= kItemHelperTimeout;
+  if ((pp.item[b].pad & kItemDeadMask) != 0) st |= kItemHelperTimeout;
   if (!(st & (kItemLength | kItemTable)) && pp.item[b].n_leaves < pp.P) st |= kItemFewLeaves;
   int64_t n = st ? 0 : pp.len[((int64_t)p * 2 + w) * pp.B + b];
   n = n < 0 ? 0 : n > T_ ? T_ : n;
@@ -7805,7 +8144,7 @@ hipError_t launch_decode_c(const DecodeParams<T>& p, hipStream_t s) {
   size_t lds = decode_lds_bytes(WC > 0 ? WC : p.W, p.C, (int)sizeof(T), SC::kStateful);
   if (HW)
     lds = ((lds + 15) & ~(size_t)15) + ((BIG || SQ) ? gq_lds_bytes(SQ, SQ ? sq_slots(WC) : kQSlots) : tab_lds_bytes()) +
-          ((SQ && !BIG) ? sq_ctab_bytes(WC, 0) + sq_rowpf_bytes(p.C) : 0);
+          ((SQ && !BIG) ? sq_ctab_bytes(WC, 0) + sq_rowpf_bytes(p.C) + sq_stage_bytes(WC, p.C) : 0);
   if (p.ring > 0) lds = ((lds + 15) & ~(size_t)15) + ring_lds_bytes(p.ring, p.W, HW && !BIG ? 4 : 8);
   if (lds > kLdsBytes) return hipErrorInvalidValue;
 #ifdef CTCX_STREAM
@@ -7989,7 +8328,7 @@ size_t pre_ring_lds_bytes(const DecodeParams<T>& p, int hk, int wc) {
   const size_t b = (decode_lds_bytes(wc, p.C, (int)sizeof(T), p.scorer_tab != nullptr) + 15) & ~(size_t)15;
   return hk == 1   ? b + tab_lds_bytes()
          : hk == 2 ? b + gq_lds_bytes(false)
-         : hk == 3 ? b + gq_lds_bytes(true, sq_slots(wc)) + (p.C <= 64 ? sq_ctab_bytes(wc, (int)p.C) + sq_rowpf_bytes(p.C) : 0)
+         : hk == 3 ? b + gq_lds_bytes(true, sq_slots(wc)) + (p.C <= 64 ? sq_ctab_bytes(wc, (int)p.C) + sq_rowpf_bytes(p.C) + sq_stage_bytes(wc, p.C) : 0)
                    : b;
 }
 // the two-wave kernel this call runs (0: none), given the kind the host chose

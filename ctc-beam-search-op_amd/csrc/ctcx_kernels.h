@@ -138,6 +138,18 @@ struct ItemOut {
   int64_t records;        // records written to HBM (all of them without the record ring; T * W can pass 2^31)
 };
 static_assert(sizeof(ItemOut) == 32, "ItemOut layout");
+// CTCX_EARLY_RECURSE (ctcx_decode.hip; the small-C scored two-wave kernels):
+// ItemOut.pad keeps the hand-over's timeout in bit 0 and carries, in the bits
+// above it, the item's frames whose recursion came from the helper wave
+// (ctcext_stats.early_recursed_frames; a stream's header keeps the running
+// count in CtcxStreamHdr.pad[0]).  With the macro 0 the word is what it was.
+#ifndef CTCX_EARLY_RECURSE
+#define CTCX_EARLY_RECURSE 1
+#endif
+constexpr int32_t kItemDeadMask = CTCX_EARLY_RECURSE ? 1 : -1;
+__host__ __device__ inline int64_t item_early_frames(const ItemOut& io) {
+  return CTCX_EARLY_RECURSE ? (int64_t)((uint32_t)io.pad >> 1) : 0;
+}
 
 // Large C (> 64): per-(t, b) row facts computed by the parallel pre-pass
 // ctcx_row_prep before the decode kernel, which would otherwise derive them
@@ -212,6 +224,8 @@ struct DecodeParams {
 // element formats of x (= CTCEXT_IN_*)
 constexpr int32_t kInNative = 0, kInF16 = 1, kInBF16 = 2;
 constexpr int32_t kTestHelperDead = 1;
+// (diagnostics, CTCEXT_EARLY_RECURSE=0 in the environment at launch: the helper stages no recursion)
+constexpr int32_t kTestNoEarlyRecurse = 2;
 // helper_kind's modes and the record size of a two-wave kernel kind (4-byte
 // Rec32 records: the score table, and the scored queue at C <= 64)
 // (kHelperScoredWide: the scored queue for beams of 129..256 too -- measured

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kNT) void ctcx_stream_commit(CtcxStreamCommitParams
   char* const dst = p.committed + b * p.stride;
   const char* const src = p.written + b * p.stride;
   __shared__ int32_t s_bad;
-  if (tid == 0) s_bad = p.item[b].pad;
+  if (tid == 0) s_bad = p.item[b].pad & ctcx::kItemDeadMask;
   __syncthreads();
   const int32_t bad = s_bad;
   int32_t frames, n_leaves;

@@ -151,7 +151,8 @@ class Stats(ctypes.Structure):
                 ("traceback_ms", ctypes.c_double), ("n_devices", ctypes.c_int32),
                 ("tier", ctypes.c_int32), ("ring_frames", ctypes.c_int32),
                 ("records_written", ctypes.c_int64), ("record_bytes", ctypes.c_int32),
-                ("helper", ctypes.c_int32), ("helper_redecodes", ctypes.c_int32), ("kernel", ctypes.c_int32)]
+                ("helper", ctypes.c_int32), ("helper_redecodes", ctypes.c_int32), ("kernel", ctypes.c_int32),
+                ("early_recursed_frames", ctypes.c_int64)]
 
 
 # ctcext_stats.kernel (include/ctcext.h, CTCEXT_KERNEL_*)

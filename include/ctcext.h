@@ -85,7 +85,8 @@ enum {
  *      ctcext_phase_counters' layout is [batch][32]
  *   7: ctcext_decode_args.inputs_format, .inputs_stride_t, .inputs_stride_b
  *      (appended; zero = the dense [max_time, batch, num_classes] tensor of dtype)
- *   8: ctcext_stats.kernel (the former pad_: same size and offsets) */
+ *   8: ctcext_stats.kernel (the former pad_: same size and offsets);
+ *      ctcext_stats.early_recursed_frames (appended: ctcext_get_stats_sized) */
 #define CTCEXT_ABI_VERSION 8
 
 typedef struct ctcext_decoder ctcext_decoder;
@@ -178,6 +179,10 @@ typedef struct {
   int32_t kernel;                  /* last decode, root device: the kernels its launchers ran
                                       (CTCEXT_KERNEL_* below); after ctcext_row_facts, the
                                       pre-pass field alone */
+  int64_t early_recursed_frames;   /* last decode: frames, summed over items, whose recursion
+                                      the helper wave computed during the frame before (the
+                                      small-C scored two-wave kernel; a stream's count is
+                                      cumulative, like its other counters) */
 } ctcext_stats;
 
 /* ctcext_stats.kernel.  Each launcher records what it launched, so the value

@@ -78,6 +78,9 @@ if m[31] > 0:
 if sq_small:
     print("  helper first chunk: entry to control words read %.0f, scan step %.0f, publish %.0f cycles/frame"
           % (m[16] / fr, m[17] / fr, m[18] / fr))
+    # (counter 23 in these kernels: the helper's recursion of the next frame, CTCX_EARLY_RECURSE)
+    print("  helper early recursion %.0f cycles/frame; early-recursed frames %d of %d"
+          % (m[23] / fr, d.last_stats.get("early_recursed_frames", 0), B * T))
 if os.environ.get("CTCX_DIAG_EXTP"):   # (a build with -DCTCX_PHASE_EXTP: the extract's stop)
     h = buf[:, 27].astype(np.uint64)
     cnt = [int(((h >> np.uint64(16 * k)) & np.uint64(0xFFFF)).sum()) for k in range(4)]
