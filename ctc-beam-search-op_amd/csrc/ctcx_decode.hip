@@ -45,6 +45,7 @@
 
 #include "ctcx_kernels.h"
 #include "ctcx_topn.h"
+#include "ctcx_regsort.h"
 #include "glibc_math.h"
 #include "glibc_math_f64.h"
 
@@ -3613,6 +3614,107 @@ __device__ CTCX_HELPER_FN void help_early_recurse(CTCX_HCTX cx, int buf, const C
   }
 }
 
+// CTCX_REG_SORT: Extract()'s std::sort (a beam no push changed this frame, or
+// one that is not full yet) over two wave registers instead of lane 0's
+// literal replay over LDS -- ctcx_regsort.h, in the one-node float LDS-tier
+// kernels.  0: lit_sort as before.
+#ifndef CTCX_REG_SORT
+#define CTCX_REG_SORT 1
+#endif
+#if CTCX_REG_SORT && !defined(CTCX_GSTATE)
+// ctcx_regsort.h's lane array over VGPRs: position p is lane p & 63 of
+// r[p >> 6]; every index and every value that crosses lanes is wave-uniform
+struct WaveLanes {
+  int r0, r1, aux;
+  CTCX_LDS int* out;   // the result, by position
+  __device__ __forceinline__ unsigned get(int p) const {
+    return (unsigned)(p < 64 ? bcast(r0, p) : bcast(r1, p - 64));
+  }
+  __device__ __forceinline__ void set(int p, unsigned v) {
+    if (p < 64) r0 = writelane(r0, (int)v, p);
+    else r1 = writelane(r1, (int)v, p - 64);
+  }
+  __device__ __forceinline__ uint64_t below(int reg, unsigned x) const {
+    return __ballot((unsigned)(reg ? r1 : r0) < x);
+  }
+  __device__ __forceinline__ uint64_t above(int reg, unsigned x) const {
+    return __ballot((unsigned)(reg ? r1 : r0) > x);
+  }
+  // The stable placement (ctcx_regsort.h): position p's element goes to its
+  // key plus the number of equal keys below p.  x = key << 8 | p; for a lower
+  // position q with the same key, x_q - (key << 8) = q < p, and for any other
+  // key the difference is negative (wraps) or at least 256.
+  __device__ __forceinline__ void finish(int n) {
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned key0 = (unsigned)r0 >> 16, key1 = (unsigned)r1 >> 16;
+    const unsigned b0 = key0 << 8, b1 = key1 << 8;
+    const int x0 = (int)(b0 | lane), x1 = (int)(b1 | (lane + 64));
+    unsigned c0 = 0, c1 = 0;
+    // (eight lanes a round; a position at or past n holds 0xFFFFFFFF, whose
+    // x never comes out below 256 more than a member's base)
+    const int n0 = n < 64 ? (n + 7) & ~7 : 64, n1 = (n + 7) & ~7;
+    for (int q = 0; q < n0; q += 8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const unsigned xq = (unsigned)bcast(x0, q + u);
+        c0 += xq - b0 < lane ? 1u : 0u;
+        c1 += xq - b1 < lane + 64 ? 1u : 0u;
+      }
+    }
+    for (int q = 64; q < n1; q += 8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) c1 += (unsigned)bcast(x1, q + u - 64) - b1 < lane + 64 ? 1u : 0u;
+    }
+    const unsigned d0 = key0 + c0, d1 = key1 + c1;   // (< n for keys that are ranks: checked all the same)
+    if (lane < (unsigned)n && d0 < (unsigned)n) out[d0] = r0 & 0xFFFF;
+    if (lane + 64 < (unsigned)n && d1 < (unsigned)n) out[d1] = r1 & 0xFFFF;
+  }
+  __device__ __forceinline__ unsigned aux_get(int i) const { return (unsigned)bcast(aux, i); }
+  __device__ __forceinline__ void aux_set(int i, unsigned v) { aux = writelane(aux, (int)v, i); }
+};
+
+// std::sort of he[1..n]'s slots by their current totals into sorted[0..n), in
+// registers; false (nothing stored): a NaN total or the sort's depth limit --
+// the caller runs lit_sort.  Wave 0, all lanes; 1 <= n <= 128.
+template <typename T>
+__device__ __forceinline__ bool reg_sort_extract(const Ctx<T>& cx, const CTCX_LDS HE<T>* he, int n) {
+  static_assert(sizeof(T) == 4, "float totals");
+  const int lane = threadIdx.x & 63;
+  const bool in0 = lane < n, in1 = lane + 64 < n;
+  const int s0 = in0 ? he[lane + 1].s : 0, s1 = in1 ? he[lane + 65].s : 0;
+  // (the comparator's operand: the slot's current total; past n: NaN, which
+  // no comparison below counts)
+  const T t0 = in0 ? cx.et[s0] : __builtin_nanf(""), t1 = in1 ? cx.et[s1] : __builtin_nanf("");
+  if (__ballot((in0 && t0 != t0) || (in1 && t1 != t1))) return false;
+  // key: the number of elements with a strictly greater total (eight lanes a
+  // round: the rounds past n read NaN)
+  int k0 = 0, k1 = 0;
+  const int n0 = n < 64 ? (n + 7) & ~7 : 64, n1 = (n + 7) & ~7;
+  for (int j = 0; j < n0; j += 8) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const T tj = bcast(t0, j + u);
+      k0 += tj > t0 ? 1 : 0;
+      k1 += tj > t1 ? 1 : 0;
+    }
+  }
+  for (int j = 64; j < n1; j += 8) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const T tj = bcast(t1, j + u - 64);
+      k0 += tj > t0 ? 1 : 0;
+      k1 += tj > t1 ? 1 : 0;
+    }
+  }
+  WaveLanes l;
+  l.r0 = in0 ? (k0 << 16 | s0) : -1;
+  l.r1 = in1 ? (k1 << 16 | s1) : -1;
+  l.aux = 0;
+  l.out = cx.sorted;
+  return rs_sort(l, n);
+}
+#endif
+
 #ifdef CTCX_SQ_CHECK
 __shared__ int g_sq_dbg[8];   // (diagnostics: the first scored-field mismatch)
 #endif
@@ -5416,10 +5518,30 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
     for (int k = lane; k < nout; k += 64) cx.sorted[k] = he[k + 1].s;
   } else {
     nout = n;
-    if (lane == 0) {
+#ifdef CTCX_PHASES   // (the std::sort frames and their cycles: the upper halves of counters 7 and 11)
+    const uint64_t tq0 = pc ? __builtin_amdgcn_s_memtime() : 0;
+#endif
+    bool placed = false;
+#if CTCX_REG_SORT && !defined(CTCX_GSTATE)
+    // in registers (all lanes store, as the sort_heap branch does); he is
+    // untouched, so a frame it gives up on is sorted the literal way below.
+    // Small C only: at large C nearly every frame accepts a push, so the
+    // branch is rare there, and with it compiled in cfg4 measured 0.7% slower
+    // (placement; profiles/r18_ab_reg_sort.txt).
+    if constexpr (RN == 1 && sizeof(T) == 4 && !BIG) {
+      if (n >= 1 && n <= 128) placed = reg_sort_extract<T>(cx, he, n);
+    }
+#endif
+    if (!placed && lane == 0) {
       for (int q = 0; q < n; ++q) cx.sorted[q] = he[q + 1].s;
       lit_sort(cx.sorted, n, SlotGreater<T>{cx.et});
     }
+#ifdef CTCX_PHASES
+    if (pc) {
+      pc[11] += (__builtin_amdgcn_s_memtime() - tq0) << 32;
+      pc[7] += 1ull << 32;
+    }
+#endif
   }
   wsync<HW>();
   if (last && lane == 0) {

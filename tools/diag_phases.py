@@ -27,6 +27,12 @@ buf = np.zeros((B, NPH), np.uint64)
 rc = d.lib.ctcext_phase_counters(d.handle, ctypes.c_void_p(buf.ctypes.data), B * NPH)
 if rc != 0:
     sys.exit("ctcext_phase_counters failed (%d): %s" % (rc, d.lib.ctcext_last_error().decode()))
+# the extract's std::sort frames (a beam no push changed, or one not full yet):
+# their count rides in the upper half of counter 7, their cycles in counter 11's
+sort_fr = (buf[:, 7] >> np.uint64(32)).astype(np.float64)
+sort_cy = (buf[:, 11] >> np.uint64(32)).astype(np.float64)
+buf[:, 7] &= np.uint64(0xFFFFFFFF)
+buf[:, 11] &= np.uint64(0xFFFFFFFF)
 m = buf.astype(np.float64).mean(0)
 fr = m[7]
 names = ["rowload", "recursion", "grow", "extract", "commit", "literal", "heap events", "frames",
@@ -54,6 +60,23 @@ for b in o[-3:][::-1]:
     print("    item %d: heap events %.0f/frame, extract %.0f, grow %.0f, eventloop %.0f, scoring %.0f" % (
         b, buf[b, 6] / fr, buf[b, 3] / fr, buf[b, 2] / fr, buf[b, 9] / fr, buf[b, 8] / fr))
 print("  mean heap events/frame %.1f, max %.1f" % (buf[:, 6].mean() / fr, buf[:, 6].max() / fr))
+# Extract() = std::sort: how many frames per item, what one costs, and what
+# is left of the extract phase per sort_heap pop (W pops in every other frame)
+if sort_fr.sum() > 0:
+    ext = buf[:, 3].astype(np.float64)
+    pops = (buf[:, 7].astype(np.float64) - sort_fr) * W
+    print("  std::sort frames per item: mean %.1f min %.0f max %.0f of %.0f; %.0f cycles per sort (mean),"
+          " %.0f cycles/frame over all frames, %.1f%% of the extract phase"
+          % (sort_fr.mean(), sort_fr.min(), sort_fr.max(), fr, sort_cy.sum() / sort_fr.sum(),
+             sort_cy.mean() / fr, 100.0 * sort_cy.sum() / max(1.0, ext.sum())))
+    print("  extract without the sorts: %.0f cycles/frame, %.1f per sort_heap pop"
+          % ((ext - sort_cy).mean() / fr, (ext - sort_cy).sum() / max(1.0, pops.sum())))
+    items = list(o[-3:][::-1]) + [int(v) for v in os.environ.get("CTCX_DIAG_ITEMS", "").split(",") if v and int(v) < B]
+    for b in items:
+        print("    item %d: %.0f sort frames, %.0f cycles per sort, %.0f sort cycles/frame (mean item %.0f);"
+              " all phases %.0f cycles/frame (mean item %.0f)"
+              % (b, sort_fr[b], sort_cy[b] / max(1.0, sort_fr[b]), sort_cy[b] / fr, sort_cy.mean() / fr,
+                 tot[b] / fr, tot.mean() / fr))
 # two-wave kernels (cfg2/cfg3 class): the score-table wait and where the waves ran
 if True:
     print("  HW table / queue wait %.0f cycles/frame, %.2f s_sleep rounds/frame (after the first chunk: %.0f cycles)"
