@@ -2872,6 +2872,218 @@ __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, i
   }
 }
 
+// CTCX_SPARSE_BRANCH (DESIGN, round 19): pass 1 of the sparse gather below with
+// one BRANCH per lane instead of one offer per lane.  The want test
+//   (row[l] - norm) + (l == bl ? bob : bt) > bottom
+// has one operand that is the same for every branch (row[l] - norm) and three
+// that a lane can hold for the whole frame, so a window of 64 branches is
+// tested in C - 1 iterations of a few VALU instructions each, with no
+// division and no LDS gather, where the offer-per-lane form needs C - 1 scan
+// steps for the same 64 * (C - 1) offers.  The result per branch is a mask of
+// wanted label indices; popcounts and a prefix over the lanes place each
+// lane's wanted offers in the chunk.  The staged words, their order, cqn,
+// gstop and the resume point are those of the scan-step form for the same
+// (i0, li0, bottom) (tests/test_cpu_branch_gather.py restates both): the
+// resume point is that form's, step-granular, computed from the linear offer
+// index x = (i - i0) * (C - 1) + li.
+#ifndef CTCX_SPARSE_BRANCH
+#define CTCX_SPARSE_BRANCH 1
+#endif
+constexpr bool kSparseBranch = CTCX_SPARSE_BRANCH != 0;
+// The frame's branches as the helper holds them, lane b of window w branch
+// 64 * w + b (beams <= 128: two windows), from the frame-start arrays.
+template <typename T>
+struct SqBr {
+  T pv;             // lane l < C: row[l] - norm
+  T bt[2];          // the branch's total
+  T sl[2];          // the score of its own label's offer: (row[bl] - norm) + bob
+  int li[2];        // its own label as a label index (-1: none)
+  uint64_t cm[2];   // its children's labels, as label indices (wanted whatever the bottom)
+};
+__device__ __forceinline__ uint64_t lowmask_any(int n) { return n <= 0 ? 0ull : lowmask(n); }
+// inclusive prefix sum over the wave's lanes: DPP row shifts inside each row
+// of 16, then the row totals by readlane
+__device__ __forceinline__ int wave_incl_sum_dpp(int v) {
+  v += dpp_i<0x111>(v, 0);   // row_shr:1
+  v += dpp_i<0x112>(v, 0);   // row_shr:2
+  v += dpp_i<0x114>(v, 0);   // row_shr:4
+  v += dpp_i<0x118>(v, 0);   // row_shr:8
+  const int r0 = bcast(v, 15), r1 = bcast(v, 31), r2 = bcast(v, 47);
+  const int row = (int)(threadIdx.x & 63) >> 4;
+  return v + (row == 0 ? 0 : row == 1 ? r0 : row == 2 ? r0 + r1 : r0 + r1 + r2);
+}
+template <typename T, bool CT>
+__device__ __forceinline__ void sq_br_load(const Ctx<T>& cx, int buf, int nb, T norm, const GQ& gq, SqBr<T>& S) {
+  const int lane = threadIdx.x & 63;
+  const int C = cx.C, blank = cx.blank;
+  S.pv = cx.row[lane < C ? lane : 0] - norm;
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const int i = 64 * w + lane;
+    const bool v = i < nb;
+    const int ii = v ? i : 0;
+    const int bl = sel(cx.lab, buf)[ii];
+    const T bob = sel(cx.ob, buf)[ii];
+    const bool own = bl >= 0 && bl < C && bl != blank;
+    S.bt[w] = sel(cx.ot, buf)[ii];
+    S.li[w] = own ? bl - (bl > blank ? 1 : 0) : -1;
+    S.sl[w] = (cx.row[own ? bl : 0] - norm) + bob;
+    uint64_t cm = 0;
+    if constexpr (CT) {   // the children table holds them by label: drop the blank's bit
+      const uint64_t m = v ? gq.cmask[ii] : 0ull;
+      cm = (m & lowmask(blank)) | ((blank >= 63 ? 0ull : (m >> (blank + 1))) << blank);
+    } else
+    for (int k = v ? cx.head[ii] : -1; __ballot(k >= 0);) {
+      CTCX_HPC(cx, 27, 1);
+      if (k >= 0) {
+        const int lk = sel(cx.lab, buf)[k];
+        if (lk >= 0) cm |= 1ull << ((lk - (lk > blank ? 1 : 0)) & 63);
+        k = cx.sib[k];
+      }
+    }
+    S.cm[w] = cm;
+  }
+}
+// window w's wanted label indices per branch at this bottom: the same float
+// expression per offer as sq_score's (contraction off)
+template <typename T>
+__device__ __forceinline__ uint64_t sq_br_want(const SqBr<T>& S, int w, int Cm1, int blank, T bottom) {
+  const T bt = w ? S.bt[1] : S.bt[0];
+  uint32_t lo = 0, hi = 0;
+  const int n0 = Cm1 < 32 ? Cm1 : 32;
+  for (int li = 0; li < n0; ++li) {
+    const T s = bcast(S.pv, li + (li >= blank ? 1 : 0)) + bt;
+    lo |= (s > bottom) ? (1u << li) : 0u;
+  }
+  for (int li = 32; li < Cm1; ++li) {
+    const T s = bcast(S.pv, li + (li >= blank ? 1 : 0)) + bt;
+    hi |= (s > bottom) ? (1u << (li - 32)) : 0u;
+  }
+  uint64_t M = ((uint64_t)hi << 32) | lo;
+  const int lib = w ? S.li[1] : S.li[0];   // the branch's own label: its label-ending total instead
+  if (lib >= 0) {
+    const uint64_t b = 1ull << lib;
+    M = (M & ~b) | (((w ? S.sl[1] : S.sl[0]) > bottom) ? b : 0ull);
+  }
+  return M | (w ? S.cm[1] : S.cm[0]);
+}
+// One window: its wanted masks with the span's start and the first closed turn
+// applied (kbr: that branch's lane, 64: none; a turn is closed only if it
+// starts inside the scan).
+template <typename T>
+__device__ __forceinline__ uint64_t sq_br_window(const SqBr<T>& S, int w, int nb, int Cm1, int blank, T bottom, int i0,
+                                                  int li0, int& kbr) {
+  const int i = 64 * w + (int)(threadIdx.x & 63);
+  const bool v = i >= i0 && i < nb;
+  uint64_t M = sq_br_want<T>(S, w, Cm1, blank, bottom);
+  M = v ? M : 0ull;
+  if (i == i0) M &= ~lowmask(li0);
+  const uint64_t cM = __ballot(v && !((w ? S.bt[1] : S.bt[0]) > bottom) && (i > i0 || li0 == 0));
+  kbr = cM ? (int)__builtin_ctzll(cM) : 64;
+  return (int)(threadIdx.x & 63) >= kbr ? 0ull : M;
+}
+// Pass 1 of gather_small_sparse in that form: stages the chunk's packed words
+// at sc[0 .. cqn) and moves (i0, li0) to the resume point.
+template <typename T, bool CT>
+__device__ __forceinline__ void gather_small_branch(const Ctx<T>& cx, int buf, int nb, T bottom, int& i0, int& li0,
+                                                    bool& gstop, CTCX_LDS uint32_t* sc, int& cqn, const GQ& gq,
+                                                    const SqBr<T>& S) {
+  const int lane = threadIdx.x & 63;
+  const int Cm1 = cx.C - 1, blank = cx.blank;
+  cqn = 0;
+  if (i0 >= nb) return;
+  const int xend = (nb - i0) * Cm1;   // offers from branch i0's first to the frame's last
+  int xres = 0;                       // the resume point as an offer index from branch i0's first
+  for (int w = i0 >> 6;; ++w) {
+    CTCX_HPC(cx, 31, 1);
+    const int i = 64 * w + lane;
+    const int xs = (i - i0) * Cm1;   // the branch's first offer
+    int kbr;
+    uint64_t R = sq_br_window<T>(S, w, nb, Cm1, blank, bottom, i0, li0, kbr);
+    const int cnt = (int)__builtin_popcountll(R);
+    const int inc = wave_incl_sum_dpp(cnt);
+    const int tot = bcast(inc, 63);
+    const int room = 64 - cqn;
+    // the lane's wanted offers that fit, lowest label first, at the chunk
+    // positions after those of the lanes below
+    int pos = cqn + inc - cnt;
+    int t = room - (inc - cnt);
+    t = t < 0 ? 0 : t > cnt ? cnt : t;
+    const uint64_t tM = __ballot(t > 0);
+    int lastli = 0;
+    while (__ballot(t > 0)) {
+      const bool on = t > 0;
+      const int li = on ? (int)__builtin_ctzll(R) : 0;
+      const int l = li + (li >= blank ? 1 : 0);
+      const bool ch = on && (((w ? S.cm[1] : S.cm[0]) >> li) & 1ull);
+      int cw = -1;
+      if constexpr (CT) {
+        if (ch) cw = gq.ctab[i * 64 + l];
+      } else if (__ballot(ch)) {   // GetChild: the first child of that label in the sibling list
+        for (int k = ch ? cx.head[i] : -1; __ballot(k >= 0);) {
+          CTCX_HPC(cx, 27, 1);
+          int nk = -1;
+          if (k >= 0) {
+            const int lk = sel(cx.lab, buf)[k];
+            const int sk = cx.sib[k];
+            if (lk == l) cw = k;
+            else nk = sk;
+          }
+          k = nk;
+        }
+      }
+      if (on) {
+        sc[pos] = sq_pack(i, cw, l);
+        R &= R - 1ull;
+        lastli = li;
+        ++pos;
+        --t;
+      }
+    }
+    if (tot >= room) {
+      // the chunk fills at offer x64, in the scan step [hi - 64, hi).  A wanted
+      // offer left in that step (before a turn closed in it): the step-wise
+      // form resumes after x64; none: it passes over the step's rest, up to
+      // the closed turn.  The step may run on into the next window.
+      const int L = 63 - (int)__builtin_clzll(tM);
+      const int x64 = bcast(xs + lastli, L);
+      const int hi = li0 + ((x64 - li0) & ~63) + 64;
+      bool more = __ballot((R & lowmask_any(hi - xs)) != 0ull) != 0ull;
+      int xstop = kbr < 64 ? bcast(xs, kbr) : hi;
+      if (!more && kbr == 64 && 64 * (w + 1) < nb && (64 * (w + 1) - i0) * Cm1 < hi) {
+        CTCX_HPC(cx, 31, 1);
+        int kbr2;
+        const uint64_t R2 = sq_br_window<T>(S, w + 1, nb, Cm1, blank, bottom, i0, li0, kbr2);
+        const int xs2 = xs + 64 * Cm1;
+        more = __ballot((R2 & lowmask_any(hi - xs2)) != 0ull) != 0ull;
+        if (kbr2 < 64) xstop = bcast(xs2, kbr2);
+      }
+      xstop = xstop < hi ? xstop : hi;
+      cqn = 64;
+      if (more) {
+        xres = x64 + 1;
+      } else {
+        xres = xstop;
+        gstop = xstop < hi;
+      }
+      break;
+    }
+    cqn += tot;
+    if (kbr < 64) {   // a closed turn ends the frame's grow before it
+      xres = bcast(xs, kbr);
+      gstop = true;
+      break;
+    }
+    if (64 * (w + 1) >= nb) {   // the last step ran past the frame's last offer
+      xres = li0 + ((xend - li0 + 63) & ~63);
+      break;
+    }
+  }
+  const int qr = xres / Cm1;
+  i0 += qr;
+  li0 = xres - qr * Cm1;
+}
+
 // The same chunk in two passes, for the chunks after the frame's first: those
 // are sparse (cfg3, T = 1500: ~6.5 scan steps of 64 offers per chunk of up to
 // 64), and gather_small_scored scores every scanned offer in full before it
@@ -2888,7 +3100,8 @@ __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, i
 template <typename T, bool CT = false>
 __device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, int nb, T norm, T bottom, int& i0,
                                                     int& li0, bool& gstop, CTCX_LDS u32x4* qa, CTCX_LDS float* qp,
-                                                    int& cqn, const GQ& gq) {
+                                                    int& cqn, const GQ& gq,
+                                                    [[maybe_unused]] const SqBr<T>* br = nullptr) {
   const int lane = threadIdx.x & 63;
   const int Cm1 = cx.C - 1, blank = cx.blank;
   const float rcp = 1.0f / (float)Cm1;
@@ -2896,6 +3109,9 @@ __device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, i
   cqn = 0;
   const int sp_i0 = i0;
   const bool sp_mid = li0 != 0;
+  if constexpr (kSparseBranch) {   // pass 1 with a branch per lane
+    gather_small_branch<T, CT>(cx, buf, nb, bottom, i0, li0, gstop, sc, cqn, gq, *br);
+  } else
   while (cqn < 64 && i0 < nb) {   // pass 1: filter
     CTCX_HPC(cx, 31, 1);
     const int x = li0 + lane;
@@ -2993,11 +3209,15 @@ __device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, i
 
 // The scored gather queue's helper (SQ kernels): as help_gather_chunks, up to
 // kSqLead chunks ahead of wave 0, each chunk's offers scored (sq_score).
-// small C: two ahead (cfg3 decode 124.9 -> 123.4 ms, same box); large C: one
-// (two costs cfg4 +1.6%: chunks gathered against older bottoms carry more
-// offers wave 0 then rejects)
+// small C: one ahead since the branch-per-lane filter (kSparseBranch; round
+// 19: with the gather cheap the helper no longer needs the head start, and
+// chunks gathered against a fresher bottom carry fewer offers wave 0 then
+// rejects: cfg3 106.05 -> 105.39 ms per step, cfg2 39.65 -> 39.32, every
+// pair, profiles/r19_ab_lead.txt; with the scan-step filter two ahead won,
+// cfg3 decode 124.9 -> 123.4 ms, and a -DCTCX_SPARSE_BRANCH=0 build keeps
+// two); large C: one (two costs cfg4 +1.6%, for the same reason)
 #ifndef CTCX_SQ_LEAD
-#define CTCX_SQ_LEAD 2
+#define CTCX_SQ_LEAD (CTCX_SPARSE_BRANCH != 0 ? 1 : 2)
 #endif
 #ifndef CTCX_SQ_FIRST1
 #define CTCX_SQ_FIRST1 1
@@ -3030,9 +3250,14 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
   int i0 = 0, li0 = 0, cbr = -1;
   bool gstop = false;
   [[maybe_unused]] const uint64_t hg0 = CTCX_HTIME();
+  [[maybe_unused]] SqBr<T> br;
   for (int c = 0;; ++c) {
     bool done = false;
     uint64_t tw = 0;
+    // (kSparseBranch: the frame's branches into registers ahead of the first
+    // sparse chunk, beside the wait for wave 0's starting bottom)
+    if constexpr (!BIG && kSparseBranch)
+      if (c == (kSqFirst1 ? 1 : 0)) sq_br_load<T, kCtab>(cx, buf, nb, norm, q, br);
     [[maybe_unused]] const uint64_t hw0 = CTCX_HTIME();
     for (int spin = 0;; ++spin) {   // the grow still running, and wave 0 at most kSqLead chunks behind
       if (ctl_ld(m, kCtlDone) != 0) { done = true; break; }
@@ -3070,6 +3295,10 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
     int cqn = 0;
     CTCX_LDS u32x4* qa = q.a + slot * 64;
     CTCX_LDS float* qp = q.p + slot * 64;
+#if defined(CTCX_PHASE_LATE) && defined(CTCX_PHASES)   // (this chunk's scan steps or window passes: counter 31 before and after)
+    const bool hlate = cx.prof && threadIdx.x == 64;
+    const uint64_t hst0 = hlate ? __hip_atomic_load(cx.prof + 31, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+#endif
     if constexpr (BIG) {
       // the compacted (branch, label index) entries go to the slot's value
       // array first; each lane then scores its entry and overwrites its own
@@ -3105,6 +3334,7 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
       // scored as it is scanned.  The later chunks are sparse: filtered, then
       // scored (gather_small_sparse).
       if (kSqFirst1 && c == 0) gather_small_scored<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, true, q);
+      else if constexpr (kSparseBranch) gather_small_sparse<T, kCtab>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, q, &br);
       else gather_small_sparse<T, kCtab>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, q);
     }
     [[maybe_unused]] const uint64_t hs2 = CTCX_HTIME();
@@ -3122,6 +3352,11 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
       CTCX_HPC(cx, 18, CTCX_HTIME() - hs2);
     }
     CTCX_HPC(cx, 30, 1);
+#if defined(CTCX_PHASE_LATE) && defined(CTCX_PHASES)
+    if (hlate)
+      CTCX_HPC_(cx, kPhLateSteps + (c < 15 ? c : 15),
+                __hip_atomic_load(cx.prof + 31, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - hst0);
+#endif
     if (cqn == 0 || gstop) break;   // the last chunk of the frame
   }
   CTCX_HPC(cx, 24, CTCX_HTIME() - hg0);
@@ -3999,8 +4234,15 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
                 (void)uni((int)h0);
                 pc[19] += __builtin_amdgcn_s_memtime() - tq0;
                 pc[20] += spins;
+#ifdef CTCX_PHASE_LATE   // (how late the chunk was: from this ask to wave 0 seeing it published)
+                pc[kPhLateWait + (gqc < 15 ? gqc : 15)] += __builtin_amdgcn_s_memtime() - tq0;
+                pc[kPhLateCnt + (gqc < 15 ? gqc : 15)] += 1;
+#endif
               }
             }
+#ifdef CTCX_PHASE_LATE
+            if (pc) pc[kPhLateAsk + (gqc < 15 ? gqc : 15)] += 1;
+#endif
           }
           __asm__ volatile("" ::: "memory");
           ++gqc;

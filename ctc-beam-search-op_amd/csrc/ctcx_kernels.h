@@ -69,7 +69,16 @@ namespace ctcx {
 // 3 extract, 4 commit, 5 literal frames, 6 grow events, 7 frames, 8 offer
 // scoring, 9 event loops, 10 heap pushes, 11 offer chunks, 12 accepted
 // events, 13 heap pushes (count)
+#ifdef CTCX_PHASE_LATE
+// (diagnostics of the scored queue's later chunks, by chunk index 0..15, the
+// last one collecting every later chunk: [32, 48) times wave 0 asked for the
+// chunk, [48, 64) cycles it then waited for it, [64, 80) the helper's scan
+// steps or window passes spent on it, [80, 96) times wave 0 had to wait)
+constexpr int kPhaseN = 96;
+constexpr int kPhLateAsk = 32, kPhLateWait = 48, kPhLateSteps = 64, kPhLateCnt = 80;
+#else
 constexpr int kPhaseN = 32;   // [0, 24): wave 0, [24, 32): the helper wave (CTCX_PHASES)
+#endif
 
 constexpr uint32_t kBpRestart = 0xFFFFFFFEu;  // candidate started a new chain
 constexpr uint32_t kBpNone = 0xFFFFFFFFu;     // no candidate of that kind

@@ -8,7 +8,13 @@ build alone times make_heap, in counter 23).
 
 Counter 14 is wave 0's wait for the frame's first chunk (a part of the queue
 wait, counter 19), printed once.  In the small-C scored kernels the gather
-counters 16..18 are the helper's first chunk in three spans."""
+counters 16..18 are the helper's first chunk in three spans.
+
+CTCX_DIAG_LATE=1, with a phases build that adds -DCTCX_PHASE_LATE
+(tools/build_variant.sh name "-DCTCX_PHASE_LATE" phases): the scored queue's
+later chunks by chunk index -- wave 0's asks, how often and for how long the
+chunk was late, the helper's scan steps or window passes spent on it.
+CTCX_DIAG_BRANCH=0 names counter 31 for a -DCTCX_SPARSE_BRANCH=0 build."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ctc-beam-search-op_amd"))
 import numpy as np
@@ -23,6 +29,14 @@ ctcext_amd.ctc_ext_beam_search_decoder(x, sl, W, P, merge_repeated=True, flags=f
 out = ctcext_amd.ctc_ext_beam_search_decoder(x, sl, W, P, merge_repeated=True, flags=f)
 d = ctcext_amd.get_decoder(0)
 NPH = 32   # ctcx_kernels.h kPhaseN: [0, 24) wave 0, [24, 32) the helper wave
+LATE = bool(os.environ.get("CTCX_DIAG_LATE"))   # (a build with -DCTCX_PHASE_LATE: 64 more, by chunk index)
+if LATE:
+    NPH = 96
+# the small-C helper's later chunks: filtered a branch per lane (the default
+# build, CTCX_SPARSE_BRANCH=1: counter 31 counts window passes, plus the first
+# chunk's one scan step) or an offer per lane (CTCX_DIAG_BRANCH=0 for a build
+# with -DCTCX_SPARSE_BRANCH=0: scan steps)
+BRANCH = os.environ.get("CTCX_DIAG_BRANCH", "1") != "0"
 buf = np.zeros((B, NPH), np.uint64)
 rc = d.lib.ctcext_phase_counters(d.handle, ctypes.c_void_p(buf.ctypes.data), B * NPH)
 if rc != 0:
@@ -93,11 +107,28 @@ hn = {24: "helper gather (whole)", 25: "helper to first chunk", 26: "helper wait
       28: "helper rank extract", 29: "helper ring flush"}
 for k, name in hn.items():
     print("  %-26s %10.0f cycles/frame" % (name, m[k] / fr))
-print("  helper chunks %.2f/frame, scan steps %.2f/frame, child-walk steps %.2f/frame"
-      % (m[30] / fr, m[31] / fr, m[27] / fr))
+step_name = "window passes (and the first chunk's scan step)" if (sq_small and BRANCH) else "scan steps"
+print("  helper chunks %.2f/frame, %s %.2f/frame, child-walk steps %.2f/frame"
+      % (m[30] / fr, step_name, m[31] / fr, m[27] / fr))
 if m[31] > 0:
     busy = m[24] - m[26]
-    print("  helper busy (gather minus waits for wave 0) %.0f cycles/frame, %.0f per scan step" % (busy / fr, busy / m[31]))
+    print("  helper busy (gather minus waits for wave 0) %.0f cycles/frame, %.0f per %s" % (
+        busy / fr, busy / m[31], "window pass or scan step" if (sq_small and BRANCH) else "scan step"))
+if LATE:
+    # wave 0's scored-chunk loop asks for chunk k (the kCtlReady test): how often, how
+    # often the helper had not published it yet, and for how long wave 0 then slept
+    print("  later chunks by index (the last row: every chunk from 15 on); cycles per frame over all frames")
+    print("    chunk  asked/frame  late/frame  wait cycles/frame  wait per late ask  helper %s/frame"
+          % ("passes" if BRANCH else "steps"))
+    for k in range(16):
+        ask, wait, steps, cnt = m[32 + k], m[48 + k], m[64 + k], m[80 + k]
+        if ask == 0 and steps == 0:
+            continue
+        # (chunk 0 goes by the generic chunk path, which is not stamped: its wait is
+        # the first-chunk wait above)
+        print("    %5d  %11.3f  %10.3f  %17.0f  %17.0f  %14.2f" % (
+            k, ask / fr, cnt / fr, wait / fr, wait / max(1.0, cnt), steps / fr))
+    print("    all    %11.3f  %10.3f  %17.0f" % (m[32:48].sum() / fr, m[80:96].sum() / fr, m[48:64].sum() / fr))
 if sq_small:
     print("  helper first chunk: entry to control words read %.0f, scan step %.0f, publish %.0f cycles/frame"
           % (m[16] / fr, m[17] / fr, m[18] / fr))
