@@ -6,12 +6,36 @@
 // cpu_baseline leg may load it.  The product path (ctc-beam-search-op_amd/)
 // never links, loads or calls it.
 //
-// Pinning: the reference (TF custom op) is unbuildable in this image (it needs
-// TensorFlow and Eigen headers that are not installed), so this restatement is
-// pinned by the reference's own golden vector — the Graves-paper example in
-// python/ops/ctc_ext_beam_search_decoder_ops_test.py:20-100 — checked by
-// tests/test_oracle_golden.py, for T=float and T=double.  Every other parity
-// case is pinned only through this restatement.
+// Pinning: the reference op itself needs TensorFlow, but its decoder is
+// header-only (util/*.h) and uses a handful of TensorFlow/Eigen names.
+// oracle/ref compiles those headers in place, untouched, against small
+// stand-in headers and a driver that does what kernels.cc:54-90 does, into
+// oracle/_ref/libctc_ref.so (oracle/reference.py; never committed).  This
+// restatement is pinned to that build:
+//   * tests/golden/reference_cases.json records the reference's outputs for
+//     about 120 cases (every kernel route's shape, both dtypes, ties, -inf, the
+//     duplicate-entry state, paths without alignment, both TopPaths errors,
+//     the whole float range); tests/test_oracle_reference.py holds both modes
+//     of this file to them bit for bit, anywhere, and where the library is
+//     present sweeps ~3500 random items live against it;
+//   * the fixtures the GPU tests trust (full_length.json's cfg3 cases, two of
+//     large_vocab.json's) were recomputed with the reference and found equal;
+//   * the reference's own golden vector, the Graves-paper example in
+//     python/ops/ctc_ext_beam_search_decoder_ops_test.py:20-100, is checked
+//     against this file (tests/test_oracle_golden.py) and run through the
+//     reference build, for T=float and T=double.
+// What stays pinned by reading only:
+//   * gtl::TopN's rules (TensorFlow's source is not at hand: the stand-in
+//     top_n.h is the same restatement as BoundedTop below, so the build
+//     cannot contradict it);
+//   * the bigram scorer: the reference's AddAlignmentCandidate takes
+//     BeamEntry<T>*, so its decoder cannot be instantiated with a scorer that
+//     has state, and only BaseBeamScorer is built;
+//   * the op around the decoder: input validation and the SparseTensor
+//     packing of StoreAllDecodedSequences (kernels.cc:97-257);
+//   * NaN and +inf logits (the stand-in row maximum is Eigen's only without
+//     NaN); the full-length cfg4/cfg5 fixtures, which the reference's
+//     allocation of every child of every branch puts out of reach.
 //
 // What is restated, with the reference lines it follows
 // (paths relative to tensorflow_ctc_ext_beam_search_decoder/cc/):

@@ -7,7 +7,9 @@ whose outputs differ.  Inputs are drawn exactly as bench.make_inputs draws them
 (numpy default_rng(20251015 + rank), float32 [T, B, C] ~ N(0, 1), seq_len = T)
 for ranks 0..7 of cfg2, cfg3 and cfg4; cfg5's logits are drawn on the device
 by torch (30.7 GB) and have no fixture.  The oracle (shared mode, the
-restatement pinned by the reference's golden vector, test.py:20-100) decodes
+restatement pinned to a compiled build of the reference's headers,
+tests/test_oracle_reference.py; rank 0 of cfg2 was recomputed with that build
+and has this digest, make_reference_fixtures.py group C) decodes
 the batch in item shards over worker processes; the items are independent
 (kernels.cc:68-90) and the SparseTensor packing (kernels.cc:163-257) is done
 once over the whole batch.

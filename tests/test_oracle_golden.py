@@ -1,5 +1,12 @@
-"""Pins the CPU oracle (test infrastructure) to the reference's only golden
-vector: python/ops/ctc_ext_beam_search_decoder_ops_test.py:20-100."""
+"""The CPU oracle (test infrastructure) against the reference's only golden
+vector, python/ops/ctc_ext_beam_search_decoder_ops_test.py:20-100, and
+against itself: its two modes, the shared mode's node economy, the scorer
+hook, the bench digests.
+
+That vector is one item (T=8, C=3, W=10, no ties, 1e-6): it does not notice,
+for one, an LSE computed in double.  What pins the oracle to the reference is
+tests/test_oracle_reference.py: recorded outputs of a compiled build of the
+reference's own headers (oracle/ref), and a live sweep against that build."""
 import json
 import os
 
