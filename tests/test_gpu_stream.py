@@ -26,7 +26,11 @@ LITERAL = _lib.CTCEXT_FLAG_FORCE_LITERAL
 DEAD = _lib.CTCEXT_FLAG_TEST_HELPER_DEAD
 NP = {"f32": np.float32, "f64": np.float64}
 KINDS = {"normal": dict(merge_repeated=False, blank_index=0),
-         "ties": dict(merge_repeated=True, blank_index=None)}   # (None: C // 2, a non-zero blank)
+         "ties": dict(merge_repeated=True, blank_index=None),   # (None: C // 2, a non-zero blank)
+         # -inf logits: literal and duplicate frames on both sides of a push (the
+         # census of test_gpu_stream_matrix.py holds the oracle to decoding
+         # every compared prefix of these inputs without an error)
+         "neg_inf": dict(merge_repeated=True, blank_index=0)}
 # the whole float range (tests/range_inputs.py), test_family_chunked_numeric_range
 RANGE_KINDS = {"logsoftmax": dict(merge_repeated=True, blank_index=None),
                "edges": dict(merge_repeated=False, blank_index=0)}
@@ -102,7 +106,9 @@ def _aligned_chunks(x, sl, pushes):
 def test_family_chunked_matches_oracle(name, kind, monkeypatch):
     """1. Every kernel family's stream build: pushes of 1, 1, 1, 1, 5 and the
     rest; after the 1st, 4th, 5th and last the result is the oracle's of the
-    prefix, and the kernel that ran is the family's, as a stream build."""
+    prefix, and the kernel that ran is the family's, as a stream build.  The
+    kinds: N(0,1) logits, logits on a grid of halves (ties), and N(0,1) with
+    15% of the logits -inf."""
     _chunked_family(name, kind, monkeypatch)
 
 
@@ -115,17 +121,24 @@ def test_family_chunked_numeric_range(name, kind, monkeypatch):
     _chunked_family(name, kind, monkeypatch)
 
 
+def _family_case(name, kind):
+    """(x [T, 3, C], the items' lengths, the decode attributes, the bigram
+    table or None) of one family and kind."""
+    (T, C, W, P), dtype, scorer, env, flags, row = FAMILIES[name]
+    rng = np.random.default_rng(zlib.crc32(("%s/%s" % (name, kind)).encode()))
+    x = _inputs(rng, kind, T, 3, C, NP[dtype])
+    sl = np.array([T, T - 3, T // 2], np.int32)
+    tab = (-np.abs(rng.standard_normal((C + 1, C))) * 2).astype(NP[dtype]) if scorer == "bigram" else None
+    return x, sl, _kw(kind, C), tab
+
+
 def _chunked_family(name, kind, monkeypatch):
     (T, C, W, P), dtype, scorer, env, flags, row = FAMILIES[name]
     _set_helper(monkeypatch, env)
-    rng = np.random.default_rng(zlib.crc32(("%s/%s" % (name, kind)).encode()))
     B = 3
-    x = _inputs(rng, kind, T, B, C, NP[dtype])
-    sl = np.array([T, T - 3, T // 2], np.int32)
+    x, sl, kw, tab = _family_case(name, kind)
     if kind in RANGE_KINDS:
         range_inputs.assert_census(kind, np.concatenate([x[:n, b] for b, n in enumerate(sl)]))
-    kw = _kw(kind, C)
-    tab = (-np.abs(rng.standard_normal((C + 1, C))) * 2).astype(NP[dtype]) if scorer == "bigram" else None
     with ctcext_amd.StreamDecoder(B, C, W, P, T, dtype=NP[dtype], scorer_table=tab, flags=flags, **kw) as s:
         for i, (t1, chunk, ln) in enumerate(_aligned_chunks(x, sl, PUSHES)):
             check = i in CHECK_AFTER
