@@ -23,14 +23,26 @@
 //   * the reference's own golden vector, the Graves-paper example in
 //     python/ops/ctc_ext_beam_search_decoder_ops_test.py:20-100, is checked
 //     against this file (tests/test_oracle_golden.py) and run through the
-//     reference build, for T=float and T=double.
+//     reference build, for T=float and T=double;
+//   * the bigram scorer (expand_state / expansion_score below).  The
+//     reference's AddAlignmentCandidate takes BeamEntry<T>*, so its decoder
+//     cannot be instantiated with a scorer state type; the driver instead
+//     gives it a scorer over the default EmptyBeamState that keeps each
+//     state's cached value in a side table keyed by the state object's address
+//     (ref_driver.cpp says why that names one entry between two
+//     InitializeState calls, and counts what would show otherwise).
+//     tests/golden/reference_scorer_cases.json records what the reference
+//     gave under continuous, tie-making, bigram-forbidding and extreme tables
+//     (83 cases); test_oracle_reference.py holds both modes of this file to
+//     them and sweeps ~2400 random items under random tables live.  That pins
+//     where the score is applied (recursion on the parent's old blank/total
+//     with the entry's own state, growth with the child's), that alignment
+//     candidates never see it, that the end hooks are never called and that
+//     row 0 of the table is the root's.
 // What stays pinned by reading only:
 //   * gtl::TopN's rules (TensorFlow's source is not at hand: the stand-in
 //     top_n.h is the same restatement as BoundedTop below, so the build
 //     cannot contradict it);
-//   * the bigram scorer: the reference's AddAlignmentCandidate takes
-//     BeamEntry<T>*, so its decoder cannot be instantiated with a scorer that
-//     has state, and only BaseBeamScorer is built;
 //   * the op around the decoder: input validation and the SparseTensor
 //     packing of StoreAllDecodedSequences (kernels.cc:97-257);
 //   * NaN and +inf logits (the stand-in row maximum is Eigen's only without

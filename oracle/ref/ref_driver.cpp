@@ -11,11 +11,27 @@
 // the call with that status.  The reference reports a path without alignment
 // by printing a line to std::cout; the driver captures std::cout for the call
 // and counts those lines.
+//
+// The scorer hook.  The reference's AddAlignmentCandidate takes BeamEntry<T>*
+// (ctc_beam_entry.h), so its decoder compiles only with the default
+// EmptyBeamState: a scorer cannot keep its value in the state object.  It can
+// keep it beside it.  BeamEntry::state is a member of an entry that BeamRoot
+// allocates on the heap, one unique_ptr each, never moves, and frees only when
+// Reset() replaces the root; Reset() then calls InitializeState.  So between
+// two InitializeState calls the address of a state object names one entry and
+// no other, and TableScorer below keys a side table by it: ExpandState stores
+// table[(from_label + 1) * C + to_label] under to_state's address (the root's
+// label is -1: row 0 is the root's), GetStateExpansionScore adds what is
+// stored there to previous_score, InitializeState clears the table.  The
+// counters say whether the argument held during a call (no lookup without a
+// stored value, no address re-expanded to another value) and that the decoder
+// never calls the end hooks.
 #include <cstdint>
 #include <cstring>
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "ctc_ext_beam_search_decoder.h"
@@ -55,6 +71,61 @@ int count_lines(const std::string& text, const std::string& line) {
   return n;
 }
 
+// hook_stats[] of ref_decode_scored
+enum { kInit = 0, kExpand, kLookup, kLookupNoState, kReexpandDiffers, kEndHook, kHookStats };
+
+template <class T>
+class TableScorer : public tensorflow::ctc::BaseBeamScorer<T, tensorflow::ctc::ctc_beam_search::EmptyBeamState> {
+ public:
+  typedef tensorflow::ctc::ctc_beam_search::EmptyBeamState State;
+  TableScorer(const T* table, int64_t C) : table_(table), C_(C) {
+    for (int i = 0; i < kHookStats; ++i) n[i] = 0;
+  }
+  void InitializeState(State* root) const override {
+    ++n[kInit];
+    cached_.clear();
+  }
+  void ExpandState(const State& from_state, int from_label, State* to_state, int to_label) const override {
+    ++n[kExpand];
+    const T v = table_[(int64_t)(from_label + 1) * C_ + to_label];
+    auto at = cached_.emplace((const void*)to_state, v);
+    if (!at.second && std::memcmp(&at.first->second, &v, sizeof(T)) != 0) {
+      ++n[kReexpandDiffers];
+      at.first->second = v;
+    }
+  }
+  T GetStateExpansionScore(const State& state, T previous_score) const override {
+    ++n[kLookup];
+    auto at = cached_.find((const void*)&state);
+    if (at == cached_.end()) {
+      ++n[kLookupNoState];
+      return previous_score;
+    }
+    return previous_score + at->second;
+  }
+  void ExpandStateEnd(State* state) const override { ++n[kEndHook]; }
+  T GetStateEndExpansionScore(const State& state) const override {
+    ++n[kEndHook];
+    return T(0);
+  }
+  mutable int64_t n[kHookStats];
+
+ private:
+  const T* table_;
+  int64_t C_;
+  mutable std::unordered_map<const void*, T> cached_;
+};
+
+// copies the counters out on every way out of run()
+template <class T>
+struct HookReport {
+  const TableScorer<T>& scorer;
+  int64_t* to;
+  ~HookReport() {
+    for (int i = 0; to && i < kHookStats; ++i) to[i] = scorer.n[i];
+  }
+};
+
 }  // namespace
 
 struct RefResult {
@@ -72,7 +143,8 @@ struct RefResult {
 
 template <class T>
 static RefResult* run(const T* x, const int32_t* seq_len, int64_t B, int64_t C, int W, int P,
-                      int merge, int blank_index, int blank_label) {
+                      int merge, int blank_index, int blank_label, const T* table = nullptr,
+                      int64_t* hook_stats = nullptr) {
   namespace ctc = tensorflow::ctc;
   RefResult* r = new RefResult();
   std::memset(r, 0, sizeof(*r));
@@ -81,8 +153,13 @@ static RefResult* run(const T* x, const int32_t* seq_len, int64_t B, int64_t C, 
   std::vector<double> lp_all;
   CoutCapture capture;
 
-  typename ctc::CTCExtBeamSearchDecoder<T>::DefaultBeamScorer scorer;
-  ctc::CTCExtBeamSearchDecoder<T> decoder((int)C, blank_index, W, &scorer, blank_label, 1, merge != 0);
+  // table == nullptr: the reference op's own scorer, as before there was a table
+  typename ctc::CTCExtBeamSearchDecoder<T>::DefaultBeamScorer base;
+  TableScorer<T> scored(table, C);
+  typename ctc::CTCExtBeamSearchDecoder<T>::DefaultBeamScorer* scorer = &base;
+  if (table) scorer = &scored;
+  HookReport<T> report{scored, table ? hook_stats : nullptr};
+  ctc::CTCExtBeamSearchDecoder<T> decoder((int)C, blank_index, W, scorer, blank_label, 1, merge != 0);
   for (int64_t b = 0; b < B && r->ok; ++b) {
     for (int64_t t = 0; t < seq_len[b]; ++t) {
       RowView<T> row{x + (t * B + b) * C, (int)C};
@@ -136,6 +213,22 @@ RefResult* ref_decode(int dtype, const void* x, const int32_t* seq_len, int64_t 
                       int W, int P, int merge, int blank_index, int blank_label) {
   if (dtype == 0) return run<float>((const float*)x, seq_len, B, C, W, P, merge, blank_index, blank_label);
   return run<double>((const double*)x, seq_len, B, C, W, P, merge, blank_index, blank_label);
+}
+
+// As ref_decode with TableScorer over table [C + 1, C] of the same dtype (row
+// from_label + 1, row 0 the root's; see the head of this file).  hook_stats, if
+// not null, receives six counts for the whole call: InitializeState calls,
+// ExpandState calls, GetStateExpansionScore calls, those of them that found no
+// stored value, ExpandState calls that found another value stored under the
+// address, and calls of either end hook.
+RefResult* ref_decode_scored(int dtype, const void* x, const int32_t* seq_len, int64_t B, int64_t C,
+                             int W, int P, int merge, int blank_index, int blank_label,
+                             const void* table, int64_t* hook_stats) {
+  if (dtype == 0)
+    return run<float>((const float*)x, seq_len, B, C, W, P, merge, blank_index, blank_label,
+                      (const float*)table, hook_stats);
+  return run<double>((const double*)x, seq_len, B, C, W, P, merge, blank_index, blank_label,
+                     (const double*)table, hook_stats);
 }
 
 void ref_free(RefResult* r) {

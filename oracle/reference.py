@@ -2,10 +2,13 @@
 INFRASTRUCTURE ONLY): oracle/_ref/libctc_ref.so, made by oracle/ref/Makefile
 from the reference tree's own headers where that tree is present.
 
-``raw_decode`` takes and returns what ``oracle.raw_decode`` does (BaseBeamScorer
-only: the reference's scorer hook cannot be instantiated with a state, see
-ctc_oracle.cpp "Pinning"), and raises ``oracle.OracleError`` with the
-reference Status' own message.  The op's input validation is not in the
+``raw_decode`` takes and returns what ``oracle.raw_decode`` does, and raises
+``oracle.OracleError`` with the reference Status' own message.  With a
+``scorer_table`` the reference decoder runs with a scorer of the driver's,
+derived from the reference's BaseBeamScorer over its default EmptyBeamState:
+the per-state value lives in a side table keyed by the state object's address
+(ref_driver.cpp says why that is sound), and ``hook_stats`` receives the counts
+that show it held during the call.  The op's input validation is not in the
 reference's headers but in kernels.cc; the checks here are the oracle's, made
 before the library is called.
 
@@ -69,15 +72,25 @@ def _load():
         lib.ref_decode.restype = ctypes.POINTER(_Result)
         lib.ref_decode.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        lib.ref_decode_scored.restype = ctypes.POINTER(_Result)
+        lib.ref_decode_scored.argtypes = lib.ref_decode.argtypes + [ctypes.c_void_p, ctypes.c_void_p]
         lib.ref_free.argtypes = [ctypes.POINTER(_Result)]
         _lib = lib
     return _lib
 
 
+HOOK_STATS = ("initialize_state", "expand_state", "lookups", "lookups_without_state", "reexpansions_differ",
+              "end_hook_calls")
+
+
 def raw_decode(inputs, sequence_length, beam_width, top_paths, merge_repeated=False,
-               blank_index=0, blank_label=-1):
+               blank_index=0, blank_label=-1, scorer_table=None, hook_stats=None):
     """(dec, ali, log_prob, no_label_events) as oracle.raw_decode: dec[b][p] and
-    ali[b][p] lists of ints, log_prob [B, P] of the inputs' dtype."""
+    ali[b][p] lists of ints, log_prob [B, P] of the inputs' dtype.
+    ``scorer_table`` ([C + 1, C], the inputs' dtype; row ``from_label + 1``, row 0
+    the root's): the driver's table scorer; None is BaseBeamScorer through
+    ref_decode, as before.  ``hook_stats`` (a dict, with a table only) receives
+    the HOOK_STATS counts of the call, also when it ends in an error."""
     x = np.ascontiguousarray(inputs)
     if x.dtype not in (np.float32, np.float64):
         raise TypeError("inputs must be float32 or float64")
@@ -100,8 +113,20 @@ def raw_decode(inputs, sequence_length, beam_width, top_paths, merge_repeated=Fa
     assert not np.isnan(x).any() and not np.isposinf(x).any(), "NaN / +inf are outside the reference build's scope"
     lib = _load()
     P = int(top_paths)
-    r = lib.ref_decode(0 if x.dtype == np.float32 else 1, x.ctypes.data, sl.ctypes.data, B, C,
-                       int(beam_width), P, int(bool(merge_repeated)), int(blank_index), int(blank_label))
+    args = (0 if x.dtype == np.float32 else 1, x.ctypes.data, sl.ctypes.data, B, C,
+            int(beam_width), P, int(bool(merge_repeated)), int(blank_index), int(blank_label))
+    if scorer_table is None:
+        assert hook_stats is None, "hook_stats needs a scorer_table"
+        r = lib.ref_decode(*args)
+    else:
+        tab = np.ascontiguousarray(np.asarray(scorer_table, dtype=x.dtype))
+        if tab.shape != (C + 1, C):
+            raise ValueError("scorer_table must be [num_classes + 1, num_classes]")
+        assert not np.isnan(tab).any() and not np.isposinf(tab).any(), "NaN / +inf are outside the reference build's scope"
+        counts = np.full(len(HOOK_STATS), -1, np.int64)
+        r = lib.ref_decode_scored(*args, tab.ctypes.data, counts.ctypes.data)
+        if hook_stats is not None:
+            hook_stats.update(zip(HOOK_STATS, counts.tolist()))
     try:
         res = r.contents
         if not res.ok:

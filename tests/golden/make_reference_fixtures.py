@@ -24,8 +24,15 @@ outputs are stored (GROUP_C_SKIPPED says what was not recomputed, and why).
 No case holds NaN or +inf: the library's row maximum is Eigen's only without
 them.
 
-    python tests/golden/make_reference_fixtures.py            # everything (~3 min)
+Group S (reference_scorer_cases.json, a file of its own so that the first
+stays as recorded): the reference under the driver's table scorer
+(oracle/ref/ref_driver.cpp), with tables of tests/scorer_tables.py: the SMALL
+shapes and cfg3 under each table kind, and the semantics of the hook (S_CASES).
+Each entry also holds the table's sha256 and the hook counters of the call.
+
+    python tests/golden/make_reference_fixtures.py            # everything (~4 min)
     python tests/golden/make_reference_fixtures.py NAME ...   # some cases / group C fixtures
+    python tests/golden/make_reference_fixtures.py --scorer [NAME ...]   # group S only
 """
 import hashlib
 import json
@@ -123,7 +130,101 @@ for _i, _fam in enumerate(RANGE_FAMILIES):
         _case("B_range_%s_%s" % (_fam, _dt), "B", _fam, 2100 + _i, _dt, 20, 2, 20, 30, 3, merge=_merge,
               blank=10 if _merge else 0, sl=[20, 17])
 
+# ---- group S: the reference under a bigram table scorer (reference_scorer_cases.json)
+#
+# The driver's TableScorer (oracle/ref/ref_driver.cpp) runs inside the
+# reference decoder; tables come from tests/scorer_tables.py, drawn from
+# default_rng(seed + TABLE_SEED).  A case is a group-A/B case dict plus "table",
+# the table's kind.
+S_OUT = os.path.join(HERE, "reference_scorer_cases.json")
+TABLE_SEED = 5 * 10 ** 6
+S_CASES = {}
+
+
+def _scase(name, gen, table, seed, dtype, T, B, C, W, P, merge=False, blank=0, blabel=-1, sl=None, **gen_args):
+    assert name not in S_CASES and name not in CASES, name
+    S_CASES[name] = dict(group="S", gen=gen, gen_args=gen_args, seed=seed, dtype=dtype, T=T, B=B, C=C,
+                         beam_width=W, top_paths=P, merge_repeated=merge, blank_index=blank, blank_label=blabel,
+                         seq_len=list(sl) if sl is not None else [T] * B, table=table)
+
+
+# (table kind, logits): forbidden decodes with merge_repeated off, so that a
+# decoded path is its prefix's label sequence and its bigrams can be checked
+_PAIRINGS = (("continuous", "normal"), ("grid", "ties"), ("forbidden", "neg_inf"), ("extreme", "normal"))
+# top_paths of the grid cases: the smallest (from the shape's 5, or 3) at which
+# some item's log-probabilities repeat a value, by --search-grid below
+_GRID_P = {
+    "S_T30_C20_W100_f32_grid": (3002, 17), "S_T30_C20_W100_f64_grid": (3006, 7),
+    "S_T30_C20_W200_f32_grid": (3010, 17), "S_T30_C20_W200_f64_grid": (3014, 22),
+    "S_T30_C20_W400_f32_grid": (3018, 24), "S_T30_C20_W400_f64_grid": (3022, 11),
+    "S_T20_C300_W100_f32_grid": (3026, 5), "S_T20_C300_W100_f64_grid": (3030, 5),
+    "S_T20_C300_W200_f32_grid": (3034, 5), "S_T20_C300_W200_f64_grid": (3038, 5),
+    "S_T20_C300_W400_f32_grid": (3042, 5), "S_T20_C300_W400_f64_grid": (3046, 5),
+    "S_T10_C8_W40_f32_grid": (3050, 9), "S_T10_C8_W40_f64_grid": (3054, 13),
+    "S_cfg3_W128_grid": (3229, 3), "S_cfg3_W256_grid": (3357, 3),
+}
+_OWN_P = {}     # grid case -> the top_paths of its shape, the least --search-grid gives it
+_seed = 3000
+for _T, _C, _W, _P in _SMALL:
+    for _dt in ("f32", "f64"):
+        for _tk, _kind in _PAIRINGS:
+            _seed += 1
+            _kw = _KIND[_kind]
+            _name = "S_T%d_C%d_W%d_%s_%s" % (_T, _C, _W, _dt, _tk)
+            _s, _p = _GRID_P.get(_name, (_seed, _P))
+            if _tk == "grid":
+                _OWN_P[_name] = _P
+            _scase(_name, _kind, _tk, _s, _dt, _T, 2, _C, _W, _p, merge=_kw["merge"] and _tk != "forbidden",
+                   blank=_C // 2 if _kw["blank"] is None else 0, sl=[_T, _T - 3])
+for _W in (128, 256):
+    for _tk, _kind in _PAIRINGS[:2]:
+        _name = "S_cfg3_W%d_%s" % (_W, _tk)
+        _s, _p = _GRID_P.get(_name, (3100 + _W + (_tk == "grid"), 3))
+        if _tk == "grid":
+            _OWN_P[_name] = 3
+        _scase(_name, _kind, _tk, _s, "f32", 200, 2, 29, _W, _p, merge=True, sl=[200, 197])
+
+# semantics.  An all-zero table on the inputs of a group-A case: that case's outputs
+S_ZERO_OF = {"S_zero_table_is_base_scorer": "A_T30_C20_W100_f32_ties", "S_zero_table_is_base_scorer_f64": "A_T20_C300_W200_f64_neg_inf"}
+for _name, _of in S_ZERO_OF.items():
+    S_CASES[_name] = dict(CASES[_of], group="S", table="zero")
+# nothing can leave the root: the empty path alone
+_scase("S_root_forbidden_one_path", "normal", "root_forbidden", 3201, "f32", 12, 2, 6, 8, 1, merge=True, sl=[12, 9])
+_scase("S_root_forbidden_two_paths", "normal", "root_forbidden", 3201, "f32", 12, 2, 6, 8, 2, merge=True, sl=[12, 9])
+_scase("S_root_forbidden_f64_blank_2", "ties", "root_forbidden", 3202, "f64", 12, 2, 6, 8, 1, blank=2, blabel=2, sl=[12, 9])
+# label l only before l + 1 mod C
+_scase("S_chain", "normal", "chain", 3203, "f32", 16, 2, 6, 10, 4, merge=True, sl=[16, 13])
+_scase("S_chain_f64_blank_3", "ties", "chain", 3204, "f64", 16, 2, 6, 10, 4, blank=3, sl=[16, 13])
+_scase("S_beam_1", "normal", "continuous", 3205, "f32", 25, 2, 6, 1, 1, merge=True, sl=[25, 20])
+_scase("S_beam_1_extreme", "ties", "extreme", 3206, "f64", 25, 2, 6, 1, 1, blank=3, sl=[25, 20])
+_scase("S_one_frame", "normal", "continuous", 3207, "f32", 1, 3, 9, 8, 4, blank=4)
+_scase("S_one_frame_f64_grid", "ties", "grid", 3208, "f64", 1, 3, 9, 9, 9, merge=True)
+_scase("S_one_frame_forbidden", "normal", "forbidden", 3209, "f32", 1, 3, 9, 8, 2)
+_scase("S_zero_length_item", "normal", "continuous", 3210, "f32", 8, 3, 6, 8, 1, merge=True, sl=[8, 0, 5])
+_scase("S_zero_length_item_f64", "ties", "forbidden", 3211, "f64", 8, 3, 6, 8, 1, blank=5, sl=[0, 8, 0])
+_scase("S_blank_last", "normal", "continuous", 3212, "f32", 16, 2, 6, 10, 3, merge=True, blank=5, blabel=5, sl=[16, 13])
+_scase("S_blank_middle_grid", "ties", "grid", 3213, "f64", 16, 2, 7, 10, 3, blank=3, blabel=0, sl=[16, 13])
+_scase("S_blank_middle_forbidden", "neg_inf", "forbidden", 3214, "f32", 16, 2, 7, 10, 3, blank=3, sl=[16, 13])
+_scase("S_error_more_paths_than_beam", "normal", "continuous", 3215, "f32", 6, 2, 5, 3, 4)
+_scase("S_error_less_leaves", "normal", "forbidden", 3216, "f64", 6, 3, 3, 10, 5, sl=[6, 1, 6])
+# -inf-heavy items on the half grid under a grid table, chosen (--search-scorer
+# 34000 400) so that frames start with one entry twice in the beam
+# (seed, T, B, C, W, P, -inf fraction, merge_repeated, blank_index, blank_label)
+# (two duplicate-entry items each, and an item whose finite log-probabilities
+# repeat a value; NaN rows, items that -inf left no path, do not count)
+_S_DUP = [(34039, 29, 3, 5, 9, 6, 0.5, False, 0, 1), (34083, 25, 3, 5, 7, 5, 0.5, False, 3, -1)]
+for (_s, _T, _B, _C, _W, _P, _frac, _merge, _blank, _blabel) in _S_DUP:
+    for _dt in ("f32", "f64"):
+        _scase("S_duplicate_state_%d_%s" % (_s, _dt), "neg_inf", "grid", _s, _dt, _T, _B, _C, _W, _P,
+               merge=_merge, blank=_blank, blabel=_blabel, frac=_frac, ties=True)
+
 NP = {"f32": np.float32, "f64": np.float64}
+
+
+def scorer_table(c):
+    """The [C + 1, C] table of a group-S case dict, of the case's dtype."""
+    import scorer_tables
+    return scorer_tables.table(np.random.default_rng(c["seed"] + TABLE_SEED), c["table"], c["C"], NP[c["dtype"]])
 
 
 def inputs(c):
@@ -138,6 +239,8 @@ def inputs(c):
         if gen == "ties":
             x = np.round(x * 2) / 2
         elif gen == "neg_inf":
+            if c["gen_args"].get("ties"):     # on the half grid first: with a grid table, totals repeat
+                x = np.round(x * 2) / 2
             x[rng.random(x.shape) < c["gen_args"].get("frac", 0.15)] = -np.inf
         elif gen == "neg_inf_rows":       # 15% -inf, and every fourth frame -inf throughout
             x[rng.random(x.shape) < 0.15] = -np.inf
@@ -185,11 +288,19 @@ def record(c):
     x, sl = inputs(c)
     t0 = time.time()
     entry = {"case": c, "sha256": sha(x)}
+    scored = {}
+    if c.get("table") is not None:
+        hooks = {}
+        tab = scorer_table(c)
+        entry["table_sha256"] = sha(tab)
+        scored = dict(scorer_table=tab, hook_stats=hooks)
     try:
-        dec, ali, lp, events = reference.raw_decode(x, sl, c["beam_width"], c["top_paths"], **attrs(c))
+        dec, ali, lp, events = reference.raw_decode(x, sl, c["beam_width"], c["top_paths"], **attrs(c), **scored)
         entry.update(decoded=dec, alignment=ali, log_probability_hex=hex_rows(lp), error=None, no_label=events)
     except oracle.OracleError as e:
         entry.update(decoded=None, alignment=None, log_probability_hex=None, error=str(e), no_label=None)
+    if scored:
+        entry["hook_stats"] = hooks
     entry["reference_seconds"] = round(time.time() - t0, 3)
     return entry
 
@@ -274,9 +385,33 @@ def group_c(name):
             "no_label": n, "reference_seconds": round(time.time() - t0, 1)}
 
 
+def main_scorer(names):
+    """Group S -> reference_scorer_cases.json (all of it, or the named cases)."""
+    import reference
+    assert reference.available(), "oracle/_ref/libctc_ref.so is missing: run build() where the reference tree is"
+    out = json.load(open(S_OUT)) if os.path.exists(S_OUT) and names else {}
+    out.setdefault("cases", {})
+    out["source"] = ("the reference decoder's own headers compiled by oracle/ref (g++ -O2 -std=c++14, no -march) "
+                     "with the driver's TableScorer, through oracle/reference.py")
+    out["reference_headers_sha256"] = reference.header_sha256()
+    for name in names or list(S_CASES):
+        out["cases"][name] = record(S_CASES[name])
+        print(name, out["cases"][name]["error"] or "ok", out["cases"][name]["reference_seconds"], flush=True)
+    with open(S_OUT, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("%d scorer cases, %d bytes" % (len(out["cases"]), os.path.getsize(S_OUT)))
+
+
 def main(names):
     import reference
     assert reference.available(), "oracle/_ref/libctc_ref.so is missing: run build() where the reference tree is"
+    if not names:
+        main_scorer([])
+    elif any(n in S_CASES for n in names):
+        main_scorer([n for n in names if n in S_CASES])
+        names = [n for n in names if n not in S_CASES]
+        if not names:
+            return
     out = json.load(open(OUT)) if os.path.exists(OUT) and names else {}
     out.setdefault("cases", {})
     out.setdefault("group_c", {})
@@ -296,11 +431,14 @@ def main(names):
     print("%d cases, %d bytes" % (len(out["cases"]), os.path.getsize(OUT)))
 
 
-def search(first_seed, count, short=False):
-    """How the rows of _DUP (--search 24100 400) and _NO_LABEL (--search-short
-    30000 200) were chosen: prints seeds whose case the oracle decodes without
-    an error, with duplicate-entry frames or paths without an alignment.  (A
-    condition on inputs, computed with the oracle.)"""
+def search(first_seed, count, short=False, table=None):
+    """How the rows of _DUP (--search 24100 400), _NO_LABEL (--search-short
+    30000 200) and, with a table kind, _S_DUP (--search-scorer 34000 400) were
+    chosen: prints seeds whose case the oracle decodes without an error, with
+    duplicate-entry frames or paths without an alignment.  With a table the
+    -inf-heavy logits lie on the half grid, and a seed also needs an item whose
+    finite log-probabilities repeat a value.  (A condition on inputs, computed
+    with the oracle.)"""
     import oracle
     for seed in range(first_seed, first_seed + count):
         rng = np.random.default_rng(seed + 10 ** 6)
@@ -311,24 +449,61 @@ def search(first_seed, count, short=False):
             T, B, C, W = int(rng.integers(8, 30)), int(rng.integers(2, 4)), int(rng.integers(4, 8)), int(rng.integers(4, 10))
             P, frac = int(rng.integers(1, W + 1)), float(rng.choice([0.3, 0.5]))
         merge, blank, blabel = bool(rng.integers(2)), int(rng.integers(C)), int(rng.integers(-1, C))
-        c = dict(gen="neg_inf", gen_args=dict(frac=frac), seed=seed, dtype="f32", T=T, B=B, C=C, seq_len=[T] * B,
-                 blank_index=blank)
+        c = dict(gen="neg_inf", gen_args=dict(frac=frac, ties=True) if table else dict(frac=frac), seed=seed, dtype="f32", T=T, B=B, C=C, seq_len=[T] * B,
+                 blank_index=blank, table=table)
         x, sl = inputs(c)
+        tab = scorer_table(c) if table else None
         dups = 0
         try:
             for b in range(B):
                 st = {}
-                oracle.raw_decode(x[:, b:b + 1], [T], W, P, merge, blank, blabel, stats=st)
+                oracle.raw_decode(x[:, b:b + 1], [T], W, P, merge, blank, blabel, stats=st, scorer_table=tab)
                 dups += st["duplicate_frames"] > 0
-            events = oracle.raw_decode(x, sl, W, P, merge, blank, blabel)[3]
+            lp, events = oracle.raw_decode(x, sl, W, P, merge, blank, blabel, scorer_table=tab)[2:4]
         except oracle.OracleError:
             continue
-        if dups or events:
+        if table:
+            rows = [[v for v in row.tolist() if np.isfinite(v)] for row in np.asarray(lp)]
+            if dups and any(len(r) > len(set(r)) for r in rows):
+                print((seed, T, B, C, W, P, frac, merge, blank, blabel), "dup items", dups,
+                      "items with a repeated finite log-probability", sum(len(r) > len(set(r)) for r in rows))
+        elif dups or events:
             print((seed, T, B, C, W, P, frac, merge, blank, blabel), "dup items", dups, "no-label", events)
+
+
+def search_grid():
+    """How _GRID_P was chosen: per grid case of _OWN_P its seed and the smallest
+    top_paths, from the shape's own up to 50 and the beam, at which some
+    item's log-probabilities repeat a value; computed with the oracle at the
+    largest top_paths."""
+    import oracle
+    for name, own in _OWN_P.items():
+        c = S_CASES[name]
+        x, sl = inputs(c)
+        pmax = min(50, c["beam_width"])
+        lp = oracle.raw_decode(x, sl, c["beam_width"], pmax, scorer_table=scorer_table(c), **attrs(c))[2]
+        need = []
+        for row in np.asarray(lp):
+            seen = set()
+            for i, v in enumerate(row.tolist()):
+                if v in seen:
+                    need.append(i + 1)
+                    break
+                seen.add(v)
+        if need:
+            print('    "%s": (%d, %d),' % (name, c["seed"], max(own, min(need))), flush=True)
+        else:
+            print("# %s: no item repeats a value within %d paths: take another seed" % (name, pmax))
 
 
 if __name__ == "__main__":
     if sys.argv[1:2] in (["--search"], ["--search-short"]):
         search(int(sys.argv[2]), int(sys.argv[3]), short=sys.argv[1] == "--search-short")
+    elif sys.argv[1:2] == ["--search-scorer"]:
+        search(int(sys.argv[2]), int(sys.argv[3]), table="grid")
+    elif sys.argv[1:2] == ["--search-grid"]:
+        search_grid()
+    elif sys.argv[1:2] == ["--scorer"]:
+        main_scorer(sys.argv[2:])
     else:
         main(sys.argv[1:])

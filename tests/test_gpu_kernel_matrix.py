@@ -18,6 +18,12 @@ last fitting class counts, the record ring behind a run-time-W layout.  LDS
 accesses past the allocation do not fault, so a disagreement between the
 kernel's carve and decode_lds_bytes shows only as wrong outputs, here.
 
+test_bigram_instantiation_table_kinds gives every bigram cell the other table
+kinds of tests/scorer_tables.py: entries on a grid with half-grid logits (equal
+totals: the scored kernels' tie order), forbidden bigrams (-inf entries, whole
+rows and columns of them; no decoded path may hold one) and entries at the
+ends of the float range.
+
 The last part decodes the families of tests/range_inputs.py (the whole float
 range: expf's and exp's subnormal band and underflow bound, one dominant
 class, logits near 1e6..3e7, overflowing differences, subnormals) through
@@ -34,6 +40,7 @@ from ctcext_amd import _lib
 from parity_util import compare
 import oracle
 import range_inputs
+import scorer_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -156,18 +163,12 @@ def _inputs(rng, kind, T, C, dtype):
 
 
 def _bigram_table(rng, C, dtype):
-    """-abs(normal) * 2 entries; past 5000 classes (a table of gigabytes) only
-    the root's row and every seventh row after it are non-zero, each entry the
-    sum of a row and a column term: the rest of the table is never written,
-    so building it stays cheap, and the expansions of one beam in seven are
-    still penalised."""
-    if C <= 5000:
-        return (-np.abs(rng.standard_normal((C + 1, C))) * 2).astype(NP[dtype])
-    tab = np.zeros((C + 1, C), NP[dtype])
-    ra = np.abs(rng.standard_normal(((C + 7) // 7, 1))).astype(NP[dtype])
-    rb = np.abs(rng.standard_normal((1, C))).astype(NP[dtype])
-    np.negative(ra + rb, out=tab[::7])
-    return tab
+    """scorer_tables' continuous kind: -abs(normal) * 2 entries; past 5000
+    classes (a table of gigabytes) only the root's row and every seventh row
+    after it are non-zero, each entry the sum of a row and a column term: the
+    rest of the table is never written, so building it stays cheap, and the
+    expansions of one beam in seven are still penalised."""
+    return scorer_tables.table(rng, "continuous", C, NP[dtype])
 
 
 def _decode_both(x, sl, W, P, kw, tab=None, flags=0, want_ref=True):
@@ -213,6 +214,87 @@ def _run_cell(name, monkeypatch, kinds=None, want_ref=True):
 @pytest.mark.parametrize("name", sorted(CELLS))
 def test_instantiation_matches_oracle(name, monkeypatch):
     _run_cell(name, monkeypatch)
+
+
+# ---- the bigram cells under the other table kinds
+
+# table kind -> (the logits it is paired with, merge_repeated).  forbidden
+# decodes with merge_repeated off, so that a decoded path is its prefix's label
+# sequence and every bigram of it can be looked up in the table.
+TABLE_KINDS = {"grid": ("ties", True), "forbidden": ("neg_inf", False), "extreme": ("normal", False),
+               # grid entries with 30% -inf under half-grid logits: no frame takes the literal path (the -inf logits
+               # of the forbidden pairing send nearly every frame there), so the fast path's own -inf admission
+               # tests and its tie order run.  The one kind of the run-time-W cells (tables of gigabytes, every
+               # seventh row written), where a literal frame takes seconds.
+               "grid_forbidden": ("ties", True)}
+BIGRAM_CELLS = sorted(n for n, c in CELLS.items() if c[0][2] == "bigram")
+TABLE_KIND_PARAMS = [(n, k) for n in BIGRAM_CELLS
+                     for k in (("grid", "forbidden", "extreme", "grid_forbidden") if CELLS[n][1][0][1] <= 5000
+                               else ("grid_forbidden",))]
+assert len(BIGRAM_CELLS) == 18 and len(TABLE_KIND_PARAMS) == 14 * 4 + 4
+
+
+def table_kind_case(name, tkind, B=2, reseed=""):
+    """(x [T, B, C], lengths, W, P, attributes, table) of a bigram cell under
+    a table kind; shared with the stream matrix (B = 3, and a suffix to the
+    seed's name where its census needs another draw)."""
+    row, shapes, _, _, _ = CELLS[name]
+    (T, C, W, P), = shapes
+    kind, merge = TABLE_KINDS[tkind]
+    rng = np.random.default_rng(zlib.crc32(("%s/table/%s%s" % (name, tkind, reseed)).encode()))
+    tab = scorer_tables.table(rng, tkind, C, NP[row[1]])
+    kw = dict(KINDS[kind], merge_repeated=merge)
+    if kw["blank_index"] is None:
+        kw["blank_index"] = C // 2
+    x = rng.standard_normal((T, B, C))
+    if kind == "ties":
+        x = np.round(x * 2) / 2
+    elif kind == "neg_inf":
+        x[rng.random(x.shape) < 0.15] = -np.inf
+    return x.astype(NP[row[1]]), np.array([T, max(T - 3, 1), 2][:B], np.int32), W, P, kw, tab
+
+
+def decoded_paths(out, B, P):
+    """The op's decoded label lists, path by path and item by item."""
+    paths = []
+    for p in range(P):
+        idx, val = (np.asarray(t.cpu() if hasattr(t, "cpu") else t) for t in (out.decoded_indices[p], out.decoded_values[p]))
+        for b in range(B):
+            paths.append(val[idx[:, 0] == b].tolist())
+    return paths
+
+
+@pytest.mark.parametrize("name,tkind", TABLE_KIND_PARAMS)
+def test_bigram_instantiation_table_kinds(name, tkind, monkeypatch):
+    """All seven outputs are the oracle's, bit for bit, and the kernel that ran
+    is the cell's.  Under the forbidden kinds no decoded path of the op starts
+    with a label the root's row forbids or holds a step (a, b) whose entry
+    [a + 1][b] is -inf (asserted on the op's outputs, not only through the
+    oracle), and the reference has P paths to compare."""
+    row, shapes, helper_env, flags, _ = CELLS[name]
+    monkeypatch.setenv("CTCEXT_HELPER", helper_env)
+    x, sl, W, P, kw, tab = table_kind_case(name, tkind)
+    if "forbidden" in tkind:   # (of the rows that are written; 72 entries at C = 8)
+        assert np.isneginf(tab if tab.shape[1] <= scorer_tables.SPARSE_ABOVE else tab[::scorer_tables.SPARSE_STEP]).mean() > 0.2
+    try:
+        out, ref = _decode_both(x, sl, W, P, kw, tab, flags)
+    except (oracle.OracleError, ctcext_amd.OpError) as e:
+        raise AssertionError("%s %s: %s" % (name, tkind, e))
+    k = _stats()["kernel"]
+    assert k["launched"] and _stat_row(k) == row, (name, tkind, k)
+    assert _stats()["tier"] == row[0]
+    _observed.add(row)
+    compare(out, ref, P, lp_exact=True)
+    if "forbidden" in tkind:
+        # (merge_repeated, which grid_forbidden keeps on, only drops a label
+        # equal to the one before it: every step left in a path is a step of
+        # its prefix)
+        paths = decoded_paths(out, 2, P)
+        assert any(len(p) >= 2 for p in paths)
+        assert scorer_tables.forbidden_pairs(tab, paths) == [], name
+    if tkind in ("grid", "grid_forbidden"):
+        lp = np.asarray(ref.log_probability)
+        print("%s %s: distinct log-probabilities per item %s of %d" % (name, tkind, [len(set(r.tolist())) for r in lp], P))
 
 
 def test_every_instantiation_is_accounted_for(monkeypatch):

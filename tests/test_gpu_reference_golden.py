@@ -24,6 +24,21 @@ through each route a case's shape reaches:
 Each test asserts from last_stats (tier, helper, kernel) that its route ran:
 a fallback cannot stand in for the kernel.  A case the reference ended with an
 error must raise that message.
+
+tests/golden/reference_scorer_cases.json (group S) holds what the reference
+decoder computed with a bigram table scorer in its scorer hook
+(oracle/ref/ref_driver.cpp), for tables of every kind of
+tests/scorer_tables.py.  test_bigram_route_matches_reference runs those cases
+with the table through the same routes (helper0 left out; helper1 and helper4
+ask for a two-wave kernel that a table must refuse: helper none), the stream
+with the table on the host, decode_dense with it as a CUDA tensor, and
+
+  sharded          devices=[0, 0]: two shards, each with its own copy of the
+                   table; n_devices == 2 and the root shard's kernel row
+
+and asserts on each that the kernel row's scorer is bigram.  A shape the
+scorer's state arrays put past the LDS tier, or leave no room for the ring
+(_scored_layout, from decode_lds_bytes), runs the routes it still reaches.
 """
 import functools
 import json
@@ -47,6 +62,9 @@ sys.path.insert(0, GOLDEN)
 import make_reference_fixtures as gen  # noqa: E402  (inputs(): the cases' random streams)
 
 CASES = json.load(open(os.path.join(GOLDEN, "reference_cases.json")))["cases"]
+S_CASES = json.load(open(os.path.join(GOLDEN, "reference_scorer_cases.json")))["cases"]
+assert not set(CASES) & set(S_CASES)
+ALL = dict(CASES, **S_CASES)
 DEV = "cuda:0"
 NP = {"f32": np.float32, "f64": np.float64}
 PAD = -7
@@ -62,13 +80,61 @@ def _helper(c, mode):
     table (C <= 64, beams <= 128) or the gather queue (C > 64, beams <= 256),
     both HW, else the one-wave kernel."""
     C, W = c["C"], c["beam_width"]
-    if mode == "0" or c["dtype"] != "f32" or C < 2:
-        return "none"
+    if mode == "0" or c["dtype"] != "f32" or C < 2 or c.get("table") is not None:
+        return "none"   # (a table keeps the one-wave bigram kernel whatever CTCEXT_HELPER says)
     if mode in (None, "4") and (W <= 128 or (mode == "4" and W <= 256 and C > 64)):
         return "SQ"
     if C <= 64:
         return "HW" if W <= 128 else "none"
     return "HW" if W <= 256 else "none"
+
+
+def _a16(v):
+    return (v + 15) & ~15
+
+
+def _decode_lds_bytes(W, C, tsize, scored):
+    """decode_lds_bytes of ctcx_kernels.h, line by line: the bytes of the decode
+    kernel's LDS layout for a beam capacity W."""
+    enc = 3 * W + 2
+    nbuf = 1 if C > 64 else 2
+    htab = 16
+    while htab < 2 * W:
+        htab <<= 1
+    s = nbuf * _a16(5 * W * tsize) + nbuf * _a16(3 * W * 4) + _a16(4 * W * 4) + _a16(5 * enc * tsize) + _a16(5 * enc * 4)
+    s += _a16((W + 1) * 4) * 2 + _a16(W * 4) * 2 + 64 + 32 * 8 + nbuf * 2 * W * 8 + _a16(4 * htab) + _a16(8 * W)
+    s += ((W if W > 256 else 256 if W > 128 else 128) + 2 + 64) * (16 if tsize == 8 else 8)
+    if scored:
+        s += _a16((nbuf * W + enc) * tsize)
+    s += _a16(C * tsize) + _a16(((C + 63) // 64) * tsize)
+    if C > 64:
+        nw = (C - 1 + 63) // 64
+        s += 64 * 4 + 8 * nw + 8 * ((nw + 63) // 64) + 64 * 8
+    return s
+
+
+LDS_BYTES = 160 * 1024
+assert _decode_lds_bytes(400, 20, 4, False) == 110768 and _decode_lds_bytes(400, 300, 8, False) == 130496 \
+    and _decode_lds_bytes(400, 20, 8, False) == 154608   # (the figures of _ring_fits' docstring)
+# with the scorer's states, (2 W + 3 W + 2) values more at C <= 64: 8016 bytes in float at 400 beams, 16016 in
+# double, which is past the LDS; 380 beams in double stay inside (test_gpu_kernel_matrix's cell runs in tier 0)
+assert _decode_lds_bytes(400, 20, 4, True) == 118784 and _decode_lds_bytes(400, 20, 8, True) == 170624 > LDS_BYTES \
+    and _decode_lds_bytes(380, 20, 8, True) <= LDS_BYTES and _decode_lds_bytes(400, 300, 8, True) == 143312
+
+
+def _scored_layout(c):
+    """(whether a scored decode of the case's shape stays in the LDS tier, and
+    there whether an 8-frame ring fits beside its layout): max_beam_width and
+    ring_frames of the library, for two items (the whole LDS is the budget).
+    The scorer's state arrays put (30, 20, 400) in double past the LDS tier
+    (test_gpu_kernel_matrix decodes that cell at 380 beams for the same
+    reason), and leave the ring no room at 400 beams in double at C = 300."""
+    W, C, ts = c["beam_width"], c["C"], 8 if c["dtype"] == "f64" else 4
+    if _decode_lds_bytes(W, C, ts, True) > LDS_BYTES:
+        return False, False
+    cap = 128 if W <= 128 else 256 if W <= 256 else W   # (C <= 300: the compile-time layouts fit)
+    ring = _a16(8 * W * 8) + _a16(4 * 8) + 2 * _a16(4 * W) + _a16(8 * W)
+    return True, _a16(_decode_lds_bytes(cap, C, ts, True)) + ring <= LDS_BYTES
 
 
 def _ring_fits(c):
@@ -80,11 +146,33 @@ def _ring_fits(c):
     130496 (double, C = 300) and 154608 (double, C = 20: two branch buffers of
     8-byte values): only the last leaves less than the ring needs, and has no
     ring_min route."""
+    if c.get("table") is not None:
+        return _scored_layout(c)[1]
     return not (c["beam_width"] > 256 and c["dtype"] == "f64" and c["C"] <= 64)
+
+
+def _scored_routes(c):
+    """The routes of a group-S case: as _routes, with helper1 / helper4 asking
+    for a two-wave kernel that a table must refuse, and the sharded handle
+    (two shards on device 0, each with its own copy of the table)."""
+    W = c["beam_width"]
+    if not _scored_layout(c)[0]:     # past the LDS tier: every route is the global-state bigram kernel
+        return ["default", "gstate", "stream", "dense", "sharded"]
+    routes = ["default", "helper1"]
+    if 129 <= W <= 256:
+        routes.append("helper4")
+    routes += ["literal", "gstate", "stream", "dense", "sharded"]
+    if _ring_fits(c):
+        routes.append("ring_min")
+    if c["dtype"] == "f32" and c["table"] == "grid" and c["gen"] == "ties":
+        routes += ["bf16", "fp16"]
+    return routes
 
 
 def _routes(c):
     """The routes the case's shape reaches."""
+    if c.get("table") is not None:
+        return _scored_routes(c)
     C, W = c["C"], c["beam_width"]
     routes = ["default", "helper0"]
     if _helper(c, "1") == "HW":
@@ -100,12 +188,22 @@ def _routes(c):
 
 
 PARAMS = [(name, route) for name in sorted(CASES) for route in _routes(CASES[name]["case"])]
+S_PARAMS = [(name, route) for name in sorted(S_CASES) for route in _routes(S_CASES[name]["case"])]
+
+
+@functools.lru_cache(maxsize=None)
+def _table(name):
+    fx = S_CASES[name]
+    tab = gen.scorer_table(fx["case"])
+    assert gen.sha(tab) == fx["table_sha256"], "table stream changed"
+    tab.setflags(write=False)
+    return tab
 
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
     """(x, seq_len, the recorded outputs as the op's seven fields or None, the recorded error)."""
-    fx = CASES[name]
+    fx = ALL[name]
     c = fx["case"]
     x, sl = gen.inputs(c)
     assert gen.sha(x) == fx["sha256"], "input stream changed"
@@ -121,10 +219,11 @@ def _case(name):
 
 def _kernel_row(c, helper, tier=0):
     W = c["beam_width"]
+    scorer = "base" if c.get("table") is None else "bigram"
     if tier == 1:
-        return (1, c["dtype"], "base", 1, 0, False, "none")
+        return (1, c["dtype"], scorer, 1, 0, False, "none")
     # (every shape here fits the compile-time layouts: C <= 300)
-    return (0, c["dtype"], "base", 1 if W <= 128 else 2 if W <= 256 else 4,
+    return (0, c["dtype"], scorer, 1 if W <= 128 else 2 if W <= 256 else 4,
             128 if W <= 128 else 256 if W <= 256 else 0, c["C"] > 64, helper)
 
 
@@ -139,7 +238,8 @@ def _assert_route(st, c, route, sl, stream=False):
         return
     assert k["launched"], (route, st)
     assert k["stream"] == stream, (route, k)
-    if route == "gstate":
+    assert k["scorer"] == ("base" if c.get("table") is None else "bigram"), (route, k)
+    if route == "gstate" or (c.get("table") is not None and not _scored_layout(c)[0]):
         assert st["tier"] == 1 and _stat_row(k) == _kernel_row(c, "none", tier=1), (route, st)
         return
     assert st["tier"] == 0, (route, st)
@@ -152,15 +252,17 @@ def _assert_route(st, c, route, sl, stream=False):
         assert st["literal_frames"] == frames, (route, st["literal_frames"], frames)
 
 
-def _one_shot(x, sl, c, flags):
-    return ctcext_amd.ctc_ext_beam_search_decoder(x, sl, c["beam_width"], c["top_paths"], flags=flags, **gen.attrs(c))
+def _one_shot(x, sl, c, flags, tab=None, devices=None):
+    return ctcext_amd.ctc_ext_beam_search_decoder(x, sl, c["beam_width"], c["top_paths"], flags=flags, scorer_table=tab,
+                                                  devices=devices, **gen.attrs(c))
 
 
-def _stream(x, sl, c):
+def _stream(x, sl, c, tab=None):
     T, B, C = x.shape
     cuts = [0, -(-T // 3), -(-2 * T // 3), T]
     x = np.ascontiguousarray(x)
-    with ctcext_amd.StreamDecoder(B, C, c["beam_width"], c["top_paths"], T, dtype=NP[c["dtype"]], **gen.attrs(c)) as s:
+    with ctcext_amd.StreamDecoder(B, C, c["beam_width"], c["top_paths"], T, dtype=NP[c["dtype"]], scorer_table=tab,
+                                  **gen.attrs(c)) as s:
         for i in range(3):
             t0, t1 = cuts[i], cuts[i + 1]
             n = (np.minimum(sl, t1) - np.minimum(sl, t0)).astype(np.int32)
@@ -171,16 +273,32 @@ def _stream(x, sl, c):
         return out, st
 
 
-def _dense(x, sl, c):
+def _dense(x, sl, c, tab=None):
     out = ctcext_amd.decode_dense(torch.as_tensor(np.array(x), device=DEV), torch.as_tensor(sl, device=DEV),
-                                  c["beam_width"], c["top_paths"], batch_first=False, pad_value=PAD, **gen.attrs(c))
+                                  c["beam_width"], c["top_paths"], batch_first=False, pad_value=PAD,
+                                  scorer_table=None if tab is None else torch.as_tensor(np.array(tab), device=DEV),
+                                  **gen.attrs(c))
     st = ctcext_amd.dense_check()   # (waits; raises what the synchronous call would have raised)
     return out, st
 
 
+@pytest.mark.parametrize("name,route", S_PARAMS)
+def test_bigram_route_matches_reference(name, route, monkeypatch):
+    """The group-S cases (the reference under the driver's table scorer)
+    through every route a table reaches.  _assert_route holds the kernel row to
+    scorer bigram on each; helper1 / helper4 must have stayed on one wave; the
+    sharded handle must have split the batch over its two shards and give what
+    the recorded reference gave."""
+    _check_route(name, route, monkeypatch, _table(name))
+
+
 @pytest.mark.parametrize("name,route", PARAMS)
 def test_route_matches_reference(name, route, monkeypatch):
-    c = CASES[name]["case"]
+    _check_route(name, route, monkeypatch, None)
+
+
+def _check_route(name, route, monkeypatch, tab):
+    c = ALL[name]["case"]
     x, sl, want, error = _case(name)
     P = c["top_paths"]
     if route in HELPER_ENV:
@@ -190,16 +308,22 @@ def test_route_matches_reference(name, route, monkeypatch):
 
     def run():
         if route == "stream":
-            return _stream(x, sl, c)
+            return _stream(x, sl, c, tab)
         if route == "dense":
-            return _dense(x, sl, c)
+            return _dense(x, sl, c, tab)
+        if route == "sharded":
+            out = _one_shot(x, sl, c, 0, tab, devices=[0, 0])
+            st = ctcext_amd.get_decoder((0, 0)).last_stats
+            assert st["n_devices"] == 2, st
+            return out, st
         if route in ("bf16", "fp16"):
             half = torch.bfloat16 if route == "bf16" else torch.float16
             logits = torch.from_numpy(np.array(x)).transpose(0, 1).contiguous().to(half)
             assert (logits.float().transpose(0, 1).numpy() == x).all(), "the half grid is exact in the format"
-            out = ctcext_amd.decode_logits(logits.to(DEV), sl, c["beam_width"], P, batch_first=True, **gen.attrs(c))
+            out = ctcext_amd.decode_logits(logits.to(DEV), sl, c["beam_width"], P, batch_first=True, scorer_table=tab,
+                                           **gen.attrs(c))
         else:
-            out = _one_shot(x, sl, c, FLAGS.get(route, 0))
+            out = _one_shot(x, sl, c, FLAGS.get(route, 0), tab)
         return out, ctcext_amd.get_decoder(0).last_stats
 
     if error is not None:

@@ -51,6 +51,23 @@ after a later push: here.
    without an error (an error on both sides must not stand in for a
    comparison); in the -inf kind every item's live rows contain -inf.
 
+5. test_stream_bigram_table_kinds: the bigram cells again under the table
+   kinds of tests/scorer_tables.py (test_gpu_kernel_matrix.table_kind_case,
+   three items): grid entries with half-grid logits (equal totals: the tie
+   order must survive the image) and forbidden bigrams with -inf logits, as two
+   streams that take turns on the cell's schedule, with the comparisons, row
+   and counter checks of 1; the forbidden stream's one-shot call must have
+   taken literal frames.  At the run-time-W cells (C from 9000 to 31400, every
+   seventh row of the table written) the second stream is grid_forbidden: grid
+   entries with 30% -inf on the written rows under half-grid logits, so the
+   stream builds of those four kernels copy and meet -inf table entries on the
+   fast path (no frame of it may be a non-finite replay).  The forbidden
+   pairing's -inf logits send their frames down the literal path, seconds a
+   frame at these class counts with the scorer, in the stream and again in the
+   one-shot call: measured, those four ids took 6.6, 8.0, 9.7 and 23.5 s, each
+   longer than the slowest id its cell had (4.6, 5.6, 3.5 and 9.9 s), and the
+   literal path under a forbidden table is what the fourteen smaller cells run.
+
 The references are computed once per (cell, kind) and shared, read-only,
 between the census and the GPU tests of a session.
 """
@@ -65,7 +82,9 @@ import ctcext_amd
 from ctcext_amd import _lib
 from parity_util import compare
 import oracle
-from test_gpu_kernel_matrix import BASE_KINDS, CELLS, KINDS, TABLE, _bigram_table, _stat_row
+import scorer_tables
+from test_gpu_kernel_matrix import (BASE_KINDS, BIGRAM_CELLS, CELLS, KINDS, TABLE, _bigram_table, _stat_row,
+                                    table_kind_case)
 import test_gpu_stream as stream_tests
 from test_gpu_stream import _inputs
 
@@ -80,7 +99,8 @@ COUNTERS = ("literal_frames", "literal_nonfinite", "literal_fill", "duplicate_fr
 # (cell or edge id, kind) -> a suffix of the seed's name, where the inputs of
 # crc32("<id>/<kind>") miss a condition of the census (part 4): the seed
 # changes, never the condition
-RESEED = {}
+# (eight classes, a forbidden root row and -inf logits: the first frame must leave every item three leaves)
+RESEED = {("gstate_f32_bigram", "table/forbidden"): "/b"}
 
 
 def schedule(T):
@@ -193,6 +213,47 @@ def _live_has_neg_inf(x, frames):
     return [bool(np.isneginf(x[:n, b]).any()) for b, n in enumerate(frames)]
 
 
+def _stream_table_kinds(name):
+    """grid and forbidden; at the run-time-W cells grid and grid_forbidden, the
+    kind test_gpu_kernel_matrix gives them (5 of the module docstring)."""
+    return ("grid", "forbidden") if CELLS[name][1][0][1] <= 5000 else ("grid", "grid_forbidden")
+
+
+_neg_inf_share = {}   # (cell, table kind) -> the share of -inf among the table's written rows, for the census
+
+
+@functools.lru_cache(maxsize=2)   # (one cell's two kinds: a table is up to 3.9 GB of address space, a seventh of it written)
+def _drawn(name, tkind):
+    case = table_kind_case(name, tkind, B=B, reseed=RESEED.get((name, "table/" + tkind), ""))
+    case[0].setflags(write=False)
+    case[5].setflags(write=False)
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def _table_kind_case(name, tkind):
+    """(x read-only, attributes, {push: the oracle's outputs}) of a bigram cell
+    under a table kind, on the cell's schedule.  The table is not kept with
+    them: _kind_table has it from _drawn, or draws it again."""
+    x, _, W, P, kw, tab = _drawn(name, tkind)
+    written = tab if tab.shape[1] <= scorer_tables.SPARSE_ABOVE else tab[::scorer_tables.SPARSE_STEP]
+    _neg_inf_share[name, tkind] = float(np.isneginf(written).mean())
+    pushes, check = schedule(x.shape[0])
+    after = _frames_after(pushes)
+    refs = {}
+    for k in check:
+        f = after[k]
+        try:
+            refs[k] = oracle.decode(x[:max(f)], np.array(f, np.int32), W, P, scorer_table=tab, **kw)
+        except oracle.OracleError as e:
+            raise AssertionError("%s %s: the oracle fails after push %d (frames %s): %s" % (name, tkind, k, f, e))
+    return x, kw, refs
+
+
+def _kind_table(name, tkind):
+    return _drawn(name, tkind)[5]
+
+
 # ---- 4. the census, without a GPU
 
 def test_schedules_have_the_four_properties():
@@ -232,6 +293,20 @@ def _edge_shapes(dtype, C):
     W = int(_lib.load().ctcext_max_beam_width(C, CODE[dtype]))
     assert W >= 2
     return [("edge_%s_c%d_w%d" % (dtype, C, w), C, w, t) for w, t in ((W, 0), (W + 1, 1))]
+
+
+@pytest.mark.parametrize("name", BIGRAM_CELLS)
+def test_census_bigram_table_kinds(name):
+    T = CELLS[name][1][0][0]
+    pushes, check = schedule(T)
+    for tkind in _stream_table_kinds(name):
+        x, kw, refs = _table_kind_case(name, tkind)
+        assert sorted(refs) == sorted(check)
+        if tkind == "grid_forbidden":
+            assert np.isfinite(x).all() and _neg_inf_share[name, tkind] > 0.2
+        if tkind == "forbidden":
+            assert all(_live_has_neg_inf(x, _frames_after(pushes)[-1])), name
+            assert kw["merge_repeated"] is False and _neg_inf_share[name, tkind] > 0.3
 
 
 @pytest.mark.parametrize("dtype,C", EDGE_CLASSES)
@@ -277,7 +352,8 @@ def _set_helper(monkeypatch, env):
 def _run_streams(jobs, pushes, check, W, P, dtype, tab, flags, row=None, tier=0):
     """Pushes the schedule through one stream per job (what, x, kw, refs), the
     streams taking turns push by push, and returns each stream's stats after
-    its last push.  refs None: no comparison (the census of part 2).
+    its last push.  refs None: no comparison (the census of part 2).  A job
+    with a fifth field brings its own scorer table.
 
     The streams of a call are the kinds of one shape: the same kernel and
     layout with other data and attributes.  LDS is not cleared between
@@ -286,11 +362,12 @@ def _run_streams(jobs, pushes, check, W, P, dtype, tab, flags, row=None, tier=0)
     resume left another stream's state there."""
     T, _, C = jobs[0][1].shape
     with contextlib.ExitStack() as stack:
-        streams = [stack.enter_context(ctcext_amd.StreamDecoder(B, C, W, P, max_frames=T, dtype=NP[dtype], scorer_table=tab,
-                                                                flags=flags, **kw)) for _, _, kw, _ in jobs]
+        streams = [stack.enter_context(ctcext_amd.StreamDecoder(B, C, W, P, max_frames=T, dtype=NP[dtype],
+                                                                scorer_table=job[4] if len(job) > 4 else tab,
+                                                                flags=flags, **job[2])) for job in jobs]
         at = [[0] * B for _ in jobs]
         for k, n in enumerate(pushes):
-            for s, f, (what, x, kw, refs) in zip(streams, at, jobs):
+            for s, f, (what, x, kw, refs) in zip(streams, at, (job[:4] for job in jobs)):
                 chunk = np.zeros((max(n), B, C), NP[dtype])
                 for b in range(B):
                     chunk[:n[b], b] = x[f[b]:f[b] + n[b], b]
@@ -375,6 +452,34 @@ def test_every_stream_instantiation_is_accounted_for(monkeypatch):
         assert row in _observed, cell
     assert _observed <= set(covered), sorted(_observed - set(covered))
     print("stream rows observed: %d" % len(_observed & set(covered)))
+
+
+# ---- 5. the bigram cells under the other table kinds
+
+@gpu
+@pytest.mark.parametrize("name", BIGRAM_CELLS)
+def test_stream_bigram_table_kinds(name, monkeypatch):
+    """5 of the module docstring."""
+    row, shapes, helper_env, flags, _ = _cell_shapes(name)
+    tier, dtype = row[:2]
+    _set_helper(monkeypatch, helper_env)
+    (T, C, W, P), = shapes
+    pushes, check = schedule(T)
+    jobs = [("%s table %s" % (name, tkind),) + _table_kind_case(name, tkind) + (_kind_table(name, tkind),)
+            for tkind in _stream_table_kinds(name)]
+    stats = _run_streams(jobs, pushes, check, W, P, dtype, None, flags, row, tier)
+    lengths = np.array(_frames_after(pushes)[-1], np.int32)
+    for (what, x, kw, _, tab), st in zip(jobs, stats):
+        ctcext_amd.ctc_ext_beam_search_decoder(x, lengths, W, P, flags=flags, scorer_table=tab, **kw)
+        one = ctcext_amd.get_decoder(0).last_stats
+        assert _stat_row(one["kernel"]) == row and not one["kernel"]["stream"], (what, one["kernel"])
+        print("%s: one-shot %s, stream %s" % (what, {c: one[c] for c in COUNTERS}, {c: st[c] for c in COUNTERS}))
+        if what.endswith(" table forbidden"):
+            assert one["literal_frames"] > 0, (what, one)
+        if what.endswith(" grid_forbidden"):   # (the fast path met the -inf entries)
+            assert one["literal_nonfinite"] == 0, (what, one)
+        for c in COUNTERS:
+            assert st[c] == one[c], (what, c, st[c], one[c])
 
 
 # ---- 3. the LDS tier's edges as streams

@@ -15,9 +15,21 @@ code, and a fixed-seed sweep compares the oracle with it live, item by item.
 The sweep skips only where neither the library nor the reference tree exists;
 a tree without the library is a failed build.
 
-Scope: BaseBeamScorer decodes.  gtl::TopN (the stand-in is the same
-restatement as the oracle's), the bigram scorer, the op's validation and the
-SparseTensor packing stay pinned by reading (ctc_oracle.cpp, "Pinning").
+The bigram scorer is pinned the same way.  tests/golden/reference_scorer_cases.json
+(group S) holds what the reference decoder gave with the driver's TableScorer
+in its scorer hook (oracle/ref/ref_driver.cpp: a scorer over the reference's
+default EmptyBeamState that keeps its value in a side table keyed by the state
+object's address), for tables of every kind of tests/scorer_tables.py.  Both
+oracle modes reproduce every case; a census holds the recorded data to what
+the cases exist for, from the JSON and the regenerated tables; and with the
+library a second live sweep runs random items under random tables, asserting
+on every call that the side table's argument held (no lookup without a stored
+value, no address re-expanded to another value), that the decoder never calls
+the end hooks and that it initialises the state once per Reset.
+
+Scope: gtl::TopN (the stand-in is the same restatement as the oracle's), the
+op's validation and the SparseTensor packing stay pinned by reading
+(ctc_oracle.cpp, "Pinning").
 """
 import functools
 import hashlib
@@ -32,6 +44,7 @@ import oracle
 import reference
 from parity_util import random_case
 import range_inputs
+import scorer_tables
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLDEN)
@@ -39,6 +52,9 @@ import make_reference_fixtures as gen  # noqa: E402
 
 FX = json.load(open(os.path.join(GOLDEN, "reference_cases.json")))
 CASES = FX["cases"]
+S_PATH = os.path.join(GOLDEN, "reference_scorer_cases.json")
+SFX = json.load(open(S_PATH))
+S_CASES = SFX["cases"]
 LESS = "Less leaves in the beam search than requested."
 MORE = "requested more paths than the beam width."
 
@@ -208,6 +224,144 @@ def test_group_c_fixture_is_the_references(name):
         assert gen.outputs_sha256(*_stored_outputs(v["fixture"], v["case"])) == v["reference_outputs_sha256"]
 
 
+# ---- group S: the reference under a table scorer
+
+@functools.lru_cache(maxsize=None)
+def _s_inputs(name):
+    c = S_CASES[name]["case"]
+    x, sl = gen.inputs(c)
+    tab = gen.scorer_table(c)
+    x.setflags(write=False)
+    tab.setflags(write=False)
+    return x, sl, tab
+
+
+def test_scorer_fixture_is_the_generators():
+    assert set(S_CASES) == set(gen.S_CASES)
+    for name, c in gen.S_CASES.items():
+        assert S_CASES[name]["case"] == json.loads(json.dumps(c)), name
+        assert c["group"] == "S" and c["table"] in scorer_tables.KINDS + scorer_tables.SEMANTIC
+    # recorded from the headers the first file was recorded from
+    assert SFX["reference_headers_sha256"] == FX["reference_headers_sha256"]
+    assert os.path.getsize(S_PATH) < 400 * 1000
+    # the cases the file exists for: the SMALL shapes, both dtypes, the four
+    # pairings; cfg3 at both beams under continuous and grid
+    small = {(c["T"], c["C"], c["beam_width"], c["dtype"], c["table"], c["gen"])
+             for n, c in gen.S_CASES.items() if n.startswith("S_T")}
+    want = {(T, C, W, dt, tk, kind) for (T, C, W, _) in gen._SMALL for dt in ("f32", "f64")
+            for tk, kind in (("continuous", "normal"), ("grid", "ties"), ("forbidden", "neg_inf"), ("extreme", "normal"))}
+    assert small == want and len(want) == 56
+    cfg3 = {(c["beam_width"], c["table"]) for n, c in gen.S_CASES.items() if n.startswith("S_cfg3")}
+    assert cfg3 == {(W, tk) for W in (128, 256) for tk in ("continuous", "grid")}
+    for n, c in gen.S_CASES.items():
+        if n.startswith("S_cfg3"):
+            assert (c["T"], c["C"]) == (200, 29)
+
+
+@pytest.mark.parametrize("mode", ["faithful", "shared"])
+@pytest.mark.parametrize("name", sorted(S_CASES))
+def test_oracle_reproduces_reference_under_scorer(name, mode):
+    fx = S_CASES[name]
+    c = fx["case"]
+    x, sl, tab = _s_inputs(name)
+    assert gen.sha(x) == fx["sha256"], "input stream changed"
+    assert gen.sha(tab) == fx["table_sha256"], "table stream changed"
+
+    def run():
+        return oracle.raw_decode(x, sl, c["beam_width"], c["top_paths"], mode=mode, scorer_table=tab, **gen.attrs(c))
+    if fx["error"] is not None:
+        with pytest.raises(oracle.OracleError) as e:
+            run()
+        assert str(e.value) == fx["error"]
+        return
+    dec, ali, lp, events = run()
+    assert dec == fx["decoded"]
+    assert ali == fx["alignment"]
+    assert gen.hex_rows(lp) == fx["log_probability_hex"]
+    assert events == fx["no_label"]
+
+
+def _hooks_held(hs, inits):
+    assert hs["lookups_without_state"] == 0, hs
+    assert hs["reexpansions_differ"] == 0, hs
+    assert hs["end_hook_calls"] == 0, hs
+    assert hs["initialize_state"] == inits, (hs, inits)
+
+
+def test_scorer_census():
+    """Conditions on the recorded group-S data, from the JSON and the tables
+    its seeds name (the duplicate-entry count alone needs the oracle)."""
+    assert {fx["error"] for fx in S_CASES.values()} == {None, LESS, MORE}
+    repeats = {}
+    for name, fx in S_CASES.items():
+        c = fx["case"]
+        assert c["top_paths"] <= 50
+        # the hook counters the reference reported while it recorded the case:
+        # one InitializeState for the constructor's Reset and one per item
+        # decoded (a failed TopPaths ends the call before its Reset)
+        done = c["B"] if fx["error"] is None else None
+        hs = fx["hook_stats"]
+        if done is not None:
+            _hooks_held(hs, done + 1)
+        else:
+            assert 1 <= hs["initialize_state"] <= c["B"] and hs["lookups_without_state"] == 0 \
+                and hs["reexpansions_differ"] == 0 and hs["end_hook_calls"] == 0, hs
+        if fx["error"] is not None:
+            continue
+        if c["table"] == "grid":
+            # (a row of NaN, an item that -inf left no path, repeats nothing)
+            rows = [[v for v in row if v != "nan"] for row in fx["log_probability_hex"]]
+            repeats[name] = max(len(row) - len(set(row)) for row in rows)
+        if c["table"] == "forbidden":
+            assert c["merge_repeated"] is False, name
+            tab = _s_inputs(name)[2]
+            assert np.isneginf(tab).mean() > 0.3
+            paths = [p for item in fx["decoded"] for p in item]
+            assert scorer_tables.forbidden_pairs(tab, paths) == [], name
+    print("grid cases, repeated log-probabilities in the fullest item:", repeats)
+    assert len(repeats) >= 16 + 4 and all(n >= 1 for n in repeats.values()), repeats
+    # an all-zero table is the base scorer: the recorded outputs of the group-A case
+    for name, of in gen.S_ZERO_OF.items():
+        a, z = CASES[of], S_CASES[name]
+        assert z["sha256"] == a["sha256"] and a["error"] is None
+        for k in ("decoded", "alignment", "log_probability_hex", "no_label"):
+            assert z[k] == a[k], (name, k)
+    # row 0 is the root's: with it all -inf only the empty path is left
+    for name in ("S_root_forbidden_one_path", "S_root_forbidden_f64_blank_2"):
+        fx = S_CASES[name]
+        assert fx["decoded"] == [[[]]] * fx["case"]["B"], name
+        assert fx["hook_stats"]["expand_state"] > 0 and fx["hook_stats"]["lookups"] > 0
+    assert S_CASES["S_root_forbidden_two_paths"]["error"] == LESS
+    assert S_CASES["S_root_forbidden_two_paths"]["case"]["top_paths"] == 2
+    # one successor a label: every decoded path counts up modulo C, skipping
+    # nothing (merge_repeated cannot hide a step: no label follows itself)
+    for name in ("S_chain", "S_chain_f64_blank_3"):
+        fx = S_CASES[name]
+        C = fx["case"]["C"]
+        for item in fx["decoded"]:
+            for path in item:
+                assert all(b == (a + 1) % C for a, b in zip(path, path[1:])), (name, path)
+        assert any(len(path) >= 3 for item in fx["decoded"] for path in item), name
+    assert any(fx["case"]["blank_index"] != 0 for fx in S_CASES.values())
+    assert any(fx["case"]["beam_width"] == 1 for fx in S_CASES.values())
+    assert any(fx["case"]["T"] == 1 for fx in S_CASES.values())
+    assert any(0 in fx["case"]["seq_len"] for fx in S_CASES.values())
+    # the duplicate-entry state under a grid table
+    dup_items = 0
+    for name, fx in S_CASES.items():
+        c = fx["case"]
+        if not name.startswith("S_duplicate_state"):
+            continue
+        assert c["table"] == "grid"
+        x, sl, tab = _s_inputs(name)
+        for b, n in enumerate(sl):
+            st = {}
+            oracle.raw_decode(np.ascontiguousarray(x[:n, b:b + 1]), [n], c["beam_width"], c["top_paths"], stats=st,
+                              scorer_table=tab, **gen.attrs(c))
+            dup_items += st["duplicate_frames"] > 0
+    assert dup_items >= 4, dup_items
+
+
 # ---- with the library: the reference live
 
 def _need_reference():
@@ -234,9 +388,11 @@ def test_reference_reproduces_its_own_test():
         np.testing.assert_allclose(lp, np.asarray(g["log_probability"]), rtol=1e-6, atol=1e-6)
 
 
-def _both(x, sl, W, P, kw, mode):
+def _both(x, sl, W, P, kw, mode, tab=None, hook_stats=None):
     res = []
-    for f in (lambda: oracle.raw_decode(x, sl, W, P, mode=mode, **kw), lambda: reference.raw_decode(x, sl, W, P, **kw)):
+    scored = {} if tab is None else dict(scorer_table=tab, hook_stats=hook_stats)
+    for f in (lambda: oracle.raw_decode(x, sl, W, P, mode=mode, scorer_table=tab, **kw),
+              lambda: reference.raw_decode(x, sl, W, P, **kw, **scored)):
         try:
             r = f()
             res.append((r[0], r[1], r[2].tobytes(), r[3]))
@@ -292,3 +448,60 @@ def test_live_sweep_oracle_against_reference():
         x = rng.standard_normal((T, 1, C)).astype(np.float32)
         got, want = _both(x, [T], W, P, dict(merge_repeated=True, blank_index=0, blank_label=-1), "shared")
         assert got == want and not isinstance(want, str), (T, C, W)
+
+
+def test_live_sweep_oracle_against_reference_under_scorer():
+    """About 2400 items of parity_util.random_case: the families of the sweep
+    above at 200 batches each to its 300, since drawing a table and looking
+    up the side table make an item dearer and this sweep must take no longer
+    than that one.  Each batch runs under a table of the next kind of
+    scorer_tables.KINDS, its items decoded one at a time: the oracle's
+    faithful mode and the reference with the
+    driver's TableScorer give the same labels, log-probability bits, no-label
+    counts and error messages.  On every call the hook counters show that the
+    side table held: no lookup without a stored value, no address re-expanded
+    to another value, no end-hook call, and one InitializeState for the
+    constructor's Reset plus one per item decoded.  Then the shared mode on a
+    short cfg3-shaped and a large-C item under each kind (the recorded group-S
+    cases hold both modes to the full shapes)."""
+    _need_reference()
+    items = errors = dups = expands = 0
+    by_kind = dict.fromkeys(scorer_tables.KINDS, 0)
+    for i, (fam, kwf) in enumerate(SWEEP):
+        rng = np.random.default_rng(9300 + i)
+        for j in range(200):
+            x, sl, W, P, kw = random_case(rng, **kwf)
+            kind = scorer_tables.KINDS[(i + j) % 4]
+            tab = scorer_tables.table(rng, kind, x.shape[2], x.dtype)
+            for b in range(x.shape[1]):
+                n = int(sl[b])
+                xi = np.ascontiguousarray(x[:max(n, 1), b:b + 1])
+                hs = {}
+                got, want = _both(xi, [n], W, P, kw, "faithful", tab, hs)
+                assert got == want, (fam, kind, xi.shape, W, P, kw, got, want)
+                failed = isinstance(want, str)
+                _hooks_held(hs, 1 if failed else 2)
+                items += 1
+                errors += failed
+                expands += hs["expand_state"]
+                by_kind[kind] += 1
+                if not failed and kwf.get("neg_inf"):
+                    st = {}
+                    oracle.raw_decode(xi, [n], W, P, stats=st, scorer_table=tab, **kw)
+                    dups += st["duplicate_frames"] > 0
+    print("live scorer sweep: %d items %s, %d ended in an error, %d reached the duplicate-entry state, %d ExpandState calls"
+          % (items, by_kind, errors, dups, expands))
+    assert items >= 2000 and min(by_kind.values()) >= 400 and errors >= 50 and dups >= 5, (items, by_kind, errors, dups)
+    rng = np.random.default_rng(9400)
+    for (T, C, W, P) in ((60, 29, 128, 3), (10, 300, 100, 3)):
+        for kind in scorer_tables.KINDS:
+            x = rng.standard_normal((T, 1, C))
+            if kind == "grid":
+                x = np.round(x * 2) / 2
+            x = x.astype(np.float32)
+            tab = scorer_tables.table(rng, kind, C, np.float32)
+            hs = {}
+            got, want = _both(x, [T], W, P, dict(merge_repeated=kind != "forbidden", blank_index=0, blank_label=-1),
+                              "shared", tab, hs)
+            assert got == want and not isinstance(want, str), (T, C, W, kind)
+            _hooks_held(hs, 2)
