@@ -20,6 +20,7 @@
 #include "../../include/ctcext.h"
 #define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
+#include "ctcx_skip.h"
 #include "ctcx_stable.h"
 #include "ctcx_stream_dense.h"
 #include "ctcx_times.h"
@@ -161,6 +162,7 @@ struct Dev {
   hipStream_t s = nullptr;   // stream of the current call
   hipEvent_t ev[7] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
                              // [5], [6] around the token-times kernel of a dense call
+  hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
   int64_t lo = 0, nb = 0;    // this call's shard [lo, lo + nb)
@@ -196,6 +198,7 @@ struct ctcext_decoder {
     int64_t C = 0;
     int32_t blank_index = 0, blank_label = 0, merge = 0;
     bool times_timed = false;   // events [5], [6] were recorded
+    bool skip = false;          // it was a ctcext_decode_dense_skip
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -205,6 +208,15 @@ struct ctcext_decoder {
     int32_t blank_index = 0, blank_label = 0, merge = 0;
   } tt;
   DevBuf tt_frames, tt_start, tt_end, tt_trail;
+  // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
+  // the plan, and what the call that is running reads of it
+  struct {
+    DevBuf norm, kmap, cidx, kept, xc;   // the caller's rows' normaliser [T][B]; kmap [B][T]; cidx [B][T + 1];
+                                         // kept [B]; the kept rows, dense [T][B][C] of the inputs' element type
+    bool on = false;                     // the running call skips: run_decode / dense_enqueue expand the walks
+    const int32_t* frames = nullptr;     // [B] on the device: the original lengths the expansion reads
+    int32_t blank_label = 0;
+  } skip;
 };
 
 static void release_dev(Dev& d) {
@@ -214,6 +226,8 @@ static void release_dev(Dev& d) {
                     &d.seq, &d.len, &d.phase, &d.sctab, &d.gstate, &d.dsl, &d.dstat};
   for (DevBuf* b : bufs) b->release();
   for (auto& ev : d.ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : d.sk)
     if (ev) (void)hipEventDestroy(ev);
   if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
   d.own_stream = nullptr;
@@ -257,6 +271,7 @@ extern "C" int ctcext_create_sharded(const int* devices, int n_devices, ctcext_d
       return fail(CTCEXT_INTERNAL, std::string("HIP error: ") + hipGetErrorString(e));
     }
     for (auto& ev : v.ev) (void)hipEventCreate(&ev);
+    for (auto& ev : v.sk) (void)hipEventCreate(&ev);
     // the shard inputs and the gathered walks move between the root and this
     // device by peer copies (xGMI); "already enabled" is fine
     if (v.device != devices[0]) {
@@ -282,7 +297,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail};
+                    &d->tt_trail, &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
   d->h_res.release();
@@ -674,6 +689,137 @@ static void input_strides(const ctcext_decode_args* a, int64_t& st_t, int64_t& s
   else if (B <= 1) st_b = st_t * T_;
 }
 
+// Items [v.lo, v.lo + v.nb) of inputs that v's kernels cannot read in place, as
+// a dense tensor in v.x on v's stream, and their lengths in v.sl: in the
+// inputs' own element type (halves stay 2 bytes on the way) and their own
+// dimension order -- [T][nb][C] from a time-major tensor, [nb][T][C] from a
+// batch-major one -- so that the copy is as few pieces as the strides allow.
+// st_t / st_b are the inputs' strides, es their element size; xst_t / xst_b
+// receive the copy's.
+static int stage_shard(Dev& v, const ctcext_decode_args* a, const std::vector<int32_t>& hsl, int64_t st_t,
+                       int64_t st_b, size_t es, int64_t& xst_t, int64_t& xst_b) {
+  const int64_t T_ = a->max_time, C = a->num_classes;
+  const size_t cb = (size_t)C * es;
+  HIP_OR_FAIL(v.x.ensure(cb * (size_t)v.nb * (size_t)T_ + 16));
+  HIP_OR_FAIL(v.sl.ensure(4 * (size_t)v.nb + 16));
+  const char* src = (const char*)a->inputs + (size_t)v.lo * (size_t)st_b * es;
+  const bool bmajor = st_t < st_b;
+  // outer dimension (extent no, source stride so) over inner (ni, si)
+  const int64_t no = bmajor ? v.nb : T_, ni = bmajor ? T_ : v.nb;
+  const int64_t so = bmajor ? st_b : st_t, si = bmajor ? st_t : st_b;
+  const size_t slab = cb * (size_t)ni;   // one outer index of the shard
+  if (si == C && (so == ni * C || no == 1)) {   // wholly contiguous
+    HIP_OR_FAIL(hipMemcpyAsync(v.x.p, src, slab * (size_t)no, hipMemcpyDefault, v.s));
+  } else if (si == C && so >= ni * C) {
+    // contiguous slabs (a [T][nb][C] window of a [T][B][C] tensor; the
+    // items of a batch-major tensor with padded frames): one pitched copy
+    HIP_OR_FAIL(hipMemcpy2DAsync(v.x.p, slab, src, (size_t)so * es, slab, (size_t)no, hipMemcpyDefault, v.s));
+  } else {
+    // rows apart in both dimensions (a vocabulary slice): one pitched
+    // copy of ni rows per outer index
+    for (int64_t o = 0; o < no; ++o)
+      HIP_OR_FAIL(hipMemcpy2DAsync((char*)v.x.p + (size_t)o * slab, cb, src + (size_t)o * (size_t)so * es,
+                                   (size_t)si * es, cb, (size_t)ni, hipMemcpyDefault, v.s));
+  }
+  HIP_OR_FAIL(hipMemcpyAsync(v.sl.p, hsl.data() + v.lo, 4 * (size_t)v.nb, hipMemcpyHostToDevice, v.s));
+  xst_t = bmajor ? C : v.nb * C;
+  xst_b = bmajor ? T_ * C : C;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Blank-frame skipping (ctcext.h, "Blank-frame skipping"; kernels in
+// ctcx_skip.hip).  In front of the unchanged pipeline: the normaliser of the
+// caller's rows, the plan, and the gather of the kept rows into a dense
+// tensor that enqueue_shard then decodes with the kept counts as lengths (its
+// pre-pass recomputes the normaliser of the kept rows: same rows, same bits).
+// Behind its traceback: the expansion of the alignment walks.
+
+extern "C" int ctcext_skip_validate(const ctcext_skip_args* k) {
+  if (!k) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!(k->logp_threshold <= 0))   // (NaN too)
+    return fail(CTCEXT_INVALID_ARGUMENT, "blank skip threshold must be a log-probability (<= 0)");
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// Sizes the plan's workspace (grow-only); launches nothing.
+static int skip_reserve(ctcext_decoder* d, const ctcext_decode_args* a) {
+  const size_t T_ = (size_t)a->max_time, B = (size_t)a->batch_size, C = (size_t)a->num_classes;
+  const size_t ts = a->dtype == CTCEXT_F64 ? 8 : 4;
+  const size_t es = a->inputs_format == CTCEXT_IN_NATIVE ? ts : 2;
+  HIP_OR_FAIL(d->skip.norm.ensure(ts * T_ * B));
+  HIP_OR_FAIL(d->skip.kmap.ensure(4 * T_ * B));
+  HIP_OR_FAIL(d->skip.cidx.ensure(4 * (T_ + 1) * B));
+  HIP_OR_FAIL(d->skip.kept.ensure(4 * B));
+  HIP_OR_FAIL(d->skip.xc.ensure(es * T_ * B * C + 16));
+  return CTCEXT_OK;
+}
+
+// Enqueues the normaliser, the plan and the gather over the rows at x (of
+// a->inputs_format, strides st_t / st_b) with the sanitised lengths sl and the
+// dense prologue's status words pre (or null), all on the device.  The
+// normaliser is launch_row_norm's for every num_classes: without a pre-pass
+// record it takes the row maximum in class order itself, as it does for the
+// global-state tier at any num_classes.
+template <typename T>
+static int skip_front(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k, const void* x,
+                      int64_t st_t, int64_t st_b, const int32_t* sl, const int32_t* pre, hipStream_t s) {
+  const int64_t T_ = a->max_time, B = a->batch_size, C = a->num_classes;
+  HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, a->inputs_format, sl, (T*)d->skip.norm.p, T_, B, C, st_t, st_b, s));
+  CtcxSkipPlanParams pp{};
+  pp.x = x;
+  pp.norm = d->skip.norm.p;
+  pp.seq_len = sl;
+  pp.pre = pre;
+  pp.Tmax = T_; pp.B = B; pp.xst_t = st_t; pp.xst_b = st_b;
+  pp.xfmt = a->inputs_format; pp.f64 = sizeof(T) == 8; pp.blank = a->blank_index;
+  pp.thr = (double)(T)k->logp_threshold;
+  pp.kmap = (int32_t*)d->skip.kmap.p;
+  pp.cidx = (int32_t*)d->skip.cidx.p;
+  pp.kept = (int32_t*)d->skip.kept.p;
+  pp.kept_out = a->inputs_on_device ? k->kept : nullptr;   // (host memory otherwise: copied down by the caller)
+  HIP_OR_FAIL(ctcx_launch_skip_plan(pp, s));
+  CtcxSkipGatherParams gp{};
+  gp.x = x;
+  gp.xc = d->skip.xc.p;
+  gp.kmap = pp.kmap;
+  gp.kept = pp.kept;
+  gp.Tmax = T_; gp.B = B; gp.C = C; gp.xst_t = st_t; gp.xst_b = st_b;
+  gp.esize = a->inputs_format == CTCEXT_IN_NATIVE ? (int32_t)sizeof(T) : 2;
+  HIP_OR_FAIL(ctcx_launch_skip_gather(gp, s));
+  d->skip.frames = sl;
+  d->skip.blank_label = a->blank_label;
+  return CTCEXT_OK;
+}
+
+// The arguments of the decode behind the plan: the kept rows, dense, with the
+// kept counts as lengths.
+static ctcext_decode_args skip_decode_args(const ctcext_decoder* d, const ctcext_decode_args* a) {
+  ctcext_decode_args c = *a;
+  c.inputs = d->skip.xc.p;
+  c.sequence_length = (const int32_t*)d->skip.kept.p;
+  c.inputs_on_device = 1;
+  c.inputs_stride_t = c.inputs_stride_b = 0;
+  return c;
+}
+
+// Between the traceback and scan / pack of a skipping call: the alignment
+// walks in the root's buffers, back on the original time axis.
+static int skip_expand(ctcext_decoder* d, int64_t T_, int64_t B, int P, hipStream_t s) {
+  Dev& root = d->devs[0];
+  CtcxSkipExpandParams ep{};
+  ep.seq = (int32_t*)root.seq.p;
+  ep.len = (int32_t*)root.len.p;
+  ep.frames = d->skip.frames;
+  ep.kmap = (const int32_t*)d->skip.kmap.p;
+  ep.cidx = (const int32_t*)d->skip.cidx.p;
+  ep.kept = (const int32_t*)d->skip.kept.p;
+  ep.Tmax = T_; ep.B = B; ep.P = P; ep.blank_label = d->skip.blank_label;
+  HIP_OR_FAIL(ctcx_launch_skip_expand(ep, s));
+  return CTCEXT_OK;
+}
+
 template <typename T>
 static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std::vector<int32_t>& hsl,
                       hipStream_t root_stream, int helper_mode) {
@@ -711,36 +857,10 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
       xst_t = xst_b = 0;
       sl = nullptr;
     } else {
-      // the shard's items as a dense tensor on its device, in the inputs' own
-      // element type (halves stay 2 bytes on the way) and their own dimension
-      // order: [T][nb][C] from a time-major tensor, [nb][T][C] from a
-      // batch-major one, so that the copy is as few pieces as the strides allow
-      const size_t cb = (size_t)C * es;
-      HIP_OR_FAIL(v.x.ensure(cb * (size_t)v.nb * (size_t)T_ + 16));
-      HIP_OR_FAIL(v.sl.ensure(4 * (size_t)v.nb + 16));
-      const char* src = (const char*)a->inputs + (size_t)v.lo * (size_t)st_b * es;
-      const bool bmajor = st_t < st_b;
-      // outer dimension (extent no, source stride so) over inner (ni, si)
-      const int64_t no = bmajor ? v.nb : T_, ni = bmajor ? T_ : v.nb;
-      const int64_t so = bmajor ? st_b : st_t, si = bmajor ? st_t : st_b;
-      const size_t slab = cb * (size_t)ni;   // one outer index of the shard
-      if (si == C && (so == ni * C || no == 1)) {   // wholly contiguous
-        HIP_OR_FAIL(hipMemcpyAsync(v.x.p, src, slab * (size_t)no, hipMemcpyDefault, v.s));
-      } else if (si == C && so >= ni * C) {
-        // contiguous slabs (a [T][nb][C] window of a [T][B][C] tensor; the
-        // items of a batch-major tensor with padded frames): one pitched copy
-        HIP_OR_FAIL(hipMemcpy2DAsync(v.x.p, slab, src, (size_t)so * es, slab, (size_t)no, hipMemcpyDefault, v.s));
-      } else {
-        // rows apart in both dimensions (a vocabulary slice): one pitched
-        // copy of ni rows per outer index
-        for (int64_t o = 0; o < no; ++o)
-          HIP_OR_FAIL(hipMemcpy2DAsync((char*)v.x.p + (size_t)o * slab, cb, src + (size_t)o * (size_t)so * es,
-                                       (size_t)si * es, cb, (size_t)ni, hipMemcpyDefault, v.s));
-      }
-      HIP_OR_FAIL(hipMemcpyAsync(v.sl.p, hsl.data() + v.lo, 4 * (size_t)v.nb, hipMemcpyHostToDevice, v.s));
+      // the shard's items as a dense tensor on its device
+      const int rc = stage_shard(v, a, hsl, st_t, st_b, es, xst_t, xst_b);
+      if (rc != CTCEXT_OK) return rc;
       x = v.x.p;
-      xst_t = bmajor ? C : v.nb * C;
-      xst_b = bmajor ? T_ * C : C;
       sl = (const int32_t*)v.sl.p;
     }
     int rc = enqueue_shard<T>(d, v, i == 0, a, x, a->inputs_format, xst_t, xst_b, sl, helper_mode);
@@ -778,6 +898,10 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
   HIP_OR_FAIL(d->off.ensure(8 * (size_t)(B * P * 2)));
   HIP_OR_FAIL(d->res.ensure(8 * (size_t)(P * 4)));
   HIP_OR_FAIL(d->h_kind.ensure(4 * (size_t)(B * P) + 16));
+  if (d->skip.on) {   // (a helper-timeout re-decode comes through here again, over the same plan)
+    const int rc = skip_expand(d, T_, B, P, s);
+    if (rc != CTCEXT_OK) return rc;
+  }
   HIP_OR_FAIL(ctcx::launch_scan((const int32_t*)root.len.p, (int64_t*)d->off.p, (int64_t*)d->res.p, B, P, s));
   HIP_OR_FAIL(hipMemcpyAsync(d->h_item.p, root.item.p, sizeof(ctcx::ItemOut) * (size_t)B, hipMemcpyDeviceToHost, s));
   HIP_OR_FAIL(hipMemcpyAsync(d->h_res.p, d->res.p, 8 * (size_t)(P * 4), hipMemcpyDeviceToHost, s));
@@ -833,12 +957,54 @@ static int run_decode(ctcext_decoder* d, const ctcext_decode_args* a, const std:
   return CTCEXT_OK;
 }
 
-extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args* a, ctcext_path_sizes* sizes) {
+// The plan of a synchronous skipping call and the decode behind it.  Host
+// inputs are staged on the device first, as a shard is; device inputs are read
+// in place.  The kept counts come down to the host afterwards (the call has
+// waited by then).
+template <typename T>
+static int run_decode_skip(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k,
+                           const std::vector<int32_t>& hsl, hipStream_t s, int helper_mode) {
+  const int64_t B = a->batch_size;
+  Dev& root = d->devs[0];
+  int rc = skip_reserve(d, a);
+  if (rc != CTCEXT_OK) return rc;
+  const void* x = a->inputs;
+  const int32_t* sl = a->sequence_length;
+  int64_t st_t, st_b;
+  input_strides(a, st_t, st_b);
+  if (!a->inputs_on_device) {
+    root.lo = 0;
+    root.nb = B;
+    root.s = s;
+    const size_t es = a->inputs_format == CTCEXT_IN_NATIVE ? sizeof(T) : 2;
+    rc = stage_shard(root, a, hsl, st_t, st_b, es, st_t, st_b);
+    if (rc != CTCEXT_OK) return rc;
+    x = root.x.p;
+    sl = (const int32_t*)root.sl.p;
+  }
+  rc = skip_front<T>(d, a, k, x, st_t, st_b, sl, nullptr, s);
+  if (rc != CTCEXT_OK) return rc;
+  const ctcext_decode_args c = skip_decode_args(d, a);
+  d->skip.on = true;
+  rc = run_decode<T>(d, &c, hsl, s, helper_mode);
+  d->skip.on = false;
+  if (rc != CTCEXT_OK) return rc;
+  if (k->kept && !a->inputs_on_device)   // (with device inputs the plan kernel wrote the caller's copy)
+    HIP_OR_FAIL(hipMemcpy(k->kept, d->skip.kept.p, 4 * (size_t)B, hipMemcpyDeviceToHost));
+  return CTCEXT_OK;
+}
+
+// ctcext_decode_sharded, and with k ctcext_decode_skip.
+static int decode_sync(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k,
+                       ctcext_path_sizes* sizes) {
   if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   d->have = false;
   d->dense.have = false;   // (the workspace ctcext_dense_check reads is this call's now)
   int rc = validate_shapes(a);
+  if (rc == CTCEXT_OK && k) rc = ctcext_skip_validate(k);
   if (rc != CTCEXT_OK) return rc;
+  if (k && d->devs.size() != 1)
+    return fail(CTCEXT_UNIMPLEMENTED, "blank-frame skipping needs a one-device decoder handle");
   DeviceGuard guard;
   Dev& root = d->devs[0];
   HIP_OR_FAIL(hipSetDevice(root.device));
@@ -877,8 +1043,12 @@ extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args
   d->stats = ctcext_stats{};
   if (B > 0) {
     const int helper_mode = helper_mode_from_env();
-    rc = (a->dtype == CTCEXT_F32) ? run_decode<float>(d, a, hsl, s, helper_mode)
-                                  : run_decode<double>(d, a, hsl, s, helper_mode);
+    if (k)
+      rc = (a->dtype == CTCEXT_F32) ? run_decode_skip<float>(d, a, k, hsl, s, helper_mode)
+                                    : run_decode_skip<double>(d, a, k, hsl, s, helper_mode);
+    else
+      rc = (a->dtype == CTCEXT_F32) ? run_decode<float>(d, a, hsl, s, helper_mode)
+                                    : run_decode<double>(d, a, hsl, s, helper_mode);
     if (rc != CTCEXT_OK) return rc;
     const int64_t* r = (const int64_t*)d->h_res.p;
     for (int p = 0; p < P; ++p) {
@@ -901,8 +1071,18 @@ extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args
   return CTCEXT_OK;
 }
 
+extern "C" int ctcext_decode_sharded(ctcext_decoder* d, const ctcext_decode_args* a, ctcext_path_sizes* sizes) {
+  return decode_sync(d, a, nullptr, sizes);
+}
+
 extern "C" int ctcext_decode(ctcext_decoder* d, const ctcext_decode_args* a, ctcext_path_sizes* sizes) {
-  return ctcext_decode_sharded(d, a, sizes);
+  return decode_sync(d, a, nullptr, sizes);
+}
+
+extern "C" int ctcext_decode_skip(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k,
+                                  ctcext_path_sizes* sizes) {
+  if (!k) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  return decode_sync(d, a, k, sizes);
 }
 
 extern "C" int ctcext_fetch(ctcext_decoder* d, const ctcext_outputs* o) {
@@ -1010,9 +1190,14 @@ extern "C" int ctcext_dense_validate(const ctcext_decode_args* a, const ctcext_d
 // The workspace of a dense call and its plan; launches nothing.  Sized as the
 // synchronous path sizes it (plan_shard over the whole batch on the root),
 // plus the prologue's words and the pinned buffers ctcext_dense_check fills.
+// With skip, the plan's workspace too.
 template <typename T>
-static int dense_plan(ctcext_decoder* d, const ctcext_decode_args* a, int helper_mode, ShardPlan<T>& pl) {
+static int dense_plan(ctcext_decoder* d, const ctcext_decode_args* a, bool skip, int helper_mode, ShardPlan<T>& pl) {
   const int64_t B = a->batch_size;
+  if (skip) {
+    const int rc = skip_reserve(d, a);
+    if (rc != CTCEXT_OK) return rc;
+  }
   Dev& root = d->devs[0];
   int64_t st_t, st_b;
   input_strides(a, st_t, st_b);
@@ -1038,9 +1223,11 @@ static int dense_begin(ctcext_decoder* d, const ctcext_decode_args* a, hipStream
   return CTCEXT_OK;
 }
 
-extern "C" int ctcext_dense_reserve(ctcext_decoder* d, const ctcext_decode_args* a) {
+// ctcext_dense_reserve, and with k ctcext_dense_reserve_skip.
+static int dense_reserve(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k) {
   if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   int rc = validate_shapes(a);
+  if (rc == CTCEXT_OK && k) rc = ctcext_skip_validate(k);
   if (rc == CTCEXT_OK) rc = check_limits(a);
   if (rc == CTCEXT_OK) rc = check_layout(a);
   if (rc != CTCEXT_OK) return rc;
@@ -1054,24 +1241,33 @@ extern "C" int ctcext_dense_reserve(ctcext_decoder* d, const ctcext_decode_args*
   const int helper_mode = helper_mode_from_env();
   if (a->dtype == CTCEXT_F32) {
     ShardPlan<float> pl;
-    rc = dense_plan<float>(d, a, helper_mode, pl);
+    rc = dense_plan<float>(d, a, k != nullptr, helper_mode, pl);
   } else {
     ShardPlan<double> pl;
-    rc = dense_plan<double>(d, a, helper_mode, pl);
+    rc = dense_plan<double>(d, a, k != nullptr, helper_mode, pl);
   }
   d->B = B0;
   if (rc == CTCEXT_OK) g_err.clear();
   return rc;
 }
 
+extern "C" int ctcext_dense_reserve(ctcext_decoder* d, const ctcext_decode_args* a) {
+  return dense_reserve(d, a, nullptr);
+}
+
+extern "C" int ctcext_dense_reserve_skip(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k) {
+  if (!k) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  return dense_reserve(d, a, k);
+}
+
 template <typename T>
-static int dense_enqueue(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_dense_outputs* o,
-                         int helper_mode) {
+static int dense_enqueue(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k,
+                         const ctcext_dense_outputs* o, int helper_mode) {
   const int64_t T_ = a->max_time, B = a->batch_size, C = a->num_classes;
   Dev& root = d->devs[0];
   hipStream_t s = root.s;
   ShardPlan<T> pl;
-  int rc = dense_plan<T>(d, a, helper_mode, pl);   // (nothing to grow after a reserve or a call of this shape)
+  int rc = dense_plan<T>(d, a, k != nullptr, helper_mode, pl);   // (nothing to grow after a reserve or a call of this shape)
   if (rc != CTCEXT_OK) return rc;
   int32_t* const pre = (int32_t*)root.dstat.p;
   int32_t* const fin = pre + B;
@@ -1085,7 +1281,22 @@ static int dense_enqueue(ctcext_decoder* d, const ctcext_decode_args* a, const c
                                           sizeof(T) == 8, fin + B, s));
   int64_t st_t, st_b;
   input_strides(a, st_t, st_b);
-  rc = enqueue_shard<T>(d, root, true, a, a->inputs, a->inputs_format, st_t, st_b, pp.sl, helper_mode);
+  if (k) {
+    // the plan over the caller's rows and the prologue's lengths (which stay
+    // in dsl for the token times), then the pipeline over the kept rows
+    const bool prof = (a->flags & CTCEXT_FLAG_PROFILE) != 0;
+    if (prof) HIP_OR_FAIL(hipEventRecord(root.sk[0], s));
+    rc = skip_front<T>(d, a, k, a->inputs, st_t, st_b, pp.sl, pre, s);
+    if (rc != CTCEXT_OK) return rc;
+    const ctcext_decode_args c = skip_decode_args(d, a);
+    input_strides(&c, st_t, st_b);
+    rc = enqueue_shard<T>(d, root, true, &c, c.inputs, c.inputs_format, st_t, st_b, (const int32_t*)c.sequence_length,
+                          helper_mode);
+    if (rc == CTCEXT_OK) rc = skip_expand(d, T_, B, a->top_paths, s);
+    if (rc == CTCEXT_OK && prof) HIP_OR_FAIL(hipEventRecord(root.sk[1], s));
+  } else {
+    rc = enqueue_shard<T>(d, root, true, a, a->inputs, a->inputs_format, st_t, st_b, pp.sl, helper_mode);
+  }
   if (rc != CTCEXT_OK) return rc;
   ctcx::PackDenseParams pd{};
   pd.seq = (const int32_t*)root.seq.p;
@@ -1105,11 +1316,14 @@ static int dense_enqueue(ctcext_decoder* d, const ctcext_decode_args* a, const c
   return CTCEXT_OK;
 }
 
-extern "C" int ctcext_decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_dense_outputs* o) {
+// ctcext_decode_dense, and with k ctcext_decode_dense_skip.
+static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k,
+                        const ctcext_dense_outputs* o) {
   if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   d->have = false;
   d->dense.have = false;
   int rc = ctcext_dense_validate(a, o);
+  if (rc == CTCEXT_OK && k) rc = ctcext_skip_validate(k);
   if (rc != CTCEXT_OK) return rc;
   hipStream_t s;
   rc = dense_begin(d, a, &s);
@@ -1123,8 +1337,8 @@ extern "C" int ctcext_decode_dense(ctcext_decoder* d, const ctcext_decode_args* 
   d->stats = ctcext_stats{};
   if (a->batch_size > 0) {
     const int helper_mode = helper_mode_from_env();
-    rc = a->dtype == CTCEXT_F32 ? dense_enqueue<float>(d, a, o, helper_mode)
-                                : dense_enqueue<double>(d, a, o, helper_mode);
+    rc = a->dtype == CTCEXT_F32 ? dense_enqueue<float>(d, a, k, o, helper_mode)
+                                : dense_enqueue<double>(d, a, k, o, helper_mode);
     if (rc != CTCEXT_OK) return rc;
     // what the host knows; ctcext_dense_check fills the counters
     d->stats.tier = use_gstate(a) ? 1 : 0;
@@ -1141,8 +1355,19 @@ extern "C" int ctcext_decode_dense(ctcext_decoder* d, const ctcext_decode_args* 
   d->dense.C = a->num_classes; d->dense.blank_index = a->blank_index; d->dense.blank_label = a->blank_label;
   d->dense.merge = a->merge_repeated ? 1 : 0;
   d->dense.times_timed = false;
+  d->dense.skip = k != nullptr;
   g_err.clear();
   return CTCEXT_OK;
+}
+
+extern "C" int ctcext_decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_dense_outputs* o) {
+  return decode_dense(d, a, nullptr, o);
+}
+
+extern "C" int ctcext_decode_dense_skip(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_skip_args* k,
+                                        const ctcext_dense_outputs* o) {
+  if (!k) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  return decode_dense(d, a, k, o);
 }
 
 extern "C" int ctcext_dense_check(ctcext_decoder* d) {
@@ -1203,6 +1428,22 @@ extern "C" int ctcext_dense_check(ctcext_decoder* d) {
   const int32_t* kinds = (const int32_t*)d->h_kind.p;
   for (int64_t q = 0; q < B * P; ++q) d->stats.no_label_paths += (kinds[q] < 0) ? 1 : 0;
   g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_skip_ms(ctcext_decoder* d, double* front_ms, double* expand_ms) {
+  if (!d || !front_ms || !expand_ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.skip || !(d->dense.flags & CTCEXT_FLAG_PROFILE) || d->dense.B == 0)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE skipping dense decode yet");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.sk[1]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.sk[0], root.ev[0]));
+  *front_ms = f;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[3], root.sk[1]));
+  *expand_ms = f;
   return CTCEXT_OK;
 }
 

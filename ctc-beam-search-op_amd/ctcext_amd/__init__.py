@@ -5,11 +5,11 @@ tracking; a drop-in for prouast/ctc-beam-search-op's
 from .ops import (CTCExtBeamSearchDecoder, Decoder, DenseDecode, FailedPreconditionError, InternalError,
                   InvalidArgumentError, OpError, StablePrefix, StreamDecoder, StreamDense, TokenTimes,
                   UnimplementedError, ctc_ext_beam_search_decoder, decode_dense, decode_logits, dense_check,
-                  dense_token_times, get_decoder, token_times, token_times_row)
+                  dense_token_times, get_decoder, kept_frames, token_times, token_times_row)
 
 __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "StablePrefix", "StreamDense",
            "decode_dense", "dense_check", "DenseDecode",
-           "dense_token_times", "token_times", "token_times_row", "TokenTimes",
+           "dense_token_times", "token_times", "token_times_row", "TokenTimes", "kept_frames",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

@@ -59,6 +59,11 @@ TOKEN_TIMES_SYMBOLS = ("ctcext_token_times_validate", "ctcext_token_times_tile",
                        "ctcext_stream_token_times", "ctcext_fetch_token_times", "ctcext_token_times_row",
                        "ctcext_dense_token_times_ms", "ctcext_stream_token_times_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TOKEN_TIMES_SYMBOLS
+# blank-frame skipping (CTCEXT_HAS_BLANK_SKIP)
+BLANK_SKIP_SYMBOLS = ("ctcext_skip_validate", "ctcext_decode_skip", "ctcext_dense_reserve_skip",
+                      "ctcext_decode_dense_skip", "ctcext_dense_skip_ms", "ctcext_skip_plan_row",
+                      "ctcext_skip_expand_row")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + BLANK_SKIP_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -115,6 +120,11 @@ class DenseOutputs(ctypes.Structure):
 class TokenTimesOut(ctypes.Structure):
     """ctcext_token_times: the outputs of the token-times calls."""
     _fields_ = [("start", ctypes.c_void_p), ("end", ctypes.c_void_p), ("trailing_blank", ctypes.c_void_p)]
+
+
+class SkipArgs(ctypes.Structure):
+    """ctcext_skip_args: the threshold of a skipping decode and where its kept counts go."""
+    _fields_ = [("logp_threshold", ctypes.c_double), ("kept", ctypes.c_void_p)]
 
 
 class StreamDenseOutputs(ctypes.Structure):
@@ -292,6 +302,31 @@ def load():
         lib.ctcext_dense_token_times_ms.restype = ctypes.c_int
         lib.ctcext_stream_token_times_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_stream_token_times_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_decode_skip"):   # (CTCEXT_HAS_BLANK_SKIP; older builds stay loadable for A/B runs)
+        lib.ctcext_skip_validate.argtypes = [ctypes.POINTER(SkipArgs)]
+        lib.ctcext_skip_validate.restype = ctypes.c_int
+        lib.ctcext_decode_skip.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs), ctypes.POINTER(SkipArgs),
+                                           ctypes.POINTER(PathSizes)]
+        lib.ctcext_decode_skip.restype = ctypes.c_int
+        lib.ctcext_dense_reserve_skip.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs),
+                                                  ctypes.POINTER(SkipArgs)]
+        lib.ctcext_dense_reserve_skip.restype = ctypes.c_int
+        lib.ctcext_decode_dense_skip.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs),
+                                                 ctypes.POINTER(SkipArgs), ctypes.POINTER(DenseOutputs)]
+        lib.ctcext_decode_dense_skip.restype = ctypes.c_int
+        lib.ctcext_dense_skip_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_skip_ms.restype = ctypes.c_int
+        # (logp_blank[n] of the compute dtype, f64, n, thr, int32 kmap[n], int64* kept)
+        lib.ctcext_skip_plan_row.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]
+        lib.ctcext_skip_plan_row.restype = ctypes.c_int
+        # (int64 ali_c[L], L, int32 kmap[kept], kept, n, blank_label, int64 row[n], int64* row_len)
+        lib.ctcext_skip_expand_row.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                               ctypes.POINTER(ctypes.c_int64)]
+        lib.ctcext_skip_expand_row.restype = ctypes.c_int
     _lib = lib
     return lib
 

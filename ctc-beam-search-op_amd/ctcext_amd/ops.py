@@ -119,10 +119,13 @@ class Decoder:
         return st
 
     # -- phase 1 ---------------------------------------------------------
-    def decode(self, args):
+    def decode(self, args, skip=None):
         P = max(int(args.top_paths), 1)
         sizes = (_lib.PathSizes * P)()
-        rc = self.lib.ctcext_decode_sharded(self.handle, ctypes.byref(args), sizes)
+        if skip is None:
+            rc = self.lib.ctcext_decode_sharded(self.handle, ctypes.byref(args), sizes)
+        else:   # a _lib.SkipArgs: blank-frame skipping
+            rc = self.lib.ctcext_decode_skip(self.handle, ctypes.byref(args), ctypes.byref(skip), sizes)
         if rc != _lib.CTCEXT_OK:
             _raise(self.lib, rc)
         self.last_stats = self.stats()
@@ -189,6 +192,20 @@ def _current_device():
     return 0
 
 
+def _skip_args(lib, skip_blank):
+    """The ctcext_skip_args of ``skip_blank`` (a log-probability threshold),
+    checked on the host; its ``kept`` pointer is left to the caller."""
+    if not hasattr(lib, "ctcext_decode_skip"):
+        raise UnimplementedError("this libctcext.so has no blank-frame skipping (CTCEXT_HAS_BLANK_SKIP)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    k = _lib.SkipArgs()
+    k.logp_threshold = float(skip_blank)
+    rc = lib.ctcext_skip_validate(ctypes.byref(k))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return k
+
+
 def _args(x_ptr, shape, dtype_code, on_device, sl_ptr, sl_shape, beam_width, top_paths, merge_repeated,
           blank_index, blank_label, flags, stream):
     a = _lib.DecodeArgs()
@@ -213,7 +230,8 @@ def _args(x_ptr, shape, dtype_code, on_device, sl_ptr, sl_shape, beam_width, top
 
 def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
                                 merge_repeated=False, blank_index=0, blank_label=-1,
-                                name=None, *, flags=0, outputs="auto", devices=None, scorer_table=None):
+                                name=None, *, flags=0, outputs="auto", devices=None, scorer_table=None,
+                                skip_blank=None):
     """Drop-in for the reference op.  See the module docstring.
 
     Keyword-only extensions (not in the reference):
@@ -229,6 +247,14 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
         b adds table[a + 1, b] to the score it extends.  The reference op
         always uses the identity scorer (kernels.cc:260), which None selects.
       flags: CTCEXT_FLAG_* diagnostics.
+      skip_blank: None, or a log-probability threshold (<= 0) for blank-frame
+        skipping (include/ctcext.h, "Blank-frame skipping"): a frame whose
+        blank log-probability is above it, directly after another such frame,
+        is dropped before the decode.  The outputs are the decode's of the
+        kept frames, with the alignments put back on the original time axis
+        (dropped frames read blank_label); log_probability is that of the kept
+        frames, not corrected for the dropped ones.  ``kept_frames()`` returns
+        the frames kept per item.  One device only.
     """
     del name
     if outputs not in ("auto", "host", "device"):
@@ -268,7 +294,8 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
     a = _args(x_ptr, shape, code, on_device, sl_ptr, sl_shape, beam_width, top_paths, merge_repeated,
               blank_index, blank_label, flags, stream)
     return _decode_and_fetch(lib, a, keep, shape, on_device, x.device if on_device else None,
-                             x.dtype if on_device else np.dtype(x.dtype), index, outputs, devices, scorer_table)
+                             x.dtype if on_device else np.dtype(x.dtype), index, outputs, devices, scorer_table,
+                             skip_blank)
 
 
 def logits_layout(shape, strides, batch_first=True):
@@ -301,7 +328,7 @@ def logits_layout(shape, strides, batch_first=True):
 
 def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
                   merge_repeated=False, blank_index=0, blank_label=-1,
-                  flags=0, outputs="auto", devices=None, scorer_table=None):
+                  flags=0, outputs="auto", devices=None, scorer_table=None, skip_blank=None):
     """Decode the logits tensor an acoustic model produces, as it is.
 
     ``logits`` is a torch tensor of dtype float16, bfloat16, float32 or
@@ -313,8 +340,9 @@ def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
     otherwise it is made contiguous first.  Half-precision logits are widened
     to float32 as the kernels read them, which is exact: the result is that of
     ``ctc_ext_beam_search_decoder(logits.float().transpose(0, 1), ...)``, and
-    ``log_probability`` is float32.  The other arguments and the returned
-    ``CTCExtBeamSearchDecoder`` tuple are the drop-in function's.
+    ``log_probability`` is float32.  The other arguments (``skip_blank``
+    among them) and the returned ``CTCExtBeamSearchDecoder`` tuple are the
+    drop-in function's.
     """
     if outputs not in ("auto", "host", "device"):
         raise ValueError("outputs must be 'auto', 'host' or 'device'")
@@ -366,7 +394,7 @@ def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
     a.inputs_format = fmt
     a.inputs_stride_t, a.inputs_stride_b = int(st_t), int(st_b)
     return _decode_and_fetch(lib, a, [x, sl], shape, on_device, dev, table_dtype, index, outputs, devices,
-                             scorer_table)
+                             scorer_table, skip_blank)
 
 
 DenseDecode = collections.namedtuple(
@@ -376,7 +404,7 @@ DenseDecode = collections.namedtuple(
 
 def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
                  merge_repeated=False, blank_index=0, blank_label=-1, pad_value=-1,
-                 flags=0, scorer_table=None, out=None):
+                 flags=0, scorer_table=None, out=None, skip_blank=None):
     """Decode GPU logits into padded GPU tensors without waiting for anything.
 
     The call validates what it can on the host, enqueues the whole decode on
@@ -406,8 +434,13 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
     its rows empty -- lengths 0, rows all ``pad_value``, ``log_probability``
     ``-inf`` -- and the other items are untouched by it.  ``dense_check()``
     waits and raises what the synchronous call would have raised.
+
+    ``skip_blank`` is ``ctc_ext_beam_search_decoder``'s: with it the call is
+    still enqueue-only, alignment rows stay ``T`` wide, and ``kept_frames()``
+    returns an int32 CUDA tensor this call writes without waiting.
     """
     lib = _lib.load()
+    skip = None if skip_blank is None else _skip_args(lib, skip_blank)
     if not (_is_torch(logits) and logits.is_cuda):
         raise ValueError("decode_dense takes CUDA torch tensors; use decode_logits for host inputs")
     import torch
@@ -470,9 +503,16 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
      o.status) = [t.data_ptr() for t in out]
     o.pad_value = int(pad_value)
     dec = get_decoder(index)
-    rc = lib.ctcext_decode_dense(dec.handle, ctypes.byref(a), ctypes.byref(o))
+    if skip is None:
+        rc = lib.ctcext_decode_dense(dec.handle, ctypes.byref(a), ctypes.byref(o))
+    else:
+        with torch.cuda.device(dev):
+            kept = torch.empty((B,), dtype=torch.int32, device=dev)
+        skip.kept = kept.data_ptr()
+        rc = lib.ctcext_decode_dense_skip(dec.handle, ctypes.byref(a), ctypes.byref(skip), ctypes.byref(o))
     if rc != _lib.CTCEXT_OK:
         _raise(lib, rc)
+    dec._kept = None if skip is None else kept
     dec.last_stats = dec.stats()
     dec._times_dense = (B, P, T, dev)   # (dense_token_times' output shapes)
     # x, sl and tab may be temporaries: they were allocated on this stream, and
@@ -569,6 +609,19 @@ def token_times(device=None):
     return out
 
 
+def kept_frames(device=None):
+    """The frames each item kept in the calling thread's last decode with
+    ``skip_blank`` on ``device`` (None: the current one): a numpy int32 ``[B]``
+    after ``ctc_ext_beam_search_decoder`` / ``decode_logits``, an int32 CUDA
+    tensor after ``decode_dense`` (written by that call in stream order; an
+    item with a status bit known before the decode keeps 0)."""
+    what = "kept_frames without a decode with skip_blank"
+    kept = getattr(_thread_decoder(device, what), "_kept", None)
+    if kept is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    return kept
+
+
 def token_times_row(decoded, alignment, frames, blank_label, merge_repeated=False):
     """The definition of the token times for one row, on the host (no GPU):
     ``decoded`` and ``alignment`` are one path's label and alignment rows in
@@ -632,13 +685,15 @@ def _lengths_host(sequence_length):
     return np.ascontiguousarray(sl_arr.astype(np.int32))
 
 
-def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index, outputs, devices, scorer_table):
+def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index, outputs, devices, scorer_table,
+                      skip_blank=None):
     """Everything after the inputs are described by ``a``: validation, the
     beam-scorer table, the handle, phase 1, output allocation and phase 2.
     ``shape`` is the logical (max_time, batch, num_classes); ``table_dtype``
     the compute dtype (torch for device inputs, numpy for host inputs), in
     which the scorer table is passed and log_probability comes back."""
     code, top_paths = a.dtype, a.top_paths
+    skip = None if skip_blank is None else _skip_args(lib, skip_blank)
     # the reference's shape/length checks run behind the C ABI, before any
     # device work (kernels.cc:97-139)
     rc = lib.ctcext_validate(ctypes.byref(a))
@@ -678,7 +733,21 @@ def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index
         # waited for, so it is, here
         import torch
         torch.cuda.current_stream(device).synchronize()
-    sizes = dec.decode(a)
+    dec._kept = None
+    if skip is not None:
+        # the kept counts: device memory for device inputs, host memory otherwise
+        nb = max(int(shape[1]), 0) if len(shape) == 3 else 0
+        if on_device:
+            import torch
+            with torch.cuda.device(device):
+                kept = torch.zeros((nb,), dtype=torch.int32, device=device)
+            skip.kept = kept.data_ptr()
+        else:
+            kept = np.zeros((nb,), np.int32)
+            skip.kept = kept.ctypes.data
+    sizes = dec.decode(a, skip)
+    if skip is not None:
+        dec._kept = kept.cpu().numpy() if on_device else kept
     to_device = outputs == "device" or (outputs == "auto" and on_device)
     dec._times_sync = (int(shape[1]), int(top_paths), int(shape[0]), to_device)   # (token_times' output shapes)
     out = _fetch_outputs(dec, sizes, int(shape[1]), int(top_paths), code, to_device)

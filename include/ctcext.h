@@ -691,6 +691,91 @@ int ctcext_token_times_row(const int64_t* decoded, int64_t m, const int64_t* ali
 int ctcext_dense_token_times_ms(ctcext_decoder* dec, double* ms);
 int ctcext_stream_token_times_ms(ctcext_stream* s, double* ms);
 
+/* ---------------------------------------------------------------------------
+ * Blank-frame skipping: runs of blank-dominant frames are dropped in front of
+ * the decode, and the alignment is put back on the original time axis behind
+ * it.  Opt-in: new entry points and one new struct only (CTCEXT_ABI_VERSION,
+ * ctcext_decode_args and ctcext_stats are unchanged; detect the feature by
+ * CTCEXT_HAS_BLANK_SKIP at build time or by symbol at run time).  Without
+ * these entry points every call does what it did.
+ *
+ * Definition.  thr is a log-probability (<= 0, not NaN), converted once to
+ * the compute dtype.  For item b with n frames (its sanitised length):
+ *
+ *   def skip_plan(logp_blank, n, thr):   # logp_blank[t] = x[t, b, blank_index] - norm[t, b], in the compute
+ *       dom = [logp_blank[t] > thr for t in range(n)]     # dtype; norm is the decoder's own normaliser
+ *       return [t for t in range(n) if not (t > 0 and dom[t] and dom[t - 1])]   # kmap: the frames kept
+ *
+ *   def skip_expand(ali_c, kmap, n, blank_label):   # ali_c: an alignment row of the compacted decode (a
+ *       L = len(ali_c)                              # suffix: it covers the last L kept frames)
+ *       if L == 0: return []
+ *       k = kmap[len(kmap) - L:]
+ *       row = [blank_label] * (n - k[0])
+ *       for v, f in zip(ali_c, k): row[f - k[0]] = v
+ *       return row
+ *
+ * A frame is dropped when it and the frame before it in the original sequence
+ * are both blank-dominant (whether or not that neighbour was kept): the first
+ * frame of every blank run stays, so two equal labels either side of a run
+ * stay two labels, and frame 0 always stays.  A comparison with NaN is false:
+ * a row with NaN or +inf, or with a -inf blank, is kept.  thr = 0 keeps every
+ * frame, because x - norm is never above 0 (norm = max + log(sum of
+ * exp(x - max)), and the sum holds the term exp(0) = 1, so norm >= max >= x in
+ * exact and in rounded arithmetic alike: log of a value >= 1 is >= 0).
+ *
+ * The outputs.  Decoded rows, log_probability and errors are the plain
+ * decode's of the tensor that holds item b's frames kmap_b with length
+ * len(kmap_b); "Less leaves in the beam search than requested." is judged on
+ * that compacted item.  log_probability is the compacted sequence's: it is
+ * NOT corrected for the dropped frames.  Each alignment row is skip_expand of
+ * the compacted row: it lies on the original time axis, is at most n long,
+ * and dropped frames read blank_label; alignment_shape and max_alignment
+ * follow the expanded rows, dense rows stay max_time wide.  Token times after
+ * a skipping decode are the definition above applied to the expanded rows,
+ * with the original n as frames.
+ *
+ * Cost: a second logits-sized workspace buffer (the kept rows, in the inputs'
+ * own element type) beside the normaliser, the frame map and the kept counts.
+ *
+ * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED), and
+ * streams. */
+#define CTCEXT_HAS_BLANK_SKIP 1
+
+typedef struct {
+  double logp_threshold;    /* thr above */
+  int32_t* kept;            /* optional [batch]: frames kept per item (0 for an item with a prologue status bit);
+                               a device pointer for the dense form and for device inputs, host memory otherwise */
+} ctcext_skip_args;
+
+/* Host only, no HIP call: a threshold above 0 or NaN fails with
+ * CTCEXT_INVALID_ARGUMENT "blank skip threshold must be a log-probability (<= 0)". */
+int ctcext_skip_validate(const ctcext_skip_args* skip);
+/* ctcext_decode with the rule above (synchronous).  ctcext_fetch and
+ * ctcext_fetch_token_times then work as after ctcext_decode. */
+int ctcext_decode_skip(ctcext_decoder* dec, const ctcext_decode_args* args, const ctcext_skip_args* skip,
+                       ctcext_path_sizes* sizes);
+/* ctcext_dense_reserve / ctcext_decode_dense with the rule above, under
+ * exactly their contract (enqueue-only, capturable after a reserve or a call
+ * of the same shape).  ctcext_dense_check and ctcext_dense_token_times work
+ * after them; a length error still reports the original max_time. */
+int ctcext_dense_reserve_skip(ctcext_decoder* dec, const ctcext_decode_args* args, const ctcext_skip_args* skip);
+int ctcext_decode_dense_skip(ctcext_decoder* dec, const ctcext_decode_args* args, const ctcext_skip_args* skip,
+                             const ctcext_dense_outputs* out);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the flags of the last
+ * ctcext_decode_dense_skip, the time in ms of what it enqueued in front of the
+ * pipeline (normaliser of the caller's rows, plan, gather) and of the
+ * expansion.  Waits for them.  The pack time of ctcext_dense_pack_ms includes
+ * the expansion after such a call. */
+int ctcext_dense_skip_ms(ctcext_decoder* dec, double* front_ms, double* expand_ms);
+/* Host only, no HIP call: skip_plan and skip_expand for one row, in plain C++
+ * that shares no code with the kernels.  logp_blank holds n values of the
+ * compute dtype (f64: doubles, else floats) and thr is converted to it; kmap
+ * has room for n entries, *kept receives their count.  ali_c holds L <= kept
+ * values, row has room for n, *row_len receives the expanded length. */
+int ctcext_skip_plan_row(const void* logp_blank, int32_t f64, int64_t n, double thr, int32_t* kmap, int64_t* kept);
+int ctcext_skip_expand_row(const int64_t* ali_c, int64_t L, const int32_t* kmap, int64_t kept, int64_t n,
+                           int64_t blank_label, int64_t* row, int64_t* row_len);
+
 #ifdef __cplusplus
 }
 #endif
