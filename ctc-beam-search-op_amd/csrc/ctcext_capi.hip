@@ -1502,6 +1502,21 @@ struct ctcext_stream {
                                         // the deferred record (CtcxStreamAcc), stable's walked
     HostBuf land;              // the check's landing buffer: frames | acc | ItemOut | top_kind
   } dn;
+  // Blank-frame skipping (ctcext_stream_open_skip; ctcext.h, "Streaming:
+  // blank-frame skipping"): the plan's state per item and the workspace of the
+  // chunk in front of the pre-pass, the stream's own like dn.
+  struct {
+    bool on = false;
+    double thr = 0;            // rounded to the compute dtype
+    int32_t* kept_out = nullptr;   // the caller's device [B], or null
+    DevBuf item;               // [B] CtcxSkipItem
+    DevBuf kmap, cidx;         // [B][max_frames], [B][max_frames + 1]
+    DevBuf nfr;                // [B] int32: n per item after the last push
+    DevBuf norm, ckmap, klen, xc;   // of the chunk: the caller's rows' normaliser, the gather's map, the kept
+                                    // lengths, the kept rows [chunk_time][B][C] in the chunk's element type
+    HostBuf land;              // stream_settle's: the items
+  } sk;
+  std::vector<int64_t> kept;   // host mirror of the record frames of a skipping stream (frames holds n there)
 };
 
 // The stream's attributes as the one-shot argument struct, for the shared
@@ -1575,6 +1590,10 @@ static void stream_free(ctcext_stream* st) {
                      &st->dn.sl, &st->dn.pre, &st->dn.fin, &st->dn.acc, &st->dn.walked};
   for (DevBuf* b : dbufs) b->release();
   st->dn.land.release();
+  DevBuf* kbufs[] = {&st->sk.item, &st->sk.nfr,   &st->sk.kmap, &st->sk.cidx,
+                     &st->sk.norm, &st->sk.ckmap, &st->sk.klen, &st->sk.xc};
+  for (DevBuf* b : kbufs) b->release();
+  st->sk.land.release();
   for (auto& ev : st->dn.ev)
     if (ev) (void)hipEventDestroy(ev);
   delete st;
@@ -1604,8 +1623,18 @@ static int stream_settle(ctcext_stream* st) {
   HIP_OR_FAIL(hipMemcpyAsync(h + land_item_off(B), st->dn.item.p, sizeof(ctcx::ItemOut) * (size_t)B,
                              hipMemcpyDeviceToHost, s));
   HIP_OR_FAIL(hipMemcpyAsync(h + land_kind_off(B), st->dn.top_kind.p, 4 * (size_t)(B * P), hipMemcpyDeviceToHost, s));
+  if (st->sk.on)
+    HIP_OR_FAIL(hipMemcpyAsync(st->sk.land.p, st->sk.item.p, sizeof(CtcxSkipItem) * (size_t)B, hipMemcpyDeviceToHost, s));
   HIP_OR_FAIL(hipStreamSynchronize(s));
   const int32_t* fr = (const int32_t*)h;
+  if (st->sk.on) {   // frames are the original axis's n; the header's count is the kept frames
+    const CtcxSkipItem* it = (const CtcxSkipItem*)st->sk.land.p;
+    for (int64_t b = 0; b < B; ++b) {
+      st->frames[(size_t)b] = it[b].n;
+      st->kept[(size_t)b] = fr[b];
+    }
+    return CTCEXT_OK;
+  }
   for (int64_t b = 0; b < B; ++b) st->frames[(size_t)b] = fr[b];
   return CTCEXT_OK;
 }
@@ -1681,11 +1710,26 @@ static int stream_open_t(ctcext_stream* st) {
   return CTCEXT_OK;
 }
 
-extern "C" int ctcext_stream_open(ctcext_decoder* d, const ctcext_stream_args* a, ctcext_stream** out) {
-  if (!d || !a || !out) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
-  int rc = ctcext_stream_validate(a);
-  if (rc != CTCEXT_OK) return rc;
-  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a stream needs a one-device decoder handle");
+// The per-item state of a skipping stream: sized by the batch and max_frames
+// alone, so allocated at open.  Every item starts with no frame and no flag.
+static int stream_open_skip_state(ctcext_stream* st) {
+  const size_t B = (size_t)st->a.batch_size, F = (size_t)st->a.max_frames;
+  hipStream_t s = st->dec->devs[0].own_stream;
+  HIP_OR_FAIL(st->sk.item.ensure(sizeof(CtcxSkipItem) * B + 16));
+  HIP_OR_FAIL(hipMemsetAsync(st->sk.item.p, 0, sizeof(CtcxSkipItem) * B + 16, s));
+  HIP_OR_FAIL(st->sk.kmap.ensure(4 * F * B + 16));
+  HIP_OR_FAIL(st->sk.cidx.ensure(4 * (F + 1) * B + 16));
+  HIP_OR_FAIL(hipMemsetAsync(st->sk.cidx.p, 0, 4 * (F + 1) * B + 16, s));
+  HIP_OR_FAIL(st->sk.land.ensure(sizeof(CtcxSkipItem) * B + 16));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  st->kept.assign(B, 0);
+  return CTCEXT_OK;
+}
+
+// k: the checked skip arguments of ctcext_stream_open_skip, or null.
+static int stream_open_common(ctcext_decoder* d, const ctcext_stream_args* a, const ctcext_skip_args* k,
+                              ctcext_stream** out) {
+  int rc;
   DeviceGuard guard;
   HIP_OR_FAIL(hipSetDevice(d->devs[0].device));
   ctcext_stream* st = new ctcext_stream();
@@ -1695,6 +1739,12 @@ extern "C" int ctcext_stream_open(ctcext_decoder* d, const ctcext_stream_args* a
   st->gs = use_gstate(&da);
   st->scored = a->scorer != CTCEXT_SCORER_BASE && a->batch_size > 0;
   rc = a->dtype == CTCEXT_F64 ? stream_open_t<double>(st) : stream_open_t<float>(st);
+  if (rc == CTCEXT_OK && k) {
+    st->sk.on = true;
+    st->sk.thr = a->dtype == CTCEXT_F64 ? k->logp_threshold : (double)(float)k->logp_threshold;
+    st->sk.kept_out = k->kept;
+    rc = stream_open_skip_state(st);
+  }
   st->a.scorer_table = nullptr;   // (copied)
   if (rc != CTCEXT_OK) {
     const std::string keep = g_err;
@@ -1704,6 +1754,46 @@ extern "C" int ctcext_stream_open(ctcext_decoder* d, const ctcext_stream_args* a
   }
   *out = st;
   g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_open(ctcext_decoder* d, const ctcext_stream_args* a, ctcext_stream** out) {
+  if (!d || !a || !out) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const int rc = ctcext_stream_validate(a);
+  if (rc != CTCEXT_OK) return rc;
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a stream needs a one-device decoder handle");
+  return stream_open_common(d, a, nullptr, out);
+}
+
+// What a skipping stream asks of its arguments beyond ctcext_stream_validate,
+// on the host; the decoder handle is looked at last (it is the one argument
+// that needs a device to exist).
+extern "C" int ctcext_stream_open_skip(ctcext_decoder* d, const ctcext_stream_args* a, const ctcext_skip_args* k,
+                                       ctcext_stream** out) {
+  if (!a || !out) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_stream_validate(a);
+  if (rc != CTCEXT_OK) return rc;
+  if (!k) return fail(CTCEXT_INVALID_ARGUMENT, "ctcext_stream_open_skip needs skip arguments");
+  rc = ctcext_skip_validate(k);
+  if (rc != CTCEXT_OK) return rc;
+  if (a->on_device != 1)
+    return fail(CTCEXT_INVALID_ARGUMENT, "a skipping stream needs device chunks (on_device == 1): it has the "
+                                         "enqueue-only push alone");
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a skipping stream needs a one-device decoder handle");
+  return stream_open_common(d, a, k, out);
+}
+
+extern "C" int ctcext_stream_kept(ctcext_stream* st, int64_t* kept) {
+  if (!st || !kept) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (st->dn.used) {
+    DeviceGuard guard;
+    HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+    const int rc = stream_settle(st);
+    if (rc != CTCEXT_OK) return rc;
+  }
+  const std::vector<int64_t>& v = st->sk.on ? st->kept : st->frames;   // (without skipping every frame is kept)
+  for (size_t b = 0; b < v.size(); ++b) kept[b] = v[b];
   return CTCEXT_OK;
 }
 
@@ -1752,9 +1842,13 @@ extern "C" int ctcext_stream_reset(ctcext_stream* st, const int32_t* items, int6
     HIP_OR_FAIL(hipMemsetAsync((char*)st->state[st->cur] + (size_t)b * (size_t)st->stride, 0, sizeof(CtcxStreamHdr), s));
     // ... and its stable-prefix frontier goes with the utterance
     HIP_OR_FAIL(hipMemsetAsync((CtcxStableCache*)st->stable_cache + b, 0, sizeof(CtcxStableCache), s));
+    // ... and so do a skipping stream's n and carried flag: the next frame is frame 0, and kept
+    if (st->sk.on) HIP_OR_FAIL(hipMemsetAsync((CtcxSkipItem*)st->sk.item.p + b, 0, sizeof(CtcxSkipItem), s));
   }
   HIP_OR_FAIL(hipStreamSynchronize(s));
   for (int64_t i = 0; i < cnt; ++i) st->frames[(size_t)(items ? items[i] : i)] = 0;
+  if (st->sk.on)
+    for (int64_t i = 0; i < cnt; ++i) st->kept[(size_t)(items ? items[i] : i)] = 0;
   g_err.clear();
   return CTCEXT_OK;
 }
@@ -1930,6 +2024,8 @@ static int stream_push_t(ctcext_stream* st, const ctcext_chunk* c, const std::ve
 
 extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctcext_path_sizes* sizes) {
   if (!st || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (st->sk.on)
+    return fail(CTCEXT_UNIMPLEMENTED, "a skipping stream has no synchronous push: use ctcext_stream_push_dense");
   ctcext_decoder* d = st->dec;
   const ctcext_stream_args& a = st->a;
   const int64_t B = a.batch_size;
@@ -2003,6 +2099,24 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
 // ctcx_stable.hip's kernel over the committed state headers, the records and
 // the per-item frontier cache; and the naive host walk the tests hold it to.
 
+// A skipping stream's answers are record (kept) frames r: on the original time
+// axis that is the frame behind the r-th kept one, kmap[r - 1] + 1 (0 for 0).
+static int stream_map_stable(ctcext_stream* st, int64_t* stable_frames, hipStream_t s) {
+  if (!st->sk.on) return CTCEXT_OK;
+  const int64_t B = st->a.batch_size, F = st->a.max_frames;
+  std::vector<int32_t> last((size_t)B, -1);
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t r = stable_frames[b];
+    if (r <= 0) continue;
+    if (r > F) return fail(CTCEXT_INTERNAL, "stable frames outside the stream's shape");
+    HIP_OR_FAIL(hipMemcpyAsync(&last[(size_t)b], (const int32_t*)st->sk.kmap.p + b * F + (r - 1), 4,
+                               hipMemcpyDeviceToHost, s));
+  }
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  for (int64_t b = 0; b < B; ++b) stable_frames[b] = (int64_t)last[(size_t)b] + 1;
+  return CTCEXT_OK;
+}
+
 extern "C" int ctcext_stream_stable(ctcext_stream* st, int32_t* decoded_length, int64_t* stable_frames,
                                     int64_t* walked) {
   if (!st || !decoded_length || !stable_frames) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
@@ -2044,6 +2158,10 @@ extern "C" int ctcext_stream_stable(ctcext_stream* st, int32_t* decoded_length, 
   memcpy(stable_frames, h, 8 * (size_t)B);
   if (walked) memcpy(walked, h + B, 8 * (size_t)B);
   memcpy(decoded_length, h + 2 * B, 4 * (size_t)B);
+  {
+    const int rc = stream_map_stable(st, stable_frames, s);
+    if (rc != CTCEXT_OK) return rc;
+  }
   g_err.clear();
   return CTCEXT_OK;
 }
@@ -2122,6 +2240,10 @@ extern "C" int ctcext_stream_stable_reference(ctcext_stream* st, int32_t* decode
     decoded_length[b] = len;
     stable_frames[b] = f + 1;
   }
+  {
+    const int rc = stream_map_stable(st, stable_frames, s);
+    if (rc != CTCEXT_OK) return rc;
+  }
   g_err.clear();
   return CTCEXT_OK;
 }
@@ -2195,6 +2317,15 @@ static int stream_dense_ensure(ctcext_stream* st, int64_t Tc) {
     if (st->gs && ts == 4) HIP_OR_FAIL(st->xw.ensure(4 * (size_t)(Tc * B * C) + 16));
     if (!st->gs && C > 64) HIP_OR_FAIL(st->prep.ensure(ctcx::prep_row_bytes(C, (int)ts) * (size_t)(Tc * B)));
   }
+  if (st->sk.on) {
+    HIP_OR_FAIL(st->sk.klen.ensure(4 * (size_t)B));
+    HIP_OR_FAIL(st->sk.nfr.ensure(4 * (size_t)B));
+    if (Tc > 0) {
+      HIP_OR_FAIL(st->sk.norm.ensure(ts * (size_t)(Tc * B)));
+      HIP_OR_FAIL(st->sk.ckmap.ensure(4 * (size_t)(Tc * B)));
+      HIP_OR_FAIL(st->sk.xc.ensure(ts * (size_t)(Tc * B * C) + 16));   // (room for the widest element type)
+    }
+  }
   return CTCEXT_OK;
 }
 
@@ -2234,7 +2365,8 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
   else if (Tc <= 1) st_t = st_b * B;
   else if (B <= 1) st_b = st_t * Tc;
   const void* x = c->inputs;
-  const int32_t* const sl = (const int32_t*)n.sl.p;
+  const int32_t* sl = (const int32_t*)n.sl.p;
+  auto& k = st->sk;
   char* const committed = (char*)st->state[st->cur];
   char* const other = (char*)st->state[st->cur ^ 1];
 
@@ -2250,7 +2382,43 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
   pp.pre = (int32_t*)n.pre.p;
   pp.acc = (CtcxStreamAcc*)n.acc.p;
   pp.chunk_time = Tc; pp.max_frames = F; pp.B = B;
+  pp.skip = k.on ? (CtcxSkipItem*)k.item.p : nullptr;
   HIP_OR_FAIL(ctcx_launch_stream_prologue(pp, s));
+  if (k.on) {
+    // the normaliser of the caller's rows, the chunk's plan on top of what the
+    // items carry, and the kept rows, dense: the rest of the push decodes those
+    if (Tc > 0) HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, xfmt, sl, (T*)k.norm.p, Tc, B, C, st_t, st_b, s));
+    CtcxSkipChunkParams kp{};
+    kp.x = x;
+    kp.norm = k.norm.p;
+    kp.len = sl;
+    kp.state = committed;
+    kp.stride = st->stride;
+    kp.item = (CtcxSkipItem*)k.item.p;
+    kp.chunk_time = Tc; kp.max_frames = F; kp.B = B; kp.xst_t = st_t; kp.xst_b = st_b;
+    kp.xfmt = xfmt; kp.f64 = ts == 8; kp.blank = a.blank_index;
+    kp.thr = k.thr;
+    kp.kmap = (int32_t*)k.kmap.p;
+    kp.cidx = (int32_t*)k.cidx.p;
+    kp.ckmap = (int32_t*)k.ckmap.p;
+    kp.klen = (int32_t*)k.klen.p;
+    kp.cum = pp.cum;
+    HIP_OR_FAIL(ctcx_launch_skip_chunk(kp, s));
+    if (Tc > 0) {
+      CtcxSkipGatherParams gp{};
+      gp.x = x;
+      gp.xc = k.xc.p;
+      gp.kmap = kp.ckmap;
+      gp.kept = kp.klen;
+      gp.Tmax = Tc; gp.B = B; gp.C = C; gp.xst_t = st_t; gp.xst_b = st_b;
+      gp.esize = xfmt == CTCEXT_IN_NATIVE ? ts : 2;
+      HIP_OR_FAIL(ctcx_launch_skip_gather(gp, s));
+      x = k.xc.p;
+      st_t = B * C;
+      st_b = C;
+    }
+    sl = kp.klen;
+  }
   if (Tc > 0) {   // the pre-pass over the chunk's rows, on the sanitised lengths
     if (st->gs && xfmt != CTCEXT_IN_NATIVE) {
       HIP_OR_FAIL(ctcx::launch_widen_rows(x, xfmt, (float*)st->xw.p, Tc, B, C, st_t, st_b, s));
@@ -2298,7 +2466,7 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
   cp.pre = pp.pre; cp.cum = pp.cum; cp.acc = pp.acc;
   cp.status_ws = (int32_t*)n.fin.p;
   cp.status = o ? o->status : nullptr;
-  cp.frames = o ? o->frames : nullptr;
+  cp.frames = (o && !k.on) ? o->frames : nullptr;   // (a skipping stream's are written by its finish kernel)
   cp.B = B; cp.P = P; cp.f64 = ts == 8;
   cp.few_leaves = results ? 1 : 0;
   HIP_OR_FAIL(ctcx_launch_stream_commit(cp, s));
@@ -2318,6 +2486,20 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
     if (!ctcx_stable_in_lds(W, q.rec_fmt)) q.flags = (uint8_t*)st->stable_flags.p;
     HIP_OR_FAIL(ctcx_launch_stable(q, s));
   }
+  if (k.on) {   // n and the carried flag follow the commit; the outputs that count frames go to the original axis
+    CtcxSkipFinishParams fp{};
+    fp.item = (CtcxSkipItem*)k.item.p;
+    fp.status = (const int32_t*)n.fin.p;
+    fp.dead_mask = ctcx::kItemHelperTimeout;
+    fp.cum = pp.cum;
+    fp.kmap = (const int32_t*)k.kmap.p;
+    fp.max_frames = F; fp.B = B;
+    fp.n_ws = (int32_t*)k.nfr.p;
+    fp.frames = o ? o->frames : nullptr;
+    fp.kept = k.kept_out;
+    fp.stable_frames = o ? o->stable_frames : nullptr;
+    HIP_OR_FAIL(ctcx_launch_skip_finish(fp, s));
+  }
   if (results) {
     // the walks of every frame so far, from the records the stream keeps, then ctcx_pack_dense with rows of max_frames
     ctcx::TraceParams tp{};
@@ -2331,6 +2513,17 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
     tp.len = (int32_t*)n.len.p;
     tp.len_stride = B;
     HIP_OR_FAIL(ctcx::launch_traceback(tp, s));
+    if (k.on) {   // the alignment walks of the kept frames, back on the original time axis
+      CtcxSkipExpandParams ep{};
+      ep.seq = tp.seq;
+      ep.len = tp.len;
+      ep.frames = (const int32_t*)k.nfr.p;
+      ep.kmap = (const int32_t*)k.kmap.p;
+      ep.cidx = (const int32_t*)k.cidx.p;
+      ep.kept = (const int32_t*)st->cum;
+      ep.Tmax = F; ep.B = B; ep.P = P; ep.blank_label = a.blank_label;
+      HIP_OR_FAIL(ctcx_launch_skip_expand(ep, s));
+    }
     ctcx::PackDenseParams pd{};
     pd.seq = tp.seq;
     pd.len = tp.len;
@@ -2533,7 +2726,7 @@ extern "C" int ctcext_stream_token_times(ctcext_stream* st, const ctcext_token_t
   CtcxTimesParams p{};
   p.seq = (const int32_t*)n.seq.p;
   p.len = (const int32_t*)n.len.p;
-  p.frames = (const int32_t*)st->cum;
+  p.frames = st->sk.on ? (const int32_t*)st->sk.nfr.p : (const int32_t*)st->cum;
   p.status = (const int32_t*)n.fin.p;
   p.Tmax = a.max_frames; p.B = a.batch_size; p.P = a.top_paths;
   p.merge = a.merge_repeated ? 1 : 0; p.blank_label = a.blank_label;

@@ -19,6 +19,13 @@
 //   ctcx_skip_expand   one workgroup per (item, path): the reversed alignment
 //                      walk of the compacted decode, in place, to the walk on
 //                      the original time axis.
+//   ctcx_skip_chunk    the plan of one chunk of a skipping stream: one wave
+//                      (chunks up to kSkipChunkSmall frames) or one workgroup
+//                      per item, started from what the item carries, appending
+//                      to the stream's kmap / cidx.
+//   ctcx_skip_finish   one thread per item behind a stream push's commit: n and
+//                      the carried flag follow it, the frame counts and the
+//                      stable frames go out on the original time axis.
 #include "ctcx_skip.h"
 
 namespace {
@@ -147,7 +154,124 @@ __global__ __launch_bounds__(kNT) void ctcx_skip_expand(CtcxSkipExpandParams p) 
   if (tid == 0) *lenp = Lnew;
 }
 
+// The plan of one chunk of a stream: ctcx_skip_plan's carry / scan shape with
+// NT threads per item (one wave for the usual short chunk, kSkipTile for a long
+// one), started from the item's carried flag, its frames n and its committed
+// kept count, and appending.  Frame t of the chunk is original frame n + t; the
+// t > 0 rule reads that number.  What the push may still undo (n, the flag) is
+// left in n_next / dom_next; kmap and cidx entries past the committed counts are
+// rewritten by the item's next chunk if this one is not committed.
+template <typename T, int NT>
+__global__ __launch_bounds__(NT) void ctcx_skip_chunk(CtcxSkipChunkParams p) {
+  constexpr int NW = NT / 64;
+  __shared__ int s_dom[2][NW], s_cnt[2][NW];
+  __shared__ int s_last;   // the flag of the chunk's last frame (written once, before its tile's first barrier)
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int F = (int)p.max_frames;
+  const CtcxSkipItem it = p.item[b];
+  const int n0 = clamp_len(it.n, F);
+  const int k0 = clamp_len(*(const int32_t*)(p.state + b * p.stride), n0);
+  int n = clamp_len(p.len[b], (int)p.chunk_time);
+  if (n > F - n0) n = 0;   // (the prologue's capacity rule has already said so)
+  const T thr = (T)p.thr;
+  const T* const norm = (const T*)p.norm;
+  int32_t* const kmap = p.kmap + b * p.max_frames;
+  int32_t* const cidx = p.cidx + b * (p.max_frames + 1);
+  int32_t* const ckmap = p.ckmap + b * p.chunk_time;
+  int c_dom = it.dom ? 1 : 0;   // carries (uniform): the flag of the frame before this tile, the frames kept so far
+  int c_cnt = 0;
+  for (int base = 0; base < n; base += NT) {
+    const int par = (base / NT) & 1;
+    const int t = base + tid;
+    const bool in = t < n;
+    int dom = 0;
+    if (in) {
+      const T lp = load_as<T>(p.x, p.xfmt, (int64_t)t * p.xst_t + b * p.xst_b + p.blank) - norm[(int64_t)t * p.B + b];
+      dom = lp > thr ? 1 : 0;   // (false for NaN)
+    }
+    int prev = __shfl_up(dom, 1, 64);
+    if (lane == 63) s_dom[par][wave] = dom;
+    if (t == n - 1) s_last = dom;
+    __syncthreads();
+    if (lane == 0) prev = wave == 0 ? c_dom : s_dom[par][wave - 1];
+    const int keep = (in && !(n0 + t > 0 && dom && prev)) ? 1 : 0;
+    int c = keep;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(c, d, 64);
+      if (lane >= d) c += y;
+    }
+    if (lane == 63) s_cnt[par][wave] = c;
+    __syncthreads();
+    int ex = c_cnt + c - keep, t_cnt = c_cnt;
+    for (int w = 0; w < NW; ++w) {
+      const int y = s_cnt[par][w];
+      if (w < wave) ex += y;
+      t_cnt += y;
+    }
+    if (in) cidx[n0 + t] = k0 + ex;
+    if (keep) {
+      kmap[k0 + ex] = n0 + t;
+      ckmap[ex] = t;
+    }
+    c_dom = s_dom[par][NW - 1];
+    c_cnt = t_cnt;
+  }
+  if (tid == 0) {
+    cidx[n0 + n] = k0 + c_cnt;
+    p.klen[b] = c_cnt;
+    p.cum[b] = k0 + c_cnt;
+    p.item[b].n_next = n0 + n;
+    p.item[b].dom_next = n > 0 ? s_last : c_dom;   // (no frame: the carried flag stays)
+  }
+}
+
+// One thread per item, behind the commit (and the stable query) of a push.
+__global__ __launch_bounds__(256) void ctcx_skip_finish(CtcxSkipFinishParams p) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= p.B) return;
+  CtcxSkipItem it = p.item[b];
+  if (!(p.status[b] & p.dead_mask)) {
+    it.n = it.n_next;
+    it.dom = it.dom_next;
+    p.item[b] = it;
+  }
+  p.n_ws[b] = it.n;
+  if (p.frames) p.frames[b] = it.n;
+  if (p.kept) p.kept[b] = p.cum[b];
+  if (p.stable_frames) {
+    int64_t r = p.stable_frames[b];
+    if (r > p.cum[b]) r = p.cum[b];
+    p.stable_frames[b] = r <= 0 ? 0 : (int64_t)p.kmap[b * p.max_frames + (r - 1)] + 1;
+  }
+}
+
 }  // namespace
+
+hipError_t ctcx_launch_skip_chunk(const CtcxSkipChunkParams& p, hipStream_t s) {
+  if (p.B <= 0) return hipSuccess;
+  if (p.B > 0x7fffffffLL || p.chunk_time < 0 || p.chunk_time >= 0x7fffffffLL || p.max_frames < 0 ||
+      p.max_frames >= 0x7fffffffLL || (p.chunk_time > 0 && (!p.x || !p.norm || !p.ckmap)) || !p.len || !p.state ||
+      !p.item || !p.kmap || !p.cidx || !p.klen || !p.cum ||
+      (p.xfmt != kSkipInNative && (p.f64 || (p.xfmt != kSkipInF16 && p.xfmt != kSkipInBF16))))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.B);
+  if (p.chunk_time <= kSkipChunkSmall) {
+    if (p.f64) hipLaunchKernelGGL((ctcx_skip_chunk<double, 64>), grid, dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((ctcx_skip_chunk<float, 64>), grid, dim3(64), 0, s, p);
+  } else {
+    if (p.f64) hipLaunchKernelGGL((ctcx_skip_chunk<double, kNT>), grid, dim3(kNT), 0, s, p);
+    else hipLaunchKernelGGL((ctcx_skip_chunk<float, kNT>), grid, dim3(kNT), 0, s, p);
+  }
+  return hipGetLastError();
+}
+
+hipError_t ctcx_launch_skip_finish(const CtcxSkipFinishParams& p, hipStream_t s) {
+  if (p.B <= 0) return hipSuccess;
+  if (p.B > 0x7fffffffLL || !p.item || !p.status || !p.cum || !p.kmap || !p.n_ws) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ctcx_skip_finish, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
 
 hipError_t ctcx_launch_skip_plan(const CtcxSkipPlanParams& p, hipStream_t s) {
   if (p.B <= 0) return hipSuccess;

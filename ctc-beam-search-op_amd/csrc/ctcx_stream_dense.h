@@ -8,6 +8,7 @@
 
 #include "ctcx_kernels.h"
 #include "ctcx_stable.h"
+#include "ctcx_skip.h"
 
 constexpr int32_t kCtcxItemCapacity = 16;   // = CTCEXT_ITEM_CAPACITY
 
@@ -32,6 +33,9 @@ struct CtcxStreamPrologueParams {
   int32_t* pre;                 // [B] out: kItemLength / kCtcxItemCapacity of this push
   CtcxStreamAcc* acc;           // [B]
   int64_t chunk_time, max_frames, B;
+  CtcxSkipItem* skip;           // [B] a skipping stream's items, or null.  With it reset[b] clears the item's
+                                // entry too, and the capacity is judged on its n (the original time axis), not
+                                // on the header's record frames
 };
 
 struct CtcxStreamCommitParams {

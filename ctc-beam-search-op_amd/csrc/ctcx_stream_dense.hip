@@ -39,8 +39,10 @@ __global__ __launch_bounds__(kNT) void ctcx_stream_prologue(CtcxStreamProloguePa
     const u32x4 z = {0u, 0u, 0u, 0u};
     for (int q = 0; q < (int)(sizeof(CtcxStreamHdr) / 16); ++q) ((u32x4*)hdr)[q] = z;
     *(u32x4*)(p.cache + b) = z;
+    if (p.skip) *(u32x4*)(p.skip + b) = z;
   }
-  const int64_t frames = hdr->frames;
+  const int64_t recs = hdr->frames;
+  const int64_t frames = p.skip ? (int64_t)p.skip[b].n : recs;
   int64_t v = p.chunk_length ? (int64_t)p.chunk_length[b] : p.chunk_time;
   if (v < 0) v = 0;
   int32_t st = 0;
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(kNT) void ctcx_stream_prologue(CtcxStreamProloguePa
   if (frames + v > p.max_frames) st |= kCtcxItemCapacity;
   const int32_t n = st ? 0 : (int32_t)v;
   p.sl[b] = n;
-  p.cum[b] = (int32_t)frames + n;
+  p.cum[b] = (int32_t)recs + n;   // (a skipping stream's chunk plan writes it again, with the frames it keeps)
   p.pre[b] = st;
   if (st) {
     CtcxStreamAcc a = p.acc[b];

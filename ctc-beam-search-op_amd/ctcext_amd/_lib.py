@@ -64,6 +64,9 @@ BLANK_SKIP_SYMBOLS = ("ctcext_skip_validate", "ctcext_decode_skip", "ctcext_dens
                       "ctcext_decode_dense_skip", "ctcext_dense_skip_ms", "ctcext_skip_plan_row",
                       "ctcext_skip_expand_row")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + BLANK_SKIP_SYMBOLS
+# blank-frame skipping for streams (CTCEXT_HAS_STREAM_SKIP)
+STREAM_SKIP_SYMBOLS = ("ctcext_stream_open_skip", "ctcext_stream_kept", "ctcext_skip_plan_chunk_row")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_SKIP_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -327,6 +330,18 @@ def load():
                                                ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                                ctypes.POINTER(ctypes.c_int64)]
         lib.ctcext_skip_expand_row.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_stream_open_skip"):   # (CTCEXT_HAS_STREAM_SKIP; older builds stay loadable for A/B runs)
+        lib.ctcext_stream_open_skip.argtypes = [ctypes.c_void_p, ctypes.POINTER(StreamArgs),
+                                                ctypes.POINTER(SkipArgs), ctypes.POINTER(ctypes.c_void_p)]
+        lib.ctcext_stream_open_skip.restype = ctypes.c_int
+        lib.ctcext_stream_kept.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.ctcext_stream_kept.restype = ctypes.c_int
+        # (logp_blank[n] of the compute dtype, f64, n, thr, first_frame, prev_dom, int32 kmap[n], int64* kept,
+        #  int32* last_dom)
+        lib.ctcext_skip_plan_chunk_row.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double,
+                                                   ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]
+        lib.ctcext_skip_plan_chunk_row.restype = ctypes.c_int
     _lib = lib
     return lib
 

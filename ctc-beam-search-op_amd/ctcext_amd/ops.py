@@ -802,12 +802,26 @@ class StreamDecoder:
     the device or the host is fixed by the first push.  The decode kernel is
     chosen at that moment (dtype, scorer, num_classes, beam_width and the
     ``CTCEXT_HELPER`` environment variable) and stays for the stream's life.
+
+    ``skip_blank``: None, or a log-probability threshold (<= 0) for blank-frame
+    skipping (include/ctcext.h, "Streaming: blank-frame skipping").  Every
+    ``push_dense`` then drops runs of blank-dominant frames on the device, a
+    run carried across pushes, and its outputs are those of the one-shot
+    skipping decode of everything pushed so far; ``frames``, ``stable()`` and
+    the token times stay on the original time axis.  Such a stream takes CUDA
+    chunks through ``push_dense`` only: ``push`` raises ``UnimplementedError``.
     """
 
     def __init__(self, batch_size, num_classes, beam_width, top_paths, max_frames, *,
                  dtype="float32", merge_repeated=False, blank_index=0, blank_label=-1,
-                 device=None, scorer_table=None, flags=0):
+                 device=None, scorer_table=None, flags=0, skip_blank=None):
         self.lib = _lib.load()
+        self._skip = self._kept = None
+        if skip_blank is not None:
+            if not hasattr(self.lib, "ctcext_stream_open_skip"):
+                raise UnimplementedError("this libctcext.so has no blank-frame skipping for streams "
+                                         "(CTCEXT_HAS_STREAM_SKIP)", _lib.CTCEXT_UNIMPLEMENTED)
+            self._skip = _skip_args(self.lib, skip_blank)
         name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
         if name not in ("float32", "float64"):
             _type_error("dtype", name, "float32, float64")
@@ -853,8 +867,18 @@ class StreamDecoder:
         a = self._args
         a.on_device = 1 if on_device else 0
         h = ctypes.c_void_p()
-        rc = self.lib.ctcext_stream_open(self.dec.handle, ctypes.byref(a), ctypes.byref(h))
+        if self._skip is None:
+            rc = self.lib.ctcext_stream_open(self.dec.handle, ctypes.byref(a), ctypes.byref(h))
+        else:
+            if on_device:   # the tensor every push writes its kept counts into, for the stream's life
+                import torch
+                self._kept = torch.zeros((int(a.batch_size),), dtype=torch.int32,
+                                         device=torch.device("cuda", self.dec.device))
+                self._skip.kept = self._kept.data_ptr()
+            rc = self.lib.ctcext_stream_open_skip(self.dec.handle, ctypes.byref(a), ctypes.byref(self._skip),
+                                                  ctypes.byref(h))
         if rc != _lib.CTCEXT_OK:
+            self._kept = None
             _raise(self.lib, rc)
         self.handle = h
         self.on_device = on_device
@@ -892,6 +916,32 @@ class StreamDecoder:
             if rc != _lib.CTCEXT_OK:
                 _raise(self.lib, rc)
         return out
+
+    def kept_frames(self):
+        """Frames kept per item so far on a ``skip_blank`` stream (``frames``
+        on any other): numpy int64 [batch_size].  Waits."""
+        self._check_open()
+        out = np.zeros((int(self._args.batch_size),), np.int64)
+        if self.handle:
+            if not hasattr(self.lib, "ctcext_stream_kept"):
+                raise UnimplementedError("this libctcext.so has no ctcext_stream_kept (CTCEXT_HAS_STREAM_SKIP)",
+                                         _lib.CTCEXT_UNIMPLEMENTED)
+            rc = self.lib.ctcext_stream_kept(self.handle, out.ctypes.data)
+            if rc != _lib.CTCEXT_OK:
+                _raise(self.lib, rc)
+        return out
+
+    def kept_dense(self):
+        """The int32 CUDA tensor ``[batch_size]`` that every ``push_dense`` of a
+        ``skip_blank`` stream writes its kept counts into, in stream order (the
+        same tensor for the stream's life, so a captured push keeps writing
+        it).  Opens the stream for CUDA chunks if no push has yet."""
+        self._check_open()
+        if self._skip is None:
+            raise FailedPreconditionError("kept_dense without skip_blank", _lib.CTCEXT_FAILED_PRECONDITION)
+        if not self.handle:
+            self._open(True, self._device if self._device is not None else _current_device())
+        return self._kept
 
     def reset(self, items=None):
         """Put ``items`` (None: all) back to no frames; the others are untouched."""
@@ -953,6 +1003,9 @@ class StreamDecoder:
         self._check_open()
         if outputs not in ("auto", "host", "device"):
             raise ValueError("outputs must be 'auto', 'host' or 'device'")
+        if self._skip is not None:   # (the library's own answer and message; nothing is opened or touched)
+            raise UnimplementedError("a skipping stream has no synchronous push: use ctcext_stream_push_dense",
+                                     _lib.CTCEXT_UNIMPLEMENTED)
         lib = self.lib
         a = self._args
         c, x, sl, on_device, dev, index = self._chunk(chunk, lengths, batch_first, flags)

@@ -737,8 +737,9 @@ int ctcext_stream_token_times_ms(ctcext_stream* s, double* ms);
  * Cost: a second logits-sized workspace buffer (the kept rows, in the inputs'
  * own element type) beside the normaliser, the frame map and the kept counts.
  *
- * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED), and
- * streams. */
+ * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED).
+ * Streams have entry points of their own ("Streaming: blank-frame skipping",
+ * below). */
 #define CTCEXT_HAS_BLANK_SKIP 1
 
 typedef struct {
@@ -775,6 +776,82 @@ int ctcext_dense_skip_ms(ctcext_decoder* dec, double* front_ms, double* expand_m
 int ctcext_skip_plan_row(const void* logp_blank, int32_t f64, int64_t n, double thr, int32_t* kmap, int64_t* kept);
 int ctcext_skip_expand_row(const int64_t* ali_c, int64_t L, const int32_t* kmap, int64_t kept, int64_t n,
                            int64_t blank_label, int64_t* row, int64_t* row_len);
+
+/* ---------------------------------------------------------------------------
+ * Streaming: blank-frame skipping.  A stream opened with
+ * ctcext_stream_open_skip drops runs of blank-dominant frames inside every
+ * enqueue-only push, on the device, and carries a run across push boundaries.
+ * Opt-in: a stream opened with ctcext_stream_open, and every entry point on
+ * it, does exactly what it did (CTCEXT_ABI_VERSION, ctcext_stream_args,
+ * ctcext_chunk, ctcext_stream_dense_outputs and ctcext_stats are unchanged;
+ * detect the feature by CTCEXT_HAS_STREAM_SKIP or by symbol).
+ *
+ * Definition.  The plan is causal (frame t is kept or not by frames t and
+ * t - 1 alone), so the kept frames of a prefix are a prefix of the kept frames
+ * of the whole.  Let item b have received frames 0 .. n - 1 over all its
+ * committed pushes since its last reset, and let
+ *     kmap_b = skip_plan(logp_blank_b, n, thr)
+ * of that whole sequence ("Blank-frame skipping" above).  Its record frames are
+ * the kept ones: the state header's frame count and the traceback's lengths
+ * count kept frames, and n is kept beside them.  After every push item b's
+ * outputs are those of the one-shot skipping decode of everything pushed to b
+ * so far:
+ *
+ *   outputs   Decoded rows, log_probability and CTCEXT_ITEM_FEW_LEAVES are the
+ *             plain decode's of the compacted prefix.  Each alignment row is
+ *             skip_expand(compacted row, kmap_b, n, blank_label).  A chunk
+ *             whose frames are all dropped lengthens the alignment by
+ *             blank_labels and adds to trailing_blank; it launches no decode
+ *             work for that item (a sanitised length of 0).
+ *   frames    frames[b] (the push output, ctcext_stream_frames) is n.
+ *             CTCEXT_ITEM_CAPACITY is judged on n + length > max_frames, and
+ *             the deferred message's total is on that axis: max_frames still
+ *             bounds the output rows, and the records always fit.
+ *   stable    stable_length is unchanged.  With r the record-frame answer,
+ *             stable_frames[b] is 0 if r == 0, else kmap_b[r - 1] + 1, in the
+ *             push output and in ctcext_stream_stable / _stable_reference.  It
+ *             never decreases, because kmap ascends.
+ *   times     ctcext_stream_token_times applies its definition to the expanded
+ *             rows, with n as frames.
+ *   no advance  An item that does not advance in a push (CTCEXT_ITEM_LENGTH,
+ *             _CAPACITY, _HELPER_TIMEOUT, or a chunk length of 0) keeps n, its
+ *             kept count and the carried flag exactly: a zero-length push does
+ *             not clear the flag.
+ *   reset     reset[b] != 0, or ctcext_stream_reset, puts n, the kept count and
+ *             the flag to 0: the item's next frame is frame 0 and is always
+ *             kept.  As without skipping, a status bit of the same push does
+ *             not undo the reset.
+ *   thr = 0   keeps every frame: every output of every push is bit for bit the
+ *             non-skipping stream's.
+ *
+ * ctcext_stream_push (synchronous) on such a stream answers
+ * CTCEXT_UNIMPLEMENTED and leaves the stream as it was; _frames, _kept, _reset,
+ * _stable, _check, _reserve and _token_times work.
+ *
+ * Cost: per item 4 * (2 * max_frames + 1) bytes of frame map, and per reserved
+ * chunk a second chunk-sized buffer (the kept rows), a normaliser and a map. */
+#define CTCEXT_HAS_STREAM_SKIP 1
+
+/* ctcext_stream_open with the rule above.  skip->logp_threshold is checked as
+ * by ctcext_skip_validate; skip->kept, where not NULL, is a device int32
+ * [batch] that every enqueue-only push of this stream writes (the frames kept
+ * per item so far) -- fixed for the stream's life, so a captured push keeps
+ * writing it.  Before any allocation: skip == NULL and args->on_device != 1 are
+ * CTCEXT_INVALID_ARGUMENT, a handle of more than one device
+ * CTCEXT_UNIMPLEMENTED, each with a message of its own. */
+int ctcext_stream_open_skip(ctcext_decoder* dec, const ctcext_stream_args* args, const ctcext_skip_args* skip,
+                            ctcext_stream** out);
+/* Frames kept per item so far, host [batch]; synchronous, like
+ * ctcext_stream_frames.  On a stream without skipping: the frame counts. */
+int ctcext_stream_kept(ctcext_stream* s, int64_t* kept);
+/* Host only, no HIP call, plain C++ that shares no code with the kernels: the
+ * plan in chunks.  skip_plan for frames first_frame .. first_frame + n - 1 of
+ * an item, whose logp_blank values (of the compute dtype) are the n given,
+ * with prev_dom the flag of frame first_frame - 1; the t > 0 rule reads the
+ * absolute frame.  kmap (room for n) receives absolute frame numbers, *kept
+ * their count, *last_dom the flag of the last frame (prev_dom where n == 0). */
+int ctcext_skip_plan_chunk_row(const void* logp_blank, int32_t f64, int64_t n, double thr, int64_t first_frame,
+                               int32_t prev_dom, int32_t* kmap, int64_t* kept, int32_t* last_dom);
 
 #ifdef __cplusplus
 }
