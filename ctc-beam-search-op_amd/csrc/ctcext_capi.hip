@@ -20,6 +20,7 @@
 #include "../../include/ctcext.h"
 #define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
+#include "ctcx_scores.h"
 #include "ctcx_skip.h"
 #include "ctcx_stable.h"
 #include "ctcx_stream_dense.h"
@@ -160,8 +161,8 @@ struct Dev {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t s = nullptr;   // stream of the current call
-  hipEvent_t ev[7] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
-                             // [5], [6] around the token-times kernel of a dense call
+  hipEvent_t ev[9] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
+                             // [5], [6] around the token-times kernel of a dense call, [7], [8] the token-scores kernel
   hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
@@ -174,6 +175,18 @@ struct Dev {
 };
 
 }  // namespace
+
+// What the token scores read of the decode they follow (ctcext.h, "Token
+// scores"): the logits where the kernels read them, and which normaliser
+// applies.  The library keeps no copy of either.
+struct ScoreSrc {
+  bool have = false;
+  const void* x = nullptr;
+  int32_t xfmt = 0;
+  int64_t st_t = 0, st_b = 0;
+  const void* norm = nullptr;   // [T][B] of the compute dtype
+  bool f64 = false;
+};
 
 struct ctcext_decoder {
   std::vector<Dev> devs;
@@ -199,6 +212,8 @@ struct ctcext_decoder {
     int32_t blank_index = 0, blank_label = 0, merge = 0;
     bool times_timed = false;   // events [5], [6] were recorded
     bool skip = false;          // it was a ctcext_decode_dense_skip
+    ScoreSrc sc;                // what ctcext_dense_token_scores reads beside that
+    bool scores_timed = false;  // events [7], [8] were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -208,6 +223,11 @@ struct ctcext_decoder {
     int32_t blank_index = 0, blank_label = 0, merge = 0;
   } tt;
   DevBuf tt_frames, tt_start, tt_end, tt_trail;
+  // ... and what ctcext_fetch_token_scores needs of the last ctcext_decode /
+  // ctcext_decode_skip (a stream's push leaves nothing to score), with the
+  // staging of its outputs
+  ScoreSrc ss;
+  DevBuf sc_sum, sc_min;
   // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
   // the plan, and what the call that is running reads of it
   struct {
@@ -297,7 +317,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail, &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
+                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
   d->h_res.release();
@@ -1000,6 +1020,7 @@ static int decode_sync(ctcext_decoder* d, const ctcext_decode_args* a, const ctc
   if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   d->have = false;
   d->dense.have = false;   // (the workspace ctcext_dense_check reads is this call's now)
+  d->ss.have = false;
   int rc = validate_shapes(a);
   if (rc == CTCEXT_OK && k) rc = ctcext_skip_validate(k);
   if (rc != CTCEXT_OK) return rc;
@@ -1064,6 +1085,23 @@ static int decode_sync(ctcext_decoder* d, const ctcext_decode_args* a, const ctc
   d->tt.frames = hsl;
   d->tt.C = a->num_classes; d->tt.blank_index = a->blank_index; d->tt.blank_label = a->blank_label;
   d->tt.merge = a->merge_repeated ? 1 : 0;
+  // the rows the kernels read and their normaliser, for ctcext_fetch_token_scores:
+  // device inputs in place, host inputs as stage_shard laid them out in root.x
+  if (B > 0 && d->devs.size() == 1) {
+    ScoreSrc& q = d->ss;
+    input_strides(a, q.st_t, q.st_b);
+    q.x = a->inputs;
+    if (!a->inputs_on_device) {
+      const bool bmajor = q.st_t < q.st_b;
+      q.x = root.x.p;
+      q.st_t = bmajor ? a->num_classes : B * a->num_classes;
+      q.st_b = bmajor ? T_ * a->num_classes : a->num_classes;
+    }
+    q.xfmt = a->inputs_format;
+    q.norm = k ? d->skip.norm.p : root.norm.p;
+    q.f64 = a->dtype == CTCEXT_F64;
+    q.have = true;
+  }
   root.s = s;
   if (sizes)
     for (int p = 0; p < P; ++p) sizes[p] = d->sizes[p];
@@ -1322,6 +1360,7 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   d->have = false;
   d->dense.have = false;
+  d->ss.have = false;
   int rc = ctcext_dense_validate(a, o);
   if (rc == CTCEXT_OK && k) rc = ctcext_skip_validate(k);
   if (rc != CTCEXT_OK) return rc;
@@ -1356,6 +1395,19 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   d->dense.merge = a->merge_repeated ? 1 : 0;
   d->dense.times_timed = false;
   d->dense.skip = k != nullptr;
+  // the caller's rows (with skipping the expanded alignment is on their axis)
+  // and the normaliser over them: the plan's with skipping, the pre-pass's else
+  d->dense.sc = ScoreSrc{};
+  d->dense.scores_timed = false;
+  if (a->batch_size > 0) {
+    ScoreSrc& q = d->dense.sc;
+    q.x = a->inputs;
+    q.xfmt = a->inputs_format;
+    input_strides(a, q.st_t, q.st_b);
+    q.norm = k ? d->skip.norm.p : root.norm.p;
+    q.f64 = a->dtype == CTCEXT_F64;
+    q.have = true;
+  }
   g_err.clear();
   return CTCEXT_OK;
 }
@@ -2062,6 +2114,7 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
   }
   d->have = false;
   d->dense.have = false;   // (the workspace ctcext_dense_check reads is this call's now)
+  d->ss.have = false;      // (a push keeps neither its chunk nor its normaliser: nothing to score)
   if (B > 0) {
     rc = a.dtype == CTCEXT_F32 ? stream_push_t<float>(st, c, hcl, sizes, s) : stream_push_t<double>(st, c, hcl, sizes, s);
     if (rc != CTCEXT_OK) return rc;
@@ -2821,6 +2874,147 @@ extern "C" int ctcext_stream_token_times_ms(ctcext_stream* st, double* ms) {
   HIP_OR_FAIL(hipEventSynchronize(st->dn.ev[6]));
   float f = 0;
   HIP_OR_FAIL(hipEventElapsedTime(&f, st->dn.ev[5], st->dn.ev[6]));
+  *ms = f;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Token scores (ctcext.h, "Token scores"): ctcx_scores.hip's kernel over the
+// walks the traceback left in the workspace, the spans of the token times, the
+// normaliser and the logits the decode read (ScoreSrc).  The decoder's only: a
+// stream keeps neither its chunks nor their normalisers.
+
+extern "C" int32_t ctcext_token_scores_tile(void) { return kScoresTile; }
+
+static int check_scores_out(const ctcext_token_scores* o) {
+  if (!o) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!o->logp_sum && !o->logp_min) return fail(CTCEXT_INVALID_ARGUMENT, "token scores: no output asked for");
+  return CTCEXT_OK;
+}
+
+// What both entry points share of the kernel's parameters.
+static void scores_params(CtcxScoresParams& p, const Dev& root, const ScoreSrc& q, int64_t T_, int64_t B, int64_t C,
+                          int P, int32_t blank_index, int32_t blank_label) {
+  p.seq = (const int32_t*)root.seq.p;
+  p.len = (const int32_t*)root.len.p;
+  p.x = q.x;
+  p.norm = q.norm;
+  p.Tmax = T_; p.B = B; p.C = C; p.xst_t = q.st_t; p.xst_b = q.st_b;
+  p.P = P; p.xfmt = q.xfmt; p.f64 = q.f64 ? 1 : 0;
+  p.blank_index = blank_index; p.blank_label = blank_label;
+}
+
+extern "C" int ctcext_dense_token_scores(ctcext_decoder* d, const ctcext_token_times* t,
+                                         const ctcext_token_scores* o) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_scores_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!t || !t->start || !t->end)
+    return fail(CTCEXT_INVALID_ARGUMENT, "token scores need the start and end of ctcext_dense_token_times");
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_token_scores without a ctcext_decode_dense");
+  rc = ctcext_token_times_validate(d->dense.C, d->dense.blank_index, d->dense.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (d->dense.B == 0) return CTCEXT_OK;
+  if (!d->dense.sc.have) return fail(CTCEXT_INTERNAL, "token scores: the inputs of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  CtcxScoresParams p{};
+  scores_params(p, root, d->dense.sc, d->dense.T, B, d->dense.C, d->dense.P, d->dense.blank_index,
+                d->dense.blank_label);
+  p.frames = (const int32_t*)root.dsl.p;
+  p.status = (const int32_t*)root.dstat.p + B;
+  p.start = t->start; p.end = t->end;
+  p.logp_sum = o->logp_sum; p.logp_min = o->logp_min;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[7], s));
+  HIP_OR_FAIL(ctcx_launch_token_scores(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.ev[8], s));
+    d->dense.scores_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_fetch_token_scores(ctcext_decoder* d, const ctcext_token_scores* o, int32_t outputs_on_device) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_scores_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_fetch_token_scores without a successful ctcext_decode");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "token scores need a one-device decoder handle");
+  rc = ctcext_token_times_validate(d->tt.C, d->tt.blank_index, d->tt.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  const int64_t B = d->B, T_ = d->T;
+  const int P = d->P;
+  if (B == 0) return CTCEXT_OK;
+  if (!d->ss.have)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_fetch_token_scores after a stream's push: a stream keeps no logits to score");
+  if ((int64_t)d->tt.frames.size() != B)
+    return fail(CTCEXT_INTERNAL, "token scores: the frame counts of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.s;
+  const size_t cells = (size_t)(B * P) * (size_t)T_;
+  const size_t ts = d->ss.f64 ? 8 : 4;
+  // the times into workspace, as ctcext_fetch_token_times computes them
+  HIP_OR_FAIL(d->tt_frames.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(d->tt_start.ensure(4 * cells + 16));
+  HIP_OR_FAIL(d->tt_end.ensure(4 * cells + 16));
+  HIP_OR_FAIL(hipMemcpyAsync(d->tt_frames.p, d->tt.frames.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  CtcxTimesParams tp{};
+  tp.seq = (const int32_t*)root.seq.p;
+  tp.len = (const int32_t*)root.len.p;
+  tp.frames = (const int32_t*)d->tt_frames.p;
+  tp.status = nullptr;   // (a synchronous call with a failing item has failed as a whole)
+  tp.Tmax = T_; tp.B = B; tp.P = P;
+  tp.merge = d->tt.merge; tp.blank_label = d->tt.blank_label;
+  tp.start = (int32_t*)d->tt_start.p;
+  tp.end = (int32_t*)d->tt_end.p;
+  HIP_OR_FAIL(ctcx_launch_token_times(tp, s));
+  CtcxScoresParams p{};
+  scores_params(p, root, d->ss, T_, B, d->tt.C, P, d->tt.blank_index, d->tt.blank_label);
+  p.frames = tp.frames;
+  p.status = nullptr;
+  p.start = tp.start; p.end = tp.end;
+  if (outputs_on_device) {
+    p.logp_sum = o->logp_sum; p.logp_min = o->logp_min;
+  } else {
+    if (o->logp_sum) {
+      HIP_OR_FAIL(d->sc_sum.ensure(ts * cells + 16));
+      p.logp_sum = d->sc_sum.p;
+    }
+    if (o->logp_min) {
+      HIP_OR_FAIL(d->sc_min.ensure(ts * cells + 16));
+      p.logp_min = d->sc_min.p;
+    }
+  }
+  HIP_OR_FAIL(ctcx_launch_token_scores(p, s));
+  if (!outputs_on_device && cells) {
+    if (o->logp_sum) HIP_OR_FAIL(hipMemcpyAsync(o->logp_sum, p.logp_sum, ts * cells, hipMemcpyDeviceToHost, s));
+    if (o->logp_min) HIP_OR_FAIL(hipMemcpyAsync(o->logp_min, p.logp_min, ts * cells, hipMemcpyDeviceToHost, s));
+  }
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_token_scores_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.scores_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no token scores of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.ev[8]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[7], root.ev[8]));
   *ms = f;
   return CTCEXT_OK;
 }

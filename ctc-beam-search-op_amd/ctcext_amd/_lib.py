@@ -67,6 +67,10 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + BLANK_SKIP_SYMBOLS
 # blank-frame skipping for streams (CTCEXT_HAS_STREAM_SKIP)
 STREAM_SKIP_SYMBOLS = ("ctcext_stream_open_skip", "ctcext_stream_kept", "ctcext_skip_plan_chunk_row")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_SKIP_SYMBOLS
+# token scores (CTCEXT_HAS_TOKEN_SCORES)
+TOKEN_SCORES_SYMBOLS = ("ctcext_token_scores_tile", "ctcext_dense_token_scores", "ctcext_fetch_token_scores",
+                        "ctcext_token_scores_row", "ctcext_dense_token_scores_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TOKEN_SCORES_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -123,6 +127,11 @@ class DenseOutputs(ctypes.Structure):
 class TokenTimesOut(ctypes.Structure):
     """ctcext_token_times: the outputs of the token-times calls."""
     _fields_ = [("start", ctypes.c_void_p), ("end", ctypes.c_void_p), ("trailing_blank", ctypes.c_void_p)]
+
+
+class TokenScoresOut(ctypes.Structure):
+    """ctcext_token_scores: the outputs of the token-scores calls."""
+    _fields_ = [("logp_sum", ctypes.c_void_p), ("logp_min", ctypes.c_void_p)]
 
 
 class SkipArgs(ctypes.Structure):
@@ -342,6 +351,24 @@ def load():
                                                    ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]
         lib.ctcext_skip_plan_chunk_row.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_token_scores"):   # (CTCEXT_HAS_TOKEN_SCORES; older builds stay loadable for A/B runs)
+        lib.ctcext_token_scores_tile.argtypes = []
+        lib.ctcext_token_scores_tile.restype = ctypes.c_int32
+        lib.ctcext_dense_token_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(TokenTimesOut),
+                                                  ctypes.POINTER(TokenScoresOut)]
+        lib.ctcext_dense_token_scores.restype = ctypes.c_int
+        lib.ctcext_fetch_token_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(TokenScoresOut), ctypes.c_int32]
+        lib.ctcext_fetch_token_scores.restype = ctypes.c_int
+        # (x[frames][num_classes] and norm[frames] of the compute dtype, f64, frames, num_classes,
+        #  int64 alignment[L], L, int32 start[m], int32 end[m], m, blank_index, blank_label, logp_sum[m], logp_min[m])
+        lib.ctcext_token_scores_row.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                                ctypes.c_void_p]
+        lib.ctcext_token_scores_row.restype = ctypes.c_int
+        lib.ctcext_dense_token_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_token_scores_ms.restype = ctypes.c_int
     _lib = lib
     return lib
 

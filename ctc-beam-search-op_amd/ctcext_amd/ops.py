@@ -231,7 +231,7 @@ def _args(x_ptr, shape, dtype_code, on_device, sl_ptr, sl_shape, beam_width, top
 def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
                                 merge_repeated=False, blank_index=0, blank_label=-1,
                                 name=None, *, flags=0, outputs="auto", devices=None, scorer_table=None,
-                                skip_blank=None):
+                                skip_blank=None, token_scores=False):
     """Drop-in for the reference op.  See the module docstring.
 
     Keyword-only extensions (not in the reference):
@@ -255,6 +255,11 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
         (dropped frames read blank_label); log_probability is that of the kept
         frames, not corrected for the dropped ones.  ``kept_frames()`` returns
         the frames kept per item.  One device only.
+      token_scores: True keeps what ``token_scores()`` reads after this call:
+        for device inputs a reference to the tensor the kernels read (which
+        may be a contiguous copy of ``inputs``), until the calling thread's
+        next decode on that device.  Without it ``token_scores()`` raises
+        ``FailedPreconditionError``.  One device only.
     """
     del name
     if outputs not in ("auto", "host", "device"):
@@ -295,7 +300,7 @@ def ctc_ext_beam_search_decoder(inputs, sequence_length, beam_width, top_paths,
               blank_index, blank_label, flags, stream)
     return _decode_and_fetch(lib, a, keep, shape, on_device, x.device if on_device else None,
                              x.dtype if on_device else np.dtype(x.dtype), index, outputs, devices, scorer_table,
-                             skip_blank)
+                             skip_blank, token_scores)
 
 
 def logits_layout(shape, strides, batch_first=True):
@@ -328,7 +333,7 @@ def logits_layout(shape, strides, batch_first=True):
 
 def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
                   merge_repeated=False, blank_index=0, blank_label=-1,
-                  flags=0, outputs="auto", devices=None, scorer_table=None, skip_blank=None):
+                  flags=0, outputs="auto", devices=None, scorer_table=None, skip_blank=None, token_scores=False):
     """Decode the logits tensor an acoustic model produces, as it is.
 
     ``logits`` is a torch tensor of dtype float16, bfloat16, float32 or
@@ -340,9 +345,9 @@ def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
     otherwise it is made contiguous first.  Half-precision logits are widened
     to float32 as the kernels read them, which is exact: the result is that of
     ``ctc_ext_beam_search_decoder(logits.float().transpose(0, 1), ...)``, and
-    ``log_probability`` is float32.  The other arguments (``skip_blank``
-    among them) and the returned ``CTCExtBeamSearchDecoder`` tuple are the
-    drop-in function's.
+    ``log_probability`` is float32.  The other arguments (``skip_blank`` and
+    ``token_scores`` among them) and the returned ``CTCExtBeamSearchDecoder``
+    tuple are the drop-in function's.
     """
     if outputs not in ("auto", "host", "device"):
         raise ValueError("outputs must be 'auto', 'host' or 'device'")
@@ -394,7 +399,7 @@ def decode_logits(logits, lengths, beam_width, top_paths, *, batch_first=True,
     a.inputs_format = fmt
     a.inputs_stride_t, a.inputs_stride_b = int(st_t), int(st_b)
     return _decode_and_fetch(lib, a, [x, sl], shape, on_device, dev, table_dtype, index, outputs, devices,
-                             scorer_table, skip_blank)
+                             scorer_table, skip_blank, token_scores)
 
 
 DenseDecode = collections.namedtuple(
@@ -404,7 +409,7 @@ DenseDecode = collections.namedtuple(
 
 def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
                  merge_repeated=False, blank_index=0, blank_label=-1, pad_value=-1,
-                 flags=0, scorer_table=None, out=None, skip_blank=None):
+                 flags=0, scorer_table=None, out=None, skip_blank=None, token_scores=False):
     """Decode GPU logits into padded GPU tensors without waiting for anything.
 
     The call validates what it can on the host, enqueues the whole decode on
@@ -438,6 +443,12 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
     ``skip_blank`` is ``ctc_ext_beam_search_decoder``'s: with it the call is
     still enqueue-only, alignment rows stay ``T`` wide, and ``kept_frames()``
     returns an int32 CUDA tensor this call writes without waiting.
+
+    ``token_scores=True`` keeps a reference to the tensor the kernels read
+    (``logits`` itself, or the contiguous copy made of it) until the calling
+    thread's next decode on that device, so that ``dense_token_scores()`` can
+    read it; without it that call raises ``FailedPreconditionError``.  In a
+    captured graph the scores read the static input the decode read.
     """
     lib = _lib.load()
     skip = None if skip_blank is None else _skip_args(lib, skip_blank)
@@ -503,6 +514,7 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
      o.status) = [t.data_ptr() for t in out]
     o.pad_value = int(pad_value)
     dec = get_decoder(index)
+    dec._scores_keep = dec._scores_dense = dec._scores_sync = None
     if skip is None:
         rc = lib.ctcext_decode_dense(dec.handle, ctypes.byref(a), ctypes.byref(o))
     else:
@@ -515,6 +527,9 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
     dec._kept = None if skip is None else kept
     dec.last_stats = dec.stats()
     dec._times_dense = (B, P, T, dev)   # (dense_token_times' output shapes)
+    if token_scores:   # (dense_token_scores' output shapes and dtype, and the rows its kernel reads)
+        dec._scores_keep = x
+        dec._scores_dense = (B, P, T, dev, fdt)
     # x, sl and tab may be temporaries: they were allocated on this stream, and
     # the caching allocator hands their memory out again in stream order
     del x, sl, tab
@@ -522,6 +537,7 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
 
 
 TokenTimes = collections.namedtuple("TokenTimes", ["start", "end", "trailing_blank"])
+TokenScores = collections.namedtuple("TokenScores", ["logp_sum", "logp_min"])
 
 
 def _times_lib(lib):
@@ -609,6 +625,132 @@ def token_times(device=None):
     return out
 
 
+def _scores_lib(lib):
+    if not hasattr(lib, "ctcext_dense_token_scores"):
+        raise UnimplementedError("this libctcext.so has no token scores (CTCEXT_HAS_TOKEN_SCORES)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+_NO_SCORES = "token scores need a decode with token_scores=True"
+
+
+def _scores_device(dev, B, P, width, dtype):
+    """Uninitialised CUDA outputs of a token-scores call and their struct."""
+    import torch
+    with torch.cuda.device(dev):
+        out = TokenScores(torch.empty((B, P, width), dtype=dtype, device=dev),
+                          torch.empty((B, P, width), dtype=dtype, device=dev))
+    o = _lib.TokenScoresOut()
+    o.logp_sum, o.logp_min = [t.data_ptr() for t in out]
+    return out, o
+
+
+def dense_token_scores(times=None, device=None):
+    """How sure the decoder is of every decoded token of the calling thread's
+    last ``decode_dense(..., token_scores=True)`` on ``device`` (None: the
+    current one), without waiting for anything: one small kernel enqueued
+    behind the decode and its token times, on the stream the decode went to
+    (so it can be captured into the same ``torch.cuda.graph``).
+
+    ``times`` is what ``dense_token_times()`` returned for that decode; None
+    calls it here.  Returns ``TokenScores(logp_sum, logp_min)``: CUDA tensors
+    of the compute dtype, ``[B, top_paths, T]``.  For token ``i`` of row
+    ``[b, p]``, over the frames ``start[b, p, i] .. end[b, p, i]`` of the best
+    alignment, ``logp_sum`` is the sum and ``logp_min`` the minimum of the
+    log-posterior of the class the alignment holds at that frame (the blank's
+    at the blank frames inside a merged token), from the decoder's own
+    normaliser.  Tokens without times, everything past the row's decoded
+    length and every row of an item with a status bit are NaN.  The mean
+    confidence of a token is ``exp(logp_sum / (end - start + 1))``.  The
+    definition is in ``include/ctcext.h``, "Token scores"; the ``blank_label``
+    rule of the token times applies."""
+    what = "ctcext_dense_token_scores without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = _scores_lib(dec.lib)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_SCORES, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    if times is None:
+        times = dense_token_times(device)
+    for name, v in (("start", times.start), ("end", times.end)):
+        if not (_is_torch(v) and v.is_cuda and v.device == dev and tuple(v.shape) == (B, P, T)
+                and str(v.dtype) == "torch.int32" and v.is_contiguous()):
+            raise ValueError("times.%s must be a contiguous int32 tensor of shape %s on %s" % (name, (B, P, T), dev))
+    t = _lib.TokenTimesOut()
+    t.start, t.end = times.start.data_ptr(), times.end.data_ptr()
+    out, o = _scores_device(dev, B, P, T, fdt)
+    rc = lib.ctcext_dense_token_scores(dec.handle, ctypes.byref(t), ctypes.byref(o))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def token_scores(device=None):
+    """``dense_token_scores`` for the synchronous calls: the scores of the
+    hypotheses the calling thread's last ``ctc_ext_beam_search_decoder`` or
+    ``decode_logits`` with ``token_scores=True`` on ``device`` returned (a
+    stream keeps no logits: not after a push).  Waits.  Returns numpy arrays,
+    or CUDA tensors where that call's outputs were."""
+    what = "ctcext_fetch_token_scores without a successful ctcext_decode"
+    dec = _thread_decoder(device, what)
+    lib = _scores_lib(dec.lib)
+    if getattr(dec, "_times_sync", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_sync", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_SCORES, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, to_device, f64 = shape
+    if to_device:
+        import torch
+        out, o = _scores_device(torch.device("cuda", dec.device), B, P, T, torch.float64 if f64 else torch.float32)
+    else:
+        dt = np.float64 if f64 else np.float32
+        out = TokenScores(np.empty((B, P, T), dt), np.empty((B, P, T), dt))
+        o = _lib.TokenScoresOut()
+        o.logp_sum, o.logp_min = [t.ctypes.data for t in out]
+    rc = lib.ctcext_fetch_token_scores(dec.handle, ctypes.byref(o), 1 if to_device else 0)
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def token_scores_row(x, norm, alignment, frames, start, end, blank_index, blank_label):
+    """The definition of the token scores for one row, on the host (no GPU):
+    ``x`` is one item's logits ``[frames, num_classes]`` (float32 or float64,
+    the compute dtype), ``norm`` its rows' normaliser ``[frames]``,
+    ``alignment`` one path's alignment row in label order (without padding),
+    ``start`` / ``end`` that path's token times.  Returns ``(logp_sum,
+    logp_min)``: arrays of ``len(start)`` of ``x``'s dtype."""
+    lib = _scores_lib(_lib.load())
+    x = np.asarray(x)
+    dt = np.float64 if x.dtype == np.float64 else np.float32
+    frames = int(frames)
+    x = np.ascontiguousarray(x[:frames], dtype=dt)
+    if x.ndim != 2:
+        raise ValueError("token_scores_row: x must be [frames, num_classes]")
+    nm = np.ascontiguousarray(np.asarray(norm).reshape(-1)[:frames], dtype=dt)
+    if x.shape[0] != frames or nm.size != frames:
+        raise ValueError("token_scores_row: x and norm must hold the item's frames")
+    al = np.ascontiguousarray(np.asarray(alignment, dtype=np.int64).reshape(-1))
+    st = np.ascontiguousarray(np.asarray(start, dtype=np.int32).reshape(-1))
+    en = np.ascontiguousarray(np.asarray(end, dtype=np.int32).reshape(-1))
+    if st.size != en.size:
+        raise ValueError("token_scores_row: start and end must have one length")
+    lsum = np.empty((st.size,), dt)
+    lmin = np.empty((st.size,), dt)
+    rc = lib.ctcext_token_scores_row(x.ctypes.data, nm.ctypes.data, 1 if dt == np.float64 else 0, frames,
+                                     int(x.shape[1]), _ptr(al, ctypes.c_int64), int(al.size),
+                                     _ptr(st, ctypes.c_int32), _ptr(en, ctypes.c_int32), int(st.size),
+                                     int(blank_index), int(blank_label), lsum.ctypes.data, lmin.ctypes.data)
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_token_scores_row: bad arguments", rc)
+    return lsum, lmin
+
+
 def kept_frames(device=None):
     """The frames each item kept in the calling thread's last decode with
     ``skip_blank`` on ``device`` (None: the current one): a numpy int32 ``[B]``
@@ -686,7 +828,7 @@ def _lengths_host(sequence_length):
 
 
 def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index, outputs, devices, scorer_table,
-                      skip_blank=None):
+                      skip_blank=None, token_scores=False):
     """Everything after the inputs are described by ``a``: validation, the
     beam-scorer table, the handle, phase 1, output allocation and phase 2.
     ``shape`` is the logical (max_time, batch, num_classes); ``table_dtype``
@@ -734,6 +876,7 @@ def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index
         import torch
         torch.cuda.current_stream(device).synchronize()
     dec._kept = None
+    dec._scores_keep = dec._scores_dense = dec._scores_sync = None
     if skip is not None:
         # the kept counts: device memory for device inputs, host memory otherwise
         nb = max(int(shape[1]), 0) if len(shape) == 3 else 0
@@ -750,6 +893,11 @@ def _decode_and_fetch(lib, a, keep, shape, on_device, device, table_dtype, index
         dec._kept = kept.cpu().numpy() if on_device else kept
     to_device = outputs == "device" or (outputs == "auto" and on_device)
     dec._times_sync = (int(shape[1]), int(top_paths), int(shape[0]), to_device)   # (token_times' output shapes)
+    if token_scores:
+        # (token_scores' output shapes and dtype; device inputs are read in place again by its kernel, host
+        # inputs from the copy the library staged)
+        dec._scores_keep = list(keep) if on_device else None
+        dec._scores_sync = dec._times_sync + (code == _lib.CTCEXT_F64,)
     out = _fetch_outputs(dec, sizes, int(shape[1]), int(top_paths), code, to_device)
     del keep
     _print_no_label(dec.last_stats["no_label_paths"])
@@ -1032,6 +1180,7 @@ class StreamDecoder:
         szs = [(s.num_decoded, s.max_decoded, s.num_alignment, s.max_alignment) for s in sizes]
         to_device = outputs == "device" or (outputs == "auto" and on_device)
         dec._times_sync = (int(a.batch_size), P, int(a.max_frames), to_device)   # (token_times' output shapes)
+        dec._scores_keep = dec._scores_sync = None   # (a push leaves nothing for token_scores)
         out = _fetch_outputs(dec, szs, int(a.batch_size), P, a.dtype, to_device)
         _print_no_label(dec.last_stats["no_label_paths"])
         return out

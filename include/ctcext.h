@@ -853,6 +853,107 @@ int ctcext_stream_kept(ctcext_stream* s, int64_t* kept);
 int ctcext_skip_plan_chunk_row(const void* logp_blank, int32_t f64, int64_t n, double thr, int64_t first_frame,
                                int32_t prev_dom, int32_t* kmap, int64_t* kept, int32_t* last_dom);
 
+/* ---------------------------------------------------------------------------
+ * Token scores: the sum and the minimum of the per-frame log-posteriors over
+ * every timed token's span of the best alignment, on the device -- "how sure"
+ * beside the token times' "where".  New entry points and structs only
+ * (CTCEXT_ABI_VERSION is unchanged; detect them by CTCEXT_HAS_TOKEN_SCORES at
+ * build time or by symbol at run time).
+ *
+ * Definition.  The inputs, for one path of item b, are
+ *   ftype       the compute dtype (float32, or float64 for float64 logits),
+ *   frames, dec[0..m), ali[0..L), start[0..m), end[0..m)
+ *               exactly as in "Token times",
+ *   x[f][c]     the item's logits as the decode read them, widened exactly to
+ *               ftype,
+ *   norm[f]     the decoder's normaliser of that row, in ftype.
+ *
+ *   def token_scores(x, norm, ali, frames, start, end, blank_index, blank_label):
+ *       base, m = frames - len(ali), len(start)
+ *       lsum, lmin = [nan] * m, [nan] * m
+ *       for i in range(m):
+ *           if start[i] < 0: continue                      # untimed token: NaN
+ *           for f in range(start[i], end[i] + 1):          # ascending frames, every frame of the span
+ *               v = ali[f - base]
+ *               c = blank_index if v == blank_label else v
+ *               lp = ftype(x[f][c]) - norm[f]              # one rounded subtraction in ftype
+ *               if f == start[i]: acc = mn = lp
+ *               else:
+ *                   acc = ftype(acc + lp)                  # one rounded add, this order, no fma
+ *                   if lp < mn: mn = lp                    # a NaN never replaces, a leading NaN stays
+ *           lsum[i], lmin[i] = acc, mn
+ *       return lsum, lmin
+ *
+ * A merged token's span includes the blank frames between its runs; those
+ * frames contribute the blank's log-posterior.  The outputs are logp_sum and
+ * logp_min, of ftype, [batch][top_paths][width], width being max_time.
+ * Everything that is not a timed token is a NaN: untimed tokens, cells past the
+ * row's decoded length, and every row of an item with a status bit.  After a
+ * skipping decode the definition applies on the original time axis: to the
+ * expanded alignment rows, in which dropped frames read blank_label, to the
+ * caller's rows, and to the normaliser of the caller's rows that the plan
+ * computed.  The blank_label rule of token times applies unchanged, with the
+ * same message.  Mean confidence is exp(logp_sum / (end - start + 1)): the
+ * caller's one elementwise op, not computed here.
+ *
+ * The kernel trusts nothing in start / end: it scores a token only when
+ * 0 <= start <= end < frames, start >= frames - L, the token index is below
+ * the decoded length, and each alignment value of the span is blank_label or
+ * in [0, num_classes); otherwise the cell is a NaN and nothing outside the
+ * buffers is read.  No cell is written twice.
+ *
+ * The logits contract: the score calls read the inputs of the decode they
+ * follow -- the caller's tensor, through the pointer, format and strides that
+ * call was given (for host inputs of a synchronous call: the staged copy in
+ * the workspace).  That memory must still be there, unchanged, when the kernel
+ * runs; the library keeps no copy.
+ *
+ * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED), and
+ * streams.  A push keeps neither its chunk nor its normaliser, and an
+ * alignment can move to any class at any earlier frame, so a stream would need
+ * a per-frame posterior store with the commit's roll-back rules; there is no
+ * stream entry point. */
+#define CTCEXT_HAS_TOKEN_SCORES 1
+
+/* Device pointers, [batch][top_paths][max_time] of the compute dtype.  Either
+ * may be NULL, not both. */
+typedef struct {
+  void* logp_sum;
+  void* logp_min;
+} ctcext_token_scores;
+
+/* Frames of a row the kernel covers per step, aligned to multiples of it on
+ * the item's time axis (a token whose span crosses a multiple carries its sum
+ * and minimum across steps); for tests. */
+int32_t ctcext_token_scores_tile(void);
+/* Enqueues the token-scores kernel on the stream of the last
+ * ctcext_decode_dense / ctcext_decode_dense_skip, behind whatever that stream
+ * holds, over that call's rows.  times->start / times->end are what
+ * ctcext_dense_token_times wrote for the same call (both required;
+ * trailing_blank is not read).  No allocation, no host-blocking call, no
+ * device-to-host copy; capturable into the same graph as the decode.  Without
+ * a preceding dense decode: CTCEXT_FAILED_PRECONDITION. */
+int ctcext_dense_token_scores(ctcext_decoder* dec, const ctcext_token_times* times, const ctcext_token_scores* out);
+/* Synchronous; valid after ctcext_decode / ctcext_decode_skip (not after a
+ * stream's push: CTCEXT_FAILED_PRECONDITION).  Computes the times into
+ * workspace itself, then the scores.  out's pointers are device pointers with
+ * outputs_on_device, host pointers without.  One-device handles only:
+ * CTCEXT_UNIMPLEMENTED otherwise. */
+int ctcext_fetch_token_scores(ctcext_decoder* dec, const ctcext_token_scores* out, int32_t outputs_on_device);
+/* Host only, no HIP call: the definition above for one row, in plain C++ that
+ * shares no code with the kernel.  x is one item's rows, dense
+ * [frames][num_classes], and norm [frames], both of the compute dtype (f64:
+ * doubles, else floats); alignment holds L <= frames values; start / end hold
+ * m; logp_sum / logp_min (either may be NULL, not both) receive m values.  A
+ * span outside the walk, or a value that maps to no class, gives NaN as in the
+ * kernel. */
+int ctcext_token_scores_row(const void* x, const void* norm, int32_t f64, int64_t frames, int64_t num_classes,
+                            const int64_t* alignment, int64_t L, const int32_t* start, const int32_t* end, int64_t m,
+                            int32_t blank_index, int64_t blank_label, void* logp_sum, void* logp_min);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
+ * last token-scores kernel of a dense call in ms.  Waits for it. */
+int ctcext_dense_token_scores_ms(ctcext_decoder* dec, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,9 @@ Gaussian and on peaky inputs (+8 on one class per row, the blank with p = 0.7):
 its HIP-event time under CTCEXT_FLAG_PROFILE beside the pack kernel's of the
 same run and the whole call's (events around decode_dense + dense_token_times).
 
+With --scores, instead: the token-scores kernel (dense_token_scores) on the
+same two inputs, beside the token-times and the pack kernels' of the same run.
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -148,6 +151,52 @@ def times_report(args):
     return lines, res
 
 
+def scores_report(args):
+    """--scores: one row per input family at cfg3."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    lines = ["%-10s %14s %14s %14s %14s %8s %11s   (median of %d, ms; cfg3 B=%d T=%d C=%d W=%d P=%d)"
+             % ("inputs", "token scores", "token times", "pack kernel", "whole call", "sc/tt", "scored/tok", args.runs,
+                B, T, C, W, P)]
+    res = {"runs": args.runs, "shape": [B, T, C, W, P], "scores": {}}
+    for kind in ("gaussian", "peaky"):
+        x = times_inputs(kind, T, B, C)
+        ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, token_scores=True, **KW)   # warm-up: workspace, kernels
+        ctcext_amd.dense_token_scores()
+        ctcext_amd.dense_check()
+        sc_ms, tt_ms, pack_ms, call_ms = [], [], [], []
+        for _ in range(args.runs):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE,
+                                          token_scores=True, **KW)
+            tt = ctcext_amd.dense_token_times()
+            sc = ctcext_amd.dense_token_scores(tt)
+            e1.record()
+            e1.synchronize()
+            ctcext_amd.dense_check()
+            ms = ctypes.c_double()
+            for fn, acc in ((dec.lib.ctcext_dense_token_scores_ms, sc_ms), (dec.lib.ctcext_dense_token_times_ms, tt_ms),
+                            (dec.lib.ctcext_dense_pack_ms, pack_ms)):
+                if fn(dec.handle, ctypes.byref(ms)) != _lib.CTCEXT_OK:
+                    raise SystemExit(dec.lib.ctcext_last_error().decode())
+                acc.append(ms.value)
+            call_ms.append(e0.elapsed_time(e1))
+        tokens = int(out.decoded_lengths.sum())
+        scored = int((~torch.isnan(sc.logp_sum)).sum())
+        frames = int(((tt.end - tt.start + 1) * (tt.start >= 0)).sum())
+        ratio = statistics.median(sc_ms) / statistics.median(tt_ms)
+        lines.append("%-10s %14.4f %14.4f %14.4f %14.3f %8.2f %5d/%-5d"
+                     % (kind, statistics.median(sc_ms), statistics.median(tt_ms), statistics.median(pack_ms),
+                        statistics.median(call_ms), ratio, scored, tokens))
+        res["scores"][kind] = {"token_scores": stat(sc_ms), "token_times": stat(tt_ms), "pack": stat(pack_ms),
+                               "call": stat(call_ms), "scores_over_times": round(ratio, 3), "tokens": tokens,
+                               "scored": scored, "span_frames": frames}
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -158,9 +207,11 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="libctcext.so of the parent commit, for (iii)")
     ap.add_argument("--out", default=None, help="also write the tables and the JSON line here")
     ap.add_argument("--times", action="store_true", help="the token-times kernel's cost at cfg3 instead")
+    ap.add_argument("--scores", action="store_true",
+                    help="the token-scores kernel's cost at cfg3, beside the token-times and pack kernels' of the same run")
     args = ap.parse_args()
-    if args.times:
-        lines, res = times_report(args)
+    if args.times or args.scores:
+        lines, res = scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
