@@ -164,47 +164,6 @@ __device__ __forceinline__ float row16_fmax_dpp(float v) {
       : "+v"(v));
   return v;
 }
-// The set mode's beam (kSetMode): W <= 128 (value, slot) pairs, position j in
-// lane j & 63 of (sv0, ss0) for j < 64, of (sv1, ss1) above; +inf past W.
-__device__ __forceinline__ float row16_fmin_dpp(float v) {
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_min_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf"
-      : "+v"(v));
-  return v;
-}
-// position loc (uniform) := (v, s)
-__device__ __forceinline__ void set_put(float& sv0, int& ss0, float& sv1, int& ss1, int loc, float v, int s) {
-  const bool me = (int)(threadIdx.x & 63) == (loc & 63);
-  if (loc < 64) {
-    sv0 = me ? v : sv0;
-    ss0 = me ? s : ss0;
-  } else {
-    sv1 = me ? v : sv1;
-    ss1 = me ? s : ss1;
-  }
-}
-// the set's minimum (fv), its slot (fs) and position (loc), and whether another
-// position holds the same value (tied: which of them a heap would evict
-// depends on its layout).  Values are finite, never NaN.
-__device__ __forceinline__ void set_front(float sv0, int ss0, float sv1, int ss1, float& fv, int& fs, int& loc,
-                                          bool& tied) {
-  const float r = row16_fmin_dpp(__builtin_fminf(sv0, sv1));
-  const float a = bcast(r, 15), b = bcast(r, 31), c = bcast(r, 47), d = bcast(r, 63);
-  const float mm = __builtin_fminf(__builtin_fminf(a, b), __builtin_fminf(c, d));
-  const uint64_t e0 = __ballot(sv0 == mm), e1 = __ballot(sv1 == mm);
-  tied = (__builtin_popcountll(e0) + __builtin_popcountll(e1)) > 1;
-  const int l0 = (int)__builtin_ctzll(e0), l1 = (int)__builtin_ctzll(e1);
-  loc = e0 ? l0 : 64 + l1;
-  fs = e0 ? __builtin_amdgcn_readlane(ss0, l0) : __builtin_amdgcn_readlane(ss1, l1);
-  fv = mm;
-}
 // the same by v_max_f32 (IEEE maxNum: a NaN operand loses; of +0 and -0
 // either may come back) -- for maxima whose zero sign nothing reads (the row
 // facts' maxima: compared, or subtracted from values as a softmax maximum)
@@ -1219,49 +1178,22 @@ __device__ __forceinline__ void wave_make_heap_m(CTCX_LDS HE<T>* he, const HeapM
 // later (or behind an s_nop); DS operand registers are rewritten only after
 // the s_waitcnt lgkmcnt(0) that retires their instruction; lane selects come
 // from SALU.  Temporaries: s84..s99, vcc, v232..v243 (clobbered).
-// The bottom each lane's branch turn sees (bat; decoder.h:151-159): read
-// only for one lane at a time (a re-offer's lane, the chunk's last lane), so
-// with CTCX_BAT_LAZY the loop records the front after each push in lane k of
-// fa (one v_writelane, m0 = k) instead of refreshing bat in every later turn's
-// lane (a compare, a move and a select per push); the caller derives a lane's
-// bat from the last push before its turn start (bat_of in exact_step).
-#ifndef CTCX_BAT_LAZY
-#define CTCX_BAT_LAZY 0
-#endif
-#if CTCX_BAT_LAZY
-#define CTCX_BAT_A ""
-#define CTCX_BAT_B "v_writelane_b32 %[bat], %[fv], m0\n\t"   /* fa[k] = the front after push k */
-#define CTCX_BAT_C ""
-#else
+// The bottom each lane's branch turn sees (bat; decoder.h:151-159) is
+// refreshed after each push in every later turn's lane (CTCX_BAT_A/B/C: a
+// compare, a move and a select, spread over the push).
 #define CTCX_BAT_A "v_cmp_lt_i32_e64 vcc, %[k], %[sl]\n\t"   /* turns starting after lane k see the new bottom */
 #define CTCX_BAT_B "v_mov_b32_e32 v242, %[fv]\n\t"
 #define CTCX_BAT_C "v_cndmask_b32_e32 %[bat], %[bat], v242, vcc\n\t"
-#endif
-constexpr bool kBatLazy = CTCX_BAT_LAZY != 0;
 #ifdef CTCX_PHASES
 #define CTCX_EVCNT "s_add_u32 %[cnt], %[cnt], 1\n\t"   // diagnostics builds: count the pushes
 #else
 #define CTCX_EVCNT ""
 #endif
-// CTCX_HE_B64=1: the push's two node stores as ds_write_b64 (one 16-lane-group
-// access each, conflict-free over the lanes' consecutive dummy slots) instead
-// of ds_write2_b32 (two 32-lane accesses, banks (a/4) mod 32: lanes j and
-// j + 16 collide on their dummies); the min child then lives in the even
-// pair v[238:239] and the path mask in v237 (same clobbers)
-#ifndef CTCX_HE_B64
-#define CTCX_HE_B64 0
-#endif
-#if CTCX_HE_B64
-#define CTCX_HEV_CV "v238"
-#define CTCX_HEV_CS "v239"
-#define CTCX_HEV_BT "v237"
-#define CTCX_HEV_STORES "ds_write_b64 v237, v[238:239]\n\tds_write_b64 v236, v[240:241]\n\t"
-#else
+// the push's min child (value, slot), its path mask, and the two node stores
 #define CTCX_HEV_CV "v237"
 #define CTCX_HEV_CS "v238"
 #define CTCX_HEV_BT "v239"
 #define CTCX_HEV_STORES "ds_write2_b32 v239, v237, v238 offset1:1\n\tds_write2_b32 v236, v240, v241 offset1:1\n\t"
-#endif
 __device__ __forceinline__ int heap_events_f32(float s, int c, int sl, unsigned anc, unsigned req, unsigned aj,
                                                unsigned al, unsigned ar, unsigned dum, int& myslot, int& evr,
                                                float& bat, uint64_t& NC, uint64_t& RB, uint64_t& done, uint64_t LB,
@@ -1362,133 +1294,6 @@ __device__ __forceinline__ int heap_events_f32(float s, int c, int sl, unsigned 
       : "memory", "vcc", "m0", "s80", "s81", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93",
         "s94", "s95", "s96", "s97", "s98", "s99", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",
         "v240", "v241", "v242", "v243");
-  return st;
-}
-
-// The set mode's event loop (kSetMode, exact_step): heap_events_f32's
-// selections and bookkeeping, with the push a register write at the front's
-// position (floc) and the new front a DPP minimum over the set (row shifts,
-// then row_bcast 15 / 31: the minimum lands in lane 63), its position and slot
-// by ballot.  Returns 0 (no live lane wants in), 1 (lane k re-offers a branch
-// child: the caller decides it) or 2 (the next eviction meets equal minima,
-// ftied: which one a heap evicts depends on its layout -- replay).
-// Temporaries: s80..s81, s84..s96, vcc, m0, v232, v242.
-__device__ __forceinline__ int set_events_f32(float s, int c, int sl, float& sv0, int& ss0, float& sv1, int& ss1,
-                                              int& myslot, int& evr, float& bat, uint64_t& NC, uint64_t& RB,
-                                              uint64_t& done, uint64_t LB, float& fv, int& fs, int& floc, int& ftied,
-                                              int& nfree, int& nv, int nb, int& k, int& cnt) {
-  int st;
-  NC = uni64(NC); RB = uni64(RB); done = uni64(done); LB = uni64(LB);
-  fv = uni(fv); fs = uni(fs); floc = uni(floc); ftied = uni(ftied); nfree = uni(nfree); nv = uni(nv); nb = uni(nb);
-  cnt = uni(cnt);
-  asm volatile(
-      "s_mov_b32 %[st], 0\n\t"
-      "s_not_b64 s[80:81], %[done]\n\t"                    // lanes still to come
-      "v_cmp_lt_f32_e64 s[88:89], %[fv], %[s]\n\t"          // s > front
-      "s_and_b64 s[88:89], s[88:89], %[nc]\n\t"
-      "s_or_b64 s[88:89], s[88:89], %[rb]\n\t"
-      "s_and_b64 s[88:89], s[88:89], s[80:81]\n\t"         // m (SCC: m != 0)
-      "s_cbranch_scc0 .Lse_exit_%=\n\t"
-      "s_ff1_i32_b64 %[k], s[88:89]\n\t"
-      "s_bitcmp1_b64 %[lb], %[k]\n\t"
-      "s_cbranch_scc1 .Lse_rare_%=\n"
-      ".Lse_tail_%=:\n\t"
-      "s_cmp_lg_u32 %[ft], 0\n\t"                          // equal minima: the eviction is the heap's
-      "s_cbranch_scc1 .Lse_tie_%=\n\t"
-      "s_lshl_b64 s[80:81], -2, %[k]\n\t"                  // lanes after k
-      "v_readlane_b32 s84, %[s], %[k]\n\t"                 // v = offer k's score
-      "s_mov_b32 s85, %[fs]\n\t"                           // slot = the front's
-      "s_cmp_lt_i32 %[fs], %[nb]\n\t"
-      "s_cbranch_scc1 .Lse_evb_%=\n"
-      ".Lse_slot_%=:\n\t"
-      "v_cmp_eq_u32_e64 s[90:91], %[fs], %[my]\n\t"        // an entry accepted in this chunk is the evicted front
-      "s_mov_b32 m0, %[k]\n\t"
-      "v_cndmask_b32_e64 %[my], %[my], -1, s[90:91]\n\t"
-      "v_writelane_b32 %[my], s85, m0\n\t"                 // lane k: its entry's slot
-      CTCX_EVCNT
-      "s_and_b32 m0, %[floc], 63\n\t"                      // (v, slot) replaces the front
-      "s_cmp_lt_u32 %[floc], 64\n\t"
-      "s_cbranch_scc0 .Lse_put1_%=\n\t"
-      "v_writelane_b32 %[sv0], s84, m0\n\t"
-      "v_writelane_b32 %[ss0], s85, m0\n\t"
-      "s_branch .Lse_min_%=\n"
-      ".Lse_put1_%=:\n\t"
-      "v_writelane_b32 %[sv1], s84, m0\n\t"
-      "v_writelane_b32 %[ss1], s85, m0\n"
-      ".Lse_min_%=:\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_e32 v232, %[sv0], %[sv1]\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp v232, v232, v232 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp v232, v232, v232 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp v232, v232, v232 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp v232, v232, v232 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp v232, v232, v232 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_min_f32_dpp v232, v232, v232 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_readlane_b32 %[fv], v232, 63\n\t"                 // the new front's value
-      "s_nop 1\n\t"
-      "v_cmp_eq_f32_e64 s[86:87], %[fv], %[sv0]\n\t"       // its positions
-      "v_cmp_eq_f32_e64 s[92:93], %[fv], %[sv1]\n\t"
-      "s_bcnt1_i32_b64 s94, s[86:87]\n\t"
-      "s_bcnt1_i32_b64 s95, s[92:93]\n\t"
-      "s_add_u32 s94, s94, s95\n\t"
-      "s_cmp_gt_u32 s94, 1\n\t"
-      "s_cselect_b32 %[ft], 1, 0\n\t"
-      "s_ff1_i32_b64 s94, s[86:87]\n\t"
-      "s_ff1_i32_b64 s95, s[92:93]\n\t"
-      "s_cmp_lg_u64 s[86:87], 0\n\t"
-      "s_cbranch_scc0 .Lse_loc1_%=\n\t"
-      "s_mov_b32 %[floc], s94\n\t"
-      "v_readlane_b32 %[fs], %[ss0], s94\n\t"
-      "s_branch .Lse_locd_%=\n"
-      ".Lse_loc1_%=:\n\t"
-      "s_add_u32 %[floc], s95, 64\n\t"
-      "v_readlane_b32 %[fs], %[ss1], s95\n"
-      ".Lse_locd_%=:\n\t"
-      "v_cmp_lt_i32_e64 vcc, %[k], %[sl]\n\t"              // turns starting after lane k see the new bottom
-      "v_mov_b32_e32 v242, %[fv]\n\t"
-      "v_cndmask_b32_e32 %[bat], %[bat], v242, vcc\n\t"
-      "v_cmp_lt_f32_e64 s[88:89], %[fv], %[s]\n\t"         // next: s > front
-      "s_and_b64 s[88:89], s[88:89], %[nc]\n\t"
-      "s_or_b64 s[88:89], s[88:89], %[rb]\n\t"
-      "s_and_b64 s[88:89], s[88:89], s[80:81]\n\t"         // next m
-      "s_cbranch_scc0 .Lse_exit_%=\n\t"
-      "s_ff1_i32_b64 %[k], s[88:89]\n\t"
-      "s_bitcmp1_b64 %[lb], %[k]\n\t"
-      "s_cbranch_scc0 .Lse_tail_%=\n\t"                    // the next push, unless k is rare
-      "s_branch .Lse_rare_%=\n"
-      // the evicted front is a branch's entry: a fresh slot; record the
-      // eviction; a live re-offer of that branch is now wanted
-      ".Lse_evb_%=:\n\t"
-      "s_mov_b32 s85, %[nfree]\n\t"
-      "s_add_u32 %[nfree], %[nfree], 1\n\t"
-      "s_mov_b32 m0, %[nv]\n\t"
-      "s_add_u32 %[nv], %[nv], 1\n\t"
-      "v_writelane_b32 %[evr], %[fs], m0\n\t"
-      "v_cmp_eq_u32_e64 s[90:91], %[fs], %[c]\n\t"
-      "s_and_b64 s[90:91], s[90:91], %[lb]\n\t"
-      "s_or_b64 %[rb], %[rb], s[90:91]\n\t"
-      "s_branch .Lse_slot_%=\n"
-      ".Lse_tie_%=:\n\t"
-      "s_mov_b32 %[st], 2\n\t"
-      "s_branch .Lse_exit_%=\n"
-      ".Lse_rare_%=:\n\t"
-      "s_mov_b32 %[st], 1\n"
-      ".Lse_exit_%=:\n\t"
-      "s_not_b64 %[done], s[80:81]"
-      : [my] "+v"(myslot), [evr] "+v"(evr), [bat] "+v"(bat), [sv0] "+v"(sv0), [ss0] "+v"(ss0), [sv1] "+v"(sv1),
-        [ss1] "+v"(ss1), [nc] "+s"(NC), [rb] "+s"(RB), [done] "+s"(done), [fv] "+s"(fv), [fs] "+s"(fs),
-        [floc] "+s"(floc), [ft] "+s"(ftied), [nfree] "+s"(nfree), [nv] "+s"(nv), [k] "=&s"(k), [st] "=&s"(st),
-        [cnt] "+s"(cnt)
-      : [s] "v"(s), [c] "v"(c), [sl] "v"(sl), [lb] "s"(LB), [nb] "s"(nb)
-      : "memory", "vcc", "m0", "s80", "s81", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93",
-        "s94", "s95", "v232", "v242");
   return st;
 }
 
@@ -2153,44 +1958,6 @@ __device__ __forceinline__ void wsync() {
 #ifndef CTCX_SLEEP
 #define CTCX_SLEEP 1
 #endif
-// CTCX_RDY_TRIP=1: a chunk hand-over read as one LDS round trip (the count's
-// readfirstlane after the slot's words complete, not before they are issued).
-// Local ISA change, measured slower on the same box (cfg3 +0.2%, cfg4 +0.1%,
-// cfg2 +0.3%, cfg5 +0.2%; profiles/r6h_ab_rdy_trip.txt): off
-#ifndef CTCX_RDY_TRIP
-#define CTCX_RDY_TRIP 0
-#endif
-#if CTCX_RDY_TRIP
-#define CTCX_ONE_TRIP(rdy, ...) __asm__ volatile("" : "+v"(rdy) : __VA_ARGS__)
-#else
-#define CTCX_ONE_TRIP(rdy, ...) __asm__ volatile("" ::__VA_ARGS__)
-#endif
-// CTCX_HELPER_CALL=1: the helper wave's gather and rank functions as real
-// calls (Ctx by value, as literal_step), so their code is allocated apart from
-// wave 0's frame loop
-#ifndef CTCX_HELPER_CALL
-#define CTCX_HELPER_CALL 0
-#endif
-#if CTCX_HELPER_CALL
-#define CTCX_HELPER_FN __attribute__((noinline))
-#define CTCX_HCTX Ctx<T>
-#else
-#define CTCX_HELPER_FN __forceinline__
-#define CTCX_HCTX const Ctx<T>&
-#endif
-// ... and the unscored gather queue's helper (help_gather_chunks: large C,
-// beams of 129..256, cfg5's kernel) alone: cfg5 -0.4% (1457.0 vs 1462.8 ms,
-// profiles/r6s_ab_helper_call_gq.txt), within what placement moves: off
-#ifndef CTCX_HELPER_CALL_GQ
-#define CTCX_HELPER_CALL_GQ 0
-#endif
-#if CTCX_HELPER_CALL || CTCX_HELPER_CALL_GQ
-#define CTCX_HELPER_FN_GQ __attribute__((noinline))
-#define CTCX_HCTX_GQ Ctx<T>
-#else
-#define CTCX_HELPER_FN_GQ __forceinline__
-#define CTCX_HCTX_GQ const Ctx<T>&
-#endif
 constexpr int kTabSlots = CTCX_TAB_SLOTS;   // chunk slots in the ring
 // A hand-over wait gives up after ~1 s of the constant 100 MHz clock
 // (s_memrealtime), whatever the shader clock or the SIMD's other work: only a
@@ -2592,11 +2359,6 @@ struct GQ {
   CTCX_LDS u32x4* a;        // [slot][64]: scored offers (SQ)
   CTCX_LDS float* p;        // [slot][64]: their candidate values (SQ)
   int sm;                   // slots - 1 (a power of two)
-  // SQ, small C (kCtab, sq_ctab_bytes): branch i's children by label (cmask[i]
-  // bit l) and their positions (ctab[i * 64 + l]).  (Here, not in Ctx: Ctx
-  // goes by value to the literal step's call, whose register use then moves.)
-  CTCX_LDS uint64_t* cmask;
-  CTCX_LDS uint8_t* ctab;
 };
 // Scored slots per kernel: four for beams <= 128; one for beams of 129..256,
 // whose layout must stay under half a CU (cfg5: 80.1 KB of the 80 KB, a
@@ -2605,19 +2367,6 @@ struct GQ {
 __host__ __device__ constexpr int sq_slots(int wcap) { return wcap <= 128 ? kQSlots : 1; }
 __host__ __device__ inline size_t gq_lds_bytes(bool scored, int slots = kQSlots) {
   return (size_t)slots * ((scored ? 64 * 20 : 64 * 4) + 16);
-}
-// The scored queue at small C (C <= 64): each branch's children as a label
-// mask and a (branch, label) -> child position table, built at the commit
-// with the sibling lists, so the helper's GetChild (sq_score) is one or two
-// LDS reads instead of a walk down the branch's sibling list (one dependent
-// read pair per child: the frame's first branches, those the first chunk
-// holds, have the most children).
-#ifndef CTCX_CTAB
-#define CTCX_CTAB 0
-#endif
-constexpr bool kCtab = CTCX_CTAB != 0;
-__host__ __device__ constexpr size_t sq_ctab_bytes(int wcap, int C) {
-  return (kCtab && C <= 64) ? (size_t)wcap * 8 + (size_t)wcap * 64 : 0;
 }
 // The frame boundary of the scored queue's small-C kernels (SQ && !BIG: float,
 // beams <= 128, C <= 64, base scorer), off wave 0's chain (DESIGN, round 16):
@@ -2637,7 +2386,7 @@ __host__ __device__ constexpr size_t sq_ctab_bytes(int wcap, int C) {
 constexpr bool kRowPrefetch = CTCX_ROW_PREFETCH != 0;
 constexpr bool kEarlyChunk0 = CTCX_EARLY_CHUNK0 != 0;
 // the second row buffer, then four words: the frame it holds (kPfRowT; -1:
-// none) and that row's normaliser (kPfNorm).  After the children table, so
+// none) and that row's normaliser (kPfNorm).  After the gather queue, so
 // decode_lds_bytes (and with it ctcext_max_beam_width) is what it was.
 [[maybe_unused]] constexpr int kPfRowT = 0, kPfNorm = 1;
 __host__ __device__ constexpr size_t sq_rowpf_bytes(int64_t C) {
@@ -2649,14 +2398,15 @@ __host__ __device__ constexpr size_t sq_rowpf_bytes(int64_t C) {
 // position k needs that branch's words, its parent's and the row, not k: the
 // helper works on the final beam as wave 0 publishes it for the ranks (entry
 // j of the heap's copy: total xv[j], slot alias[j]), reads every source by
-// slot, and stages the nine RecNew fields per j, back-pointers as
-// (j << 1) | kind.  The commit, which knows each slot's position, moves the
-// staged words to e*[position] after its last read of e*[sorted[.]], and the
-// next frame's wave 0 skips recurse_wave0.
+// slot, and stages the recursion's nine result words per j (both endings, the
+// total, both candidates with their back-pointers, the flags, the label),
+// back-pointers as (j << 1) | kind.  The commit, which knows each slot's
+// position, moves the staged words to e*[position] after its last read of
+// e*[sorted[.]], and the next frame's wave 0 skips recurse_wave0.
 // The staging area follows the second row buffer (so decode_lds_bytes and
 // ctcext_max_beam_width are what they were): four words (kErT: the frame the
 // staged words are for, -1: none), then ten planes of wcap words (kErNbk ..
-// kErLab: RecNew's fields; kErPos: the position of entry j, written by the
+// kErLab: those nine words; kErPos: the position of entry j, written by the
 // commit).  During the hand-over the gather queue's offer plane (dead between
 // the grow's end and the next frame) holds two maps: slot -> j (kErMapSlot,
 // enc words) and branch -> j of its surviving entry (kErMapBr, wcap words).
@@ -2664,59 +2414,12 @@ __host__ __device__ constexpr size_t sq_rowpf_bytes(int64_t C) {
 #define CTCX_EARLY_RECURSE 1
 #endif
 constexpr bool kEarlyRecurse = CTCX_EARLY_RECURSE != 0 && kRowPrefetch && kEarlyChunk0;
-// CTCX_EARLY_BOTTOM: with the recursion in place at a frame's entry the helper
-// knows the starting bottom before it gathers (the smallest placed total).
-// 1: chunk 0 from -inf as before, chunk 1 without the wait for kCtlBot;
-// 2: chunk 0 gathered against the bottom too.  0: the wait as it was.
-// Both bit-exact, both measured slower than 0 in every pair (cfg3 112.8 ->
-// 113.3 / 114.0 ms per step, cfg2 41.64 -> 42.04 / 42.21, same box;
-// profiles/r17_ab_stages_cfg{3,2}.txt).  With the recursion gone wave 0
-// reaches its first-chunk wait as the helper publishes chunk 0 (the wait is 5
-// cycles per frame), and publishes kCtlBot at about the same moment, so the
-// helper's scan of the placed totals ahead of chunk 0 is on wave 0's chain
-// and the wait it removes is already short (no phase split of these two
-// builds was taken).  Off.
-#ifndef CTCX_EARLY_BOTTOM
-#define CTCX_EARLY_BOTTOM 0
-#endif
-constexpr int kEarlyBottom = kEarlyRecurse ? CTCX_EARLY_BOTTOM : 0;
 [[maybe_unused]] constexpr int kErT = 0;
 [[maybe_unused]] constexpr int kErNbk = 0, kErNl = 1, kErTot = 2, kErCb = 3, kErCn = 4, kErBpb = 5, kErBpn = 6,
                                kErFlg = 7, kErLab = 8, kErPos = 9, kErPlanes = 10;
 [[maybe_unused]] constexpr int kErMapSlot = 0, kErMapBr = 512;   // (word offsets in the offer plane: 3 * 128 + 2 <= 512)
 __host__ __device__ constexpr size_t sq_stage_bytes(int wcap, int64_t C) {
   return (kEarlyRecurse && C <= 64) ? 16 + (size_t)kErPlanes * (size_t)wcap * 4 : 0;
-}
-// Large C, beams of up to 256 (BIG kernels, WC > 0): GetChild through a
-// (parent, label) -> child hash table instead of a walk down the parent's
-// sibling list (up to one dependent LDS read pair per child of the branch:
-// at C = 5000, W = 256 the best branches hold tens of the beam's entries).
-// It lives in the per-frame new-leaf hash table's room (htab, >= 2W words),
-// which the commit no longer needs once its parents are linked: the commit
-// rebuilds it with the sibling lists, one word per branch
-// (parent << 24 | label << 8 | position; -1 empty), linear probing.  The
-// literal path's free list shares that room and runs instead of a grow; the
-// next commit rebuilds the table.
-#ifndef CTCX_CHASH
-#define CTCX_CHASH 0
-#endif
-constexpr bool kCHash = CTCX_CHASH != 0;
-__device__ __forceinline__ int chash_slot(uint32_t key, int hts) { return (int)(((key * 0x9E3779B1u) >> 12) & (uint32_t)(hts - 1)); }
-template <typename T>
-__device__ __forceinline__ int chash_find(const Ctx<T>& cx, bool v, int i, int l) {
-  const uint32_t key = ((uint32_t)i << 16) | (uint32_t)l;   // (parent, label)
-  int q = v ? chash_slot(key, cx.hts) : 0;
-  int cw = -1;
-  bool go = v;
-  while (__ballot(go)) {
-    if (go) {
-      const uint32_t w = (uint32_t)cx.htab[q];
-      if (w == 0xFFFFFFFFu) go = false;
-      else if ((w >> 8) == key) { cw = (int)(w & 255u); go = false; }
-      else q = (q + 1) & (cx.hts - 1);
-    }
-  }
-  return cw;
 }
 template <bool SCORED>
 __device__ __forceinline__ GQ gq_carve(CTCX_LDS char* p, int slots) {
@@ -2752,10 +2455,9 @@ __device__ __forceinline__ int sq_turn_lane(uint32_t pk) { return (int)((pk >> 2
 // branch child it re-offers (GetChild finds it; -1: none) and the child's
 // label-ending alignment candidate (decoder.h:172-185).  v: a real offer
 // (others skip the child walk).
-template <typename T, bool CT = false, bool CH = false>   // CT: the children table (small C), CH: the child hash
+template <typename T>
 __device__ __forceinline__ void sq_score(const Ctx<T>& cx, int buf, T norm, bool v, int i, int l, T& s, T& bt,
-                                         int& cw, Best<T>& cd, const CTCX_LDS uint64_t* cmask = nullptr,
-                                         const CTCX_LDS uint8_t* ctab = nullptr) {
+                                         int& cw, Best<T>& cd) {
   const T NI = ninf<T>();
   const int bl = sel(cx.lab, buf)[i];
   const int bflg = sel(cx.flg, buf)[i];
@@ -2766,11 +2468,6 @@ __device__ __forceinline__ void sq_score(const Ctx<T>& cx, int buf, T norm, bool
   const T p = cx.row[l] - norm;
   s = p + ((l == bl) ? bob : bt);
   cw = -1;
-  if constexpr (CT) {   // small C: the children table (sq_ctab_bytes)
-    if (v && ((cmask[i] >> (l & 63)) & 1ull)) cw = ctab[i * 64 + l];
-  } else if constexpr (CH) {   // large C: the child hash (kCHash)
-    cw = chash_find(cx, v, i, l);
-  } else
   for (int k = v ? hd : -1; __ballot(k >= 0);) {
     CTCX_HPC(cx, 27, 1);
     int nk = -1;
@@ -2799,7 +2496,7 @@ __device__ __forceinline__ void sq_score(const Ctx<T>& cx, int buf, T norm, bool
 template <typename T>
 __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, int nb, T norm, T bottom, int& i0,
                                                     int& li0, bool& gstop, CTCX_LDS u32x4* qa, CTCX_LDS float* qp,
-                                                    int& cqn, bool one_step, const GQ& gq) {
+                                                    int& cqn, bool one_step) {
   const int lane = threadIdx.x & 63;
   const int Cm1 = cx.C - 1, blank = cx.blank;
   const float rcp = 1.0f / (float)Cm1;
@@ -2826,7 +2523,7 @@ __device__ __forceinline__ void gather_small_scored(const Ctx<T>& cx, int buf, i
     T s, bt;
     int cw;
     Best<T> cd;
-    sq_score<T, kCtab>(cx, buf, norm, v, i, l, s, bt, cw, cd, gq.cmask, gq.ctab);
+    sq_score<T>(cx, buf, norm, v, i, l, s, bt, cw, cd);
     // a turn starting in this step (label index 0) and closed at this bottom
     const uint64_t brkM = __ballot(v && li == 0 && !(bt > bottom));
     const int kb = brkM ? (int)__builtin_ctzll(brkM) : 64;
@@ -2912,8 +2609,8 @@ __device__ __forceinline__ int wave_incl_sum_dpp(int v) {
   const int row = (int)(threadIdx.x & 63) >> 4;
   return v + (row == 0 ? 0 : row == 1 ? r0 : row == 2 ? r0 + r1 : r0 + r1 + r2);
 }
-template <typename T, bool CT>
-__device__ __forceinline__ void sq_br_load(const Ctx<T>& cx, int buf, int nb, T norm, const GQ& gq, SqBr<T>& S) {
+template <typename T>
+__device__ __forceinline__ void sq_br_load(const Ctx<T>& cx, int buf, int nb, T norm, SqBr<T>& S) {
   const int lane = threadIdx.x & 63;
   const int C = cx.C, blank = cx.blank;
   S.pv = cx.row[lane < C ? lane : 0] - norm;
@@ -2929,10 +2626,6 @@ __device__ __forceinline__ void sq_br_load(const Ctx<T>& cx, int buf, int nb, T 
     S.li[w] = own ? bl - (bl > blank ? 1 : 0) : -1;
     S.sl[w] = (cx.row[own ? bl : 0] - norm) + bob;
     uint64_t cm = 0;
-    if constexpr (CT) {   // the children table holds them by label: drop the blank's bit
-      const uint64_t m = v ? gq.cmask[ii] : 0ull;
-      cm = (m & lowmask(blank)) | ((blank >= 63 ? 0ull : (m >> (blank + 1))) << blank);
-    } else
     for (int k = v ? cx.head[ii] : -1; __ballot(k >= 0);) {
       CTCX_HPC(cx, 27, 1);
       if (k >= 0) {
@@ -2984,10 +2677,9 @@ __device__ __forceinline__ uint64_t sq_br_window(const SqBr<T>& S, int w, int nb
 }
 // Pass 1 of gather_small_sparse in that form: stages the chunk's packed words
 // at sc[0 .. cqn) and moves (i0, li0) to the resume point.
-template <typename T, bool CT>
+template <typename T>
 __device__ __forceinline__ void gather_small_branch(const Ctx<T>& cx, int buf, int nb, T bottom, int& i0, int& li0,
-                                                    bool& gstop, CTCX_LDS uint32_t* sc, int& cqn, const GQ& gq,
-                                                    const SqBr<T>& S) {
+                                                    bool& gstop, CTCX_LDS uint32_t* sc, int& cqn, const SqBr<T>& S) {
   const int lane = threadIdx.x & 63;
   const int Cm1 = cx.C - 1, blank = cx.blank;
   cqn = 0;
@@ -3017,9 +2709,7 @@ __device__ __forceinline__ void gather_small_branch(const Ctx<T>& cx, int buf, i
       const int l = li + (li >= blank ? 1 : 0);
       const bool ch = on && (((w ? S.cm[1] : S.cm[0]) >> li) & 1ull);
       int cw = -1;
-      if constexpr (CT) {
-        if (ch) cw = gq.ctab[i * 64 + l];
-      } else if (__ballot(ch)) {   // GetChild: the first child of that label in the sibling list
+      if (__ballot(ch)) {   // GetChild: the first child of that label in the sibling list
         for (int k = ch ? cx.head[i] : -1; __ballot(k >= 0);) {
           CTCX_HPC(cx, 27, 1);
           int nk = -1;
@@ -3097,11 +2787,10 @@ __device__ __forceinline__ void gather_small_branch(const Ctx<T>& cx, int buf, i
 // (once per chunk) scores the staged offers, lane r the r-th, and writes the
 // slot: the same entries, fields and order as gather_small_scored gives for
 // the same bottom.  The score s is the same expression in both passes.
-template <typename T, bool CT = false>
+template <typename T>
 __device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, int nb, T norm, T bottom, int& i0,
                                                     int& li0, bool& gstop, CTCX_LDS u32x4* qa, CTCX_LDS float* qp,
-                                                    int& cqn, const GQ& gq,
-                                                    [[maybe_unused]] const SqBr<T>* br = nullptr) {
+                                                    int& cqn, [[maybe_unused]] const SqBr<T>* br = nullptr) {
   const int lane = threadIdx.x & 63;
   const int Cm1 = cx.C - 1, blank = cx.blank;
   const float rcp = 1.0f / (float)Cm1;
@@ -3110,7 +2799,7 @@ __device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, i
   const int sp_i0 = i0;
   const bool sp_mid = li0 != 0;
   if constexpr (kSparseBranch) {   // pass 1 with a branch per lane
-    gather_small_branch<T, CT>(cx, buf, nb, bottom, i0, li0, gstop, sc, cqn, gq, *br);
+    gather_small_branch<T>(cx, buf, nb, bottom, i0, li0, gstop, sc, cqn, *br);
   } else
   while (cqn < 64 && i0 < nb) {   // pass 1: filter
     CTCX_HPC(cx, 31, 1);
@@ -3129,9 +2818,6 @@ __device__ __forceinline__ void gather_small_sparse(const Ctx<T>& cx, int buf, i
     const T p = cx.row[l] - norm;
     const T s = p + ((l == bl) ? bob : bt);
     int cw = -1;
-    if constexpr (CT) {
-      if (v && ((gq.cmask[i] >> (l & 63)) & 1ull)) cw = gq.ctab[i * 64 + l];
-    } else
     for (int k = v ? cx.head[i] : -1; __ballot(k >= 0);) {
       CTCX_HPC(cx, 27, 1);
       int nk = -1;
@@ -3234,13 +2920,9 @@ constexpr int kSqCap0 = CTCX_SQ_CAP0;   // large C: offers in the frame's first 
 // that stays exact has finite totals only), or chunk 1 would be gathered
 // dense and wave 0 would pay for offers the true bottom rejects.  A frame
 // whose recursion gave a non-finite total ends that wait through kCtlDone.
-// KNOWN (kEarlyRecurse, with EARLY): `known` is the frame's starting bottom
-// where the recursion was in place at the frame's entry (the smallest placed
-// total; -inf: not known, wait as above).  Chunk 1 is then gathered against it
-// without the wait for kCtlBot.
-template <typename T, bool BIG, bool EARLY = false, bool KNOWN = false>
-__device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, int nb, T norm, T pmax,
-                                                   T bottom, [[maybe_unused]] T known = T(0)) {
+template <typename T, bool BIG, bool EARLY = false>
+__device__ __forceinline__ void help_gather_scored(const Ctx<T>& cx, GQ q, int buf, int nb, T norm, T pmax,
+                                                   T bottom) {
   const int lane = threadIdx.x & 63;
   CTCX_LDS int* m = cx.misc;
   if (ctl_ld(m, kCtlDead) != 0) return;
@@ -3257,7 +2939,7 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
     // (kSparseBranch: the frame's branches into registers ahead of the first
     // sparse chunk, beside the wait for wave 0's starting bottom)
     if constexpr (!BIG && kSparseBranch)
-      if (c == (kSqFirst1 ? 1 : 0)) sq_br_load<T, kCtab>(cx, buf, nb, norm, q, br);
+      if (c == (kSqFirst1 ? 1 : 0)) sq_br_load<T>(cx, buf, nb, norm, br);
     [[maybe_unused]] const uint64_t hw0 = CTCX_HTIME();
     for (int spin = 0;; ++spin) {   // the grow still running, and wave 0 at most kSqLead chunks behind
       if (ctl_ld(m, kCtlDone) != 0) { done = true; break; }
@@ -3267,9 +2949,7 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
         break;
       }
       if (c < ctl_ld(m, kCtlCons) + (BIG ? 1 : kSqLead)) {
-        if constexpr (EARLY && KNOWN) {
-          if (c == 0 || known > ninf<T>() || ctl_ld(m, kCtlBot) != (int)0xff800000u) break;
-        } else if constexpr (EARLY) {
+        if constexpr (EARLY) {
           if (c == 0 || ctl_ld(m, kCtlBot) != (int)0xff800000u) break;
         } else {
           break;
@@ -3282,7 +2962,6 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
     // wave 0's bottom after its last chunk (it only rises)
     const T pb = (T)__builtin_bit_cast(float, (unsigned)ctl_ld(m, kCtlBot));
     bottom = pb > bottom ? pb : bottom;
-    if constexpr (KNOWN) bottom = (c > 0 && known > bottom) ? known : bottom;
 #ifdef CTCX_SQ_NOFILTER   // (diagnostics: every offer gathered, no closed turn found here)
     bottom = ninf<T>();
 #endif
@@ -3316,7 +2995,7 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
       T s, bt;
       int cw;
       Best<T> cd;
-      sq_score<T, false, kCHash>(cx, buf, norm, v, i, l, s, bt, cw, cd);
+      sq_score<T>(cx, buf, norm, v, i, l, s, bt, cw, cd);
       wsync<true>();
       if (v) {
         u32x4 ev;
@@ -3333,9 +3012,9 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
       // next chunk meanwhile).  Its offers are dense and wave 0 waits for it:
       // scored as it is scanned.  The later chunks are sparse: filtered, then
       // scored (gather_small_sparse).
-      if (kSqFirst1 && c == 0) gather_small_scored<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, true, q);
-      else if constexpr (kSparseBranch) gather_small_sparse<T, kCtab>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, q, &br);
-      else gather_small_sparse<T, kCtab>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, q);
+      if (kSqFirst1 && c == 0) gather_small_scored<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, true);
+      else if constexpr (kSparseBranch) gather_small_sparse<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn, &br);
+      else gather_small_sparse<T>(cx, buf, nb, norm, bottom, i0, li0, gstop, qa, qp, cqn);
     }
     [[maybe_unused]] const uint64_t hs2 = CTCX_HTIME();
     if (lane == 0) {
@@ -3380,50 +3059,14 @@ __device__ CTCX_HELPER_FN void help_gather_scored(CTCX_HCTX cx, GQ q, int buf, i
 #ifndef CTCX_EXT_RANK
 #define CTCX_EXT_RANK 1
 #endif
-#ifndef CTCX_EXT_BIG
-#define CTCX_EXT_BIG 0
-#endif
 #ifndef CTCX_EXT_SLEEP
 #define CTCX_EXT_SLEEP 1
 #endif
 constexpr bool kExtRank = CTCX_EXT_RANK != 0;
-#ifndef CTCX_EXT_LATE
-#define CTCX_EXT_LATE 0
-#endif
-constexpr bool kExtLate = CTCX_EXT_LATE != 0;
-// CTCX_RANK_FAST: the helper ranks by ">" alone and finds ties by collision
-// (half the compares); CTCX_EXT_FIRST > 0: wave 0 reads the helper's stop
-// after its first CTCX_EXT_FIRST pops, not only after the first 32
-#ifndef CTCX_RANK_FAST
-#define CTCX_RANK_FAST 0
-#endif
-#ifndef CTCX_EXT_FIRST
-#define CTCX_EXT_FIRST 0
-#endif
-constexpr bool kRankFast = CTCX_RANK_FAST != 0;
-// CTCX_SET_MODE: a frame that follows a tie-free one (the helper's ranks of the
-// previous beam: no two equal totals) keeps its full beam as an unordered set in
-// registers instead of the libstdc++ heap.  Without ties the heap's layout
-// decides nothing: every eviction takes the unique minimum and the sorted
-// order is the ranks.  A push is then a register write and a DPP minimum, and
-// the extract is the helper's ranks.  A tie at an eviction, or in the final
-// beam, returns kReplay: the frame runs again on the heap.
-#ifndef CTCX_SET_MODE
-#define CTCX_SET_MODE 0
-#endif
-constexpr bool kSetMode = CTCX_SET_MODE != 0;
-constexpr int kReplay = 5;   // exact_step: decode the frame again with the heap
-constexpr int kTopSet = 3;   // the TopN state of the set mode (after kTopHeap in ctcx_topn.h's enum)
-#ifndef CTCX_SET_ASM
-#define CTCX_SET_ASM 1
-#endif
-constexpr bool kSetAsm = CTCX_SET_ASM != 0;   // the set mode's common events in set_events_f32
-constexpr int kExtFirst = CTCX_EXT_FIRST;   // (A/B: the helper ranks after its pending ring flush)
-constexpr bool kExtBig = CTCX_EXT_BIG != 0;   // large C too: off (cfg4 162.5 -> 169.6 ms, same box; cfg3 unmoved)
 constexpr int kCtlStop = 3, kCtlExt = 7;   // (misc words; both reset per frame)
 constexpr int kExtMinW = 16;               // beams below this pop too few positions to gain
 template <typename T>
-__device__ CTCX_HELPER_FN void help_rank_extract(CTCX_HCTX cx, CTCX_LDS int* scr, int tbuf = 0) {
+__device__ __forceinline__ void help_rank_extract(const Ctx<T>& cx, int tbuf = 0) {
   const int lane = threadIdx.x & 63;
   CTCX_LDS int* m = cx.misc;
   if (ctl_ld(m, kCtlDead) != 0) return;
@@ -3437,8 +3080,7 @@ __device__ CTCX_HELPER_FN void help_rank_extract(CTCX_HCTX cx, CTCX_LDS int* scr
     __builtin_amdgcn_s_sleep(CTCX_EXT_SLEEP);
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  const int ext = ctl_ld(m, kCtlExt);   // 1: wave 0 pops from the heap; 2: its set (kSetMode) waits for the ranks
-  if (kSetMode ? ext == 0 : ext != 1) return;
+  if (ctl_ld(m, kCtlExt) != 1) return;   // 1: wave 0 pops from the heap and reads the ranks' stop
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #ifdef CTCX_PHASE_EXTT
   const uint32_t hx0 = (uint32_t)__builtin_amdgcn_s_memtime();
@@ -3451,50 +3093,18 @@ __device__ CTCX_HELPER_FN void help_rank_extract(CTCX_HCTX cx, CTCX_LDS int* scr
   int g0 = 0, e0 = 0, g1 = 0, e1 = 0;
   const int W4 = (W + 3) >> 2;   // (wave 0 pads the copy to a multiple of 4 with NaN: never > or ==)
   int p = W;
-  if constexpr (kRankFast) {
-    // ranks by ">" alone (equal totals share a rank, distinct ones never do),
-    // the broadcast reads batched ahead of the compares
-#pragma unroll 8
-    for (int j = 0; j < W4; ++j) {
-      const u32x4 xq = ((const CTCX_LDS u32x4*)xv)[j];
-      const float x[4] = {__uint_as_float(xq.x), __uint_as_float(xq.y), __uint_as_float(xq.z), __uint_as_float(xq.w)};
+  for (int j = 0; j < W4; ++j) {
+    const u32x4 xq = ((const CTCX_LDS u32x4*)xv)[j];   // one address: a broadcast
+    const float x[4] = {__uint_as_float(xq.x), __uint_as_float(xq.y), __uint_as_float(xq.z), __uint_as_float(xq.w)};
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        g0 += x[u] > v0;
-        g1 += x[u] > v1;
-      }
-    }
-    if (__ballot((in0 && v0 != v0) || (in1 && v1 != v1))) {   // (no order to rank by)
-      if (kSetMode && ext == 2) __hip_atomic_store(&m[kCtlStop], -1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return;
-    }
-    // a tie is two entries of one rank: each entry writes its index at its
-    // rank in scr (the gather queue's score plane: free once the grow is
-    // over), and of two that collide at least one reads back the other's
-    if (in0) scr[g0] = lane;
-    if (in1) scr[g1] = lane + 64;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    e0 = (in0 && scr[g0] != lane) ? 2 : 1;
-    e1 = (in1 && scr[g1] != lane + 64) ? 2 : 1;
-  } else {
-    for (int j = 0; j < W4; ++j) {
-      const u32x4 xq = ((const CTCX_LDS u32x4*)xv)[j];   // one address: a broadcast
-      const float x[4] = {__uint_as_float(xq.x), __uint_as_float(xq.y), __uint_as_float(xq.z), __uint_as_float(xq.w)};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        g0 += x[u] > v0;
-        e0 += x[u] == v0;
-        g1 += x[u] > v1;
-        e1 += x[u] == v1;
-      }
-    }
-    if (__ballot((in0 && v0 != v0) || (in1 && v1 != v1))) {   // (no order to rank by)
-      if (kSetMode && ext == 2) __hip_atomic_store(&m[kCtlStop], -1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return;
+    for (int u = 0; u < 4; ++u) {
+      g0 += x[u] > v0;
+      e0 += x[u] == v0;
+      g1 += x[u] > v1;
+      e1 += x[u] == v1;
     }
   }
+  if (__ballot((in0 && v0 != v0) || (in1 && v1 != v1))) return;   // (no order to rank by)
   if (in0 && e0 > 1) p = g0 < p ? g0 : p;
   if (in1 && e1 > 1) p = g1 < p ? g1 : p;
   p = uni(wave_min(p));
@@ -3535,10 +3145,6 @@ __device__ CTCX_HELPER_FN void help_rank_extract(CTCX_HCTX cx, CTCX_LDS int* scr
     }
   }
 #endif
-  if (kSetMode && ext == 2 && p < W) {   // set mode with a tie: wave 0 replays the frame on the heap
-    __hip_atomic_store(&m[kCtlStop], -1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return;
-  }
   if (p <= 2) return;   // wave 0 pops every position anyway
   if (in0 && g0 < p) cx.sorted[g0] = cx.alias[lane];
   if (in1 && g1 < p) cx.sorted[g1] = cx.alias[lane + 64];
@@ -3551,7 +3157,7 @@ __device__ CTCX_HELPER_FN void help_rank_extract(CTCX_HCTX cx, CTCX_LDS int* scr
 }
 
 template <typename T>
-__device__ CTCX_HELPER_FN_GQ void help_gather_chunks(CTCX_HCTX_GQ cx, GQ q, int buf, int nb, T norm, T pmax, T bottom,
+__device__ __forceinline__ void help_gather_chunks(const Ctx<T>& cx, GQ q, int buf, int nb, T norm, T pmax, T bottom,
                                                    int lead) {
   const int lane = threadIdx.x & 63;
   CTCX_LDS int* m = cx.misc;
@@ -3595,99 +3201,16 @@ __device__ CTCX_HELPER_FN_GQ void help_gather_chunks(CTCX_HCTX_GQ cx, GQ q, int 
 
 // kEarlyChunk0: wave 0's roll and recursion over every branch of a full beam
 // (beams <= 128: branches lane and lane + 64), with no workgroup barrier.
-// CTCX_RECURSE_PAIR: the lane's two branches as one unrolled body -- every
-// read of both (frame-start arrays, the row) ahead of either's writes, so the
-// two chains of LDS reads, lse calls and candidate pushes overlap.  The roll
-// is folded in: recurse_branch overwrites the total, both endings and the
-// flags the roll would write, so the rolled label-ending total is read from
-// the frame-start array and the flags are the roll's 0.  Same arithmetic and
-// order per branch as recurse_branch(i, i, norm, false).  Bit-exact, measured
-// slower (cfg3 114.4 -> 116.3 ms per step, cfg2 41.9 -> 43.2, every pair, same
-// box; the kernel at 254 VGPRs instead of 252; profiles/r16_ab_cfg3.txt): off,
-// wave 0 keeps the loop over its two branches.
-#ifndef CTCX_RECURSE_PAIR
-#define CTCX_RECURSE_PAIR 0
-#endif
-constexpr bool kRecursePair = CTCX_RECURSE_PAIR != 0;
-template <typename T>
-struct RecNew {
-  T nbk, nl, tot, cb, cn;
-  uint32_t bpb, bpn;
-  int flg, lab;
-};
-template <typename T, class SC>
-__device__ __forceinline__ RecNew<T> recurse_rolled(const Ctx<T>& cx, int buf, int i, T norm) {
-  static_assert(!SC::kStateful, "base scorer");
-  const T NI = ninf<T>();
-  const int f = sel(cx.flg, buf)[i];
-  const int L = sel(cx.lab, buf)[i];
-  const bool isroot = (f & F_ROOT) != 0;
-  const T o_t = sel(cx.ot, buf)[i];
-  const bool fresh = (o_t == NI);
-  const T rs_blank = (isroot || ((f & F_PROOT) && fresh)) ? T(0) : NI;
-  T nl = sel(cx.ol, buf)[i];   // (the rolled newp.label)
-  Best<T> bn{T(0), kBpNone, false}, bb{T(0), kBpNone, false};
-  if (!isroot) {
-    const T xl = cx.row[L];
-    const T p = xl - norm;
-    const int P = sel(cx.par, buf)[i];
-    if (P >= 0) {
-      const bool same = (L == sel(cx.lab, buf)[P]);
-      const T prev = same ? sel(cx.ob, buf)[P] : sel(cx.ot, buf)[P];
-      nl = lse(nl, prev, cx.etab) + xl - norm;
-      cand_from(cx, buf, P, 0, p, rs_blank, bn);
-      if (!same) cand_from(cx, buf, P, 1, p, NI, bn);
-      cand_from(cx, buf, i, 1, p, NI, bn);
-    } else {
-      nl += xl - norm;
-      cand_from(cx, buf, i, 1, p, NI, bn);
-    }
-  }
-  const T xb = cx.row[cx.blank];
-  const T nbk = o_t + xb - norm;
-  const T pb = xb - norm;
-  cand_from(cx, buf, i, 0, pb, rs_blank, bb);
-  cand_from(cx, buf, i, 1, pb, NI, bb);
-  RecNew<T> r;
-  r.nbk = nbk; r.nl = nl; r.tot = lse(nbk, nl, cx.etab);
-  r.cb = bb.p; r.bpb = bb.bp; r.cn = bn.p; r.bpn = bn.bp;
-  r.flg = (bb.ok ? F_HB : 0) | (bn.ok ? F_HN : 0);
-  r.lab = L;
-  return r;
-}
-template <typename T>
-__device__ __forceinline__ void recurse_store(const Ctx<T>& cx, int e, const RecNew<T>& r) {
-  cx.eb[e] = r.nbk;
-  cx.el[e] = r.nl;
-  cx.et[e] = r.tot;
-  cx.ecb[e] = r.cb; cx.ebpb[e] = r.bpb;
-  cx.ecn[e] = r.cn; cx.ebpn[e] = r.bpn;
-  cx.eflg[e] = r.flg;
-  cx.ekind[e] = ((uint32_t)e << 1);
-  cx.elab[e] = r.lab;
-  cx.bst[e] = 0;
-  cx.bloom[e] = 0;
-}
 template <typename T, class SC>
 __device__ __forceinline__ void recurse_wave0(const Ctx<T>& cx, int buf, int nb, T norm) {
   const int lane = threadIdx.x & 63;
-  if constexpr (kRecursePair) {
-    // (nb >= W >= 1: a lane without a branch computes on branch 0 and stores nothing)
-    const int ia = lane, ib = lane + 64;
-    const bool va = ia < nb, vb = ib < nb;
-    const RecNew<T> ra = recurse_rolled<T, SC>(cx, buf, va ? ia : 0, norm);
-    const RecNew<T> rb = recurse_rolled<T, SC>(cx, buf, vb ? ib : 0, norm);
-    if (va) recurse_store<T>(cx, ia, ra);
-    if (vb) recurse_store<T>(cx, ib, rb);
-  } else {
-    for (int i = lane; i < nb; i += 64) {
-      cx.et[i] = sel(cx.ot, buf)[i]; cx.eb[i] = sel(cx.ob, buf)[i]; cx.el[i] = sel(cx.ol, buf)[i];
-      cx.eflg[i] = 0;
-      cx.bst[i] = 0;
-      cx.bloom[i] = 0;
-    }
-    for (int i = lane; i < nb; i += 64) recurse_branch<T, SC>(cx, buf, i, i, norm, false);
+  for (int i = lane; i < nb; i += 64) {
+    cx.et[i] = sel(cx.ot, buf)[i]; cx.eb[i] = sel(cx.ob, buf)[i]; cx.el[i] = sel(cx.ol, buf)[i];
+    cx.eflg[i] = 0;
+    cx.bst[i] = 0;
+    cx.bloom[i] = 0;
   }
+  for (int i = lane; i < nb; i += 64) recurse_branch<T, SC>(cx, buf, i, i, norm, false);
   wsync<true>();   // (one wave: its LDS operations execute in order)
 }
 
@@ -3696,8 +3219,9 @@ __device__ __forceinline__ void recurse_wave0(const Ctx<T>& cx, int buf, int nb,
 // and after the row prefetch, in a frame whose final heap wave 0 published
 // (kCtlExt == 1: xv[j], alias[j] for j < W): row (frame t + 1's, in the second
 // row buffer) and norm are the helper's own prefetch.  For entry j at slot
-// e = alias[j] it computes what recurse_rolled(i = the position the commit
-// gives j) computes next frame, from what the commit will put there:
+// e = alias[j] it computes what the roll and recurse_branch(i, i, norm, false)
+// compute next frame for i = the position the commit gives j, from what the
+// commit will put there:
 //   own words            et/eb/el/ecb/ecn/eflg/elab[e]      (put_branch)
 //   flags, parent entry  as parent_of forms them, by slot: a new child's parent
 //     is its source branch, a survivor's the branch par[buf][src], both present
@@ -3705,12 +3229,12 @@ __device__ __forceinline__ void recurse_wave0(const Ctx<T>& cx, int buf, int nb,
 //     survivor whose parent had left the beam finds it among the final beam's
 //     new children by prefix hash (the commit's re-entered parent)
 //   the parent's words   its entry's, eb/et/ecb/ecn/eflg/elab[alias[pj]]
-// Same expressions in the same order as recurse_rolled; back-pointers are
+// Same expressions in the same order as recurse_branch; back-pointers are
 // staged as (j << 1) | kind and translated to positions by the commit.
 // Reads only what stays as it is from the grow's end to the commit; writes
 // the staging planes and the two maps in the gather queue's offer plane.
 template <typename T, int WC>
-__device__ CTCX_HELPER_FN void help_early_recurse(CTCX_HCTX cx, int buf, const CTCX_LDS T* row, T norm,
+__device__ __forceinline__ void help_early_recurse(const Ctx<T>& cx, int buf, const CTCX_LDS T* row, T norm,
                                                   CTCX_LDS int* sp, CTCX_LDS int* maps) {
   const int lane = threadIdx.x & 63;
   const int W = cx.W;
@@ -3792,7 +3316,7 @@ __device__ CTCX_HELPER_FN void help_early_recurse(CTCX_HCTX cx, int buf, const C
       if (lane == l) pjs[h] = found;
     }
   }
-  // the recursion (recurse_rolled's expressions, sources by slot)
+  // the recursion (recurse_branch's expressions after the roll, sources by slot)
   const T xb = row[cx.blank];
   const T pbk = xb - norm;
 #pragma unroll 1
@@ -3955,7 +3479,7 @@ __shared__ int g_sq_dbg[8];   // (diagnostics: the first scored-field mismatch)
 #endif
 template <typename T, int RN, bool BIG, class SC, bool HW, bool SQ>
 __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, bool last, int P, int* n_out,
-                          int* n_leaves, PhaseCtr pc, Tab tb, GQ gq, bool setm_in = false, bool er_hit = false) {
+                          int* n_leaves, PhaseCtr pc, Tab tb, GQ gq, bool er_hit = false) {
   // SQ: the scored gather queue (two-wave kernels, beams <= 128, any C): with
   // the beam full, every chunk of the grow comes from the helper scored
   static_assert(!SQ || (HW && (RN == 1 || (RN == 2 && BIG))), "SQ kernels");
@@ -4022,29 +3546,10 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   if (kEc0 && early) {
     if constexpr (kEc0) {
       if (helper_wave()) {
-        if constexpr (kEarlyBottom > 0) {
-          // (er_hit: the placed totals are this frame's leaves, so their
-          // minimum is the starting bottom wave 0 will publish; a total that
-          // is not finite sends wave 0 to the literal path, and kCtlDone ends
-          // the gather.  Form 1: chunk 0 from -inf as before, chunk 1 without
-          // the wait; form 2: chunk 0 from the bottom as well.)
-          T b0 = NI;
-          if (er_hit) {
-            T lm = pinf<T>();
-            for (int i = lane; i < nb; i += 64) {
-              const T v = cx.et[i];
-              lm = v < lm ? v : lm;
-            }
-            lm = wave_min(lm);
-            b0 = (lm > NI && lm < pinf<T>()) ? lm : NI;
-          }
-          help_gather_scored<T, BIG, true, true>(cx, gq, buf, nb, norm, pmax, kEarlyBottom == 2 ? b0 : NI, b0);
-        } else {
-          help_gather_scored<T, BIG, true>(cx, gq, buf, nb, norm, pmax, NI);
-        }
-        if constexpr (kExtRank && !kExtLate) {
+        help_gather_scored<T, BIG, true>(cx, gq, buf, nb, norm, pmax, NI);
+        if constexpr (kExtRank) {
           [[maybe_unused]] const uint64_t hr0 = CTCX_HTIME();
-          help_rank_extract<T>(cx, (CTCX_LDS int*)gq.p, buf);
+          help_rank_extract<T>(cx, buf);
           CTCX_HPC(cx, 28, CTCX_HTIME() - hr0);
         }
         return 0;   // the kernel takes wave 0's result
@@ -4082,9 +3587,9 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
         // shorter and cfg3 1.5% slower, 116.1 against 114.4 ms per step --
         // placement; profiles/r16_ab_prefetch_cfg3.txt.  It stays.)
         if (nb >= W) help_gather_scored<T, BIG>(cx, gq, buf, nb, norm, pmax, wave_min(lmin));
-        if constexpr (RN == 1 && kExtRank && (kExtBig || !BIG) && !kExtLate) {
+        if constexpr (RN == 1 && kExtRank && !BIG) {
           [[maybe_unused]] const uint64_t hr0 = CTCX_HTIME();
-          help_rank_extract<T>(cx, (CTCX_LDS int*)gq.p, buf);
+          help_rank_extract<T>(cx, buf);
           CTCX_HPC(cx, 28, CTCX_HTIME() - hr0);
         }
       } else if constexpr (BIG) {
@@ -4129,13 +3634,6 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
                            __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   T bottom = full ? front.v : NI;
-  // the set mode (kSetMode): kernels with the helper's ranks, float beams <= 128
-  constexpr bool kSetK = kSetMode && HW && SQ && RN == 1 && !BIG && sizeof(T) == 4 && !SC::kStateful &&
-                         kExtRank && !kExtLate;
-  const bool setm = kSetK && setm_in && !last && full && W >= kExtMinW && W <= 128;
-  float sv0 = __builtin_inff(), sv1 = __builtin_inff();
-  int ss0 = -1, ss1 = -1, floc = 0;
-  bool ftied = false;
 
   // grow (decoder.h:146-209): offers in (branch order, label order), 64 per
   // chunk.  Within a chunk the entry writes, the resets of evicted branch
@@ -4186,7 +3684,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   // records and published bottoms as that path, chunk for chunk; the bounded
   // wait, a dead helper and the re-offers of branch children are its code.
   constexpr bool kSqHeapM = SQ && HW && !BIG && RN == 1 && sizeof(T) == 4;
-  constexpr bool kSqLoop = kSqHeapM && !SC::kStateful && !kSetK && !kBatLazy;
+  constexpr bool kSqLoop = kSqHeapM && !SC::kStateful;
   while (i0 < nb && !stop) {
     if constexpr (kSqLoop) {
       if (full && st == kTopHeap && W >= 2) {
@@ -4211,7 +3709,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
             int rdy = __hip_atomic_load(&cx.misc[kCtlReady], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __asm__ volatile("" ::: "memory");
             read_slot();
-            CTCX_ONE_TRIP(rdy, "v"(h0), "v"(h3), "v"(gqa), "v"(gqv));
+            __asm__ volatile("" ::"v"(h0), "v"(h3), "v"(gqa), "v"(gqv));
             if (__builtin_expect(uni(rdy) <= gqc && !cx.tabdead, 0)) {
               // the helper is behind: the bounded wait of the generic path (a
               // wait that runs out, or a helper that gave up, ends the grow)
@@ -4471,7 +3969,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
             // the slot reads complete with the count (one round trip): otherwise
             // the compiler sinks them below the test, or hoists the count's
             // readfirstlane above them -- a second round trip either way
-            CTCX_ONE_TRIP(rdy, "v"(ta[0]), "v"(ta[1]), "v"(tpv[0]), "v"(tpv[1]));
+            __asm__ volatile("" ::"v"(ta[0]), "v"(ta[1]), "v"(tpv[0]), "v"(tpv[1]));
             if (__builtin_expect(uni(rdy) < need, 0)) {
               // wave 1 is behind (rare): wait for the count, then read again.
               // A wait that runs out of time, or a helper that gave up, ends
@@ -4804,9 +4302,9 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
           __asm__ volatile("" ::: "memory");
           read_slot();
           if constexpr (SQ)
-            CTCX_ONE_TRIP(rdy, "v"(h0), "v"(h1), "v"(h2), "v"(h3), "v"(gqa), "v"(gqv), "v"(gqp));   // one round trip
+            __asm__ volatile("" ::"v"(h0), "v"(h1), "v"(h2), "v"(h3), "v"(gqa), "v"(gqv), "v"(gqp));   // one round trip
           else
-            CTCX_ONE_TRIP(rdy, "v"(h0), "v"(h1), "v"(h2), "v"(h3), "v"(gqe), "v"(gqp));
+            __asm__ volatile("" ::"v"(h0), "v"(h1), "v"(h2), "v"(h3), "v"(gqe), "v"(gqp));
           if (__builtin_expect(uni(rdy) <= gqc && !cx.tabdead, 0)) {
             // wave 1 is behind: wait for the count, then read again (a wait that
             // runs out of time, or a helper that gave up, takes cqn = 0 below:
@@ -4897,8 +4395,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
         T s2, bt2;
         int c2;
         Best<T> cd2;
-        sq_score<T, SQ && !BIG && kCtab, BIG && kCHash && RN <= 2>(cx, buf, norm, valid, i, l, s2, bt2, c2, cd2,
-                                                                   gq.cmask, gq.ctab);
+        sq_score<T>(cx, buf, norm, valid, i, l, s2, bt2, c2, cd2);
         const int fmask = (__builtin_bit_cast(unsigned, (float)s2) != __builtin_bit_cast(unsigned, (float)s) ? 1 : 0) |
                           (__builtin_bit_cast(unsigned, (float)bt2) != __builtin_bit_cast(unsigned, (float)bt) ? 2 : 0) |
                           (c2 != c ? 4 : 0) |
@@ -4998,9 +4495,6 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
       // the branch child this offer re-offers, if any (GetChild finds it): walk
       // branch i's children, each step one read pair (label, next sibling)
       c = -1;
-      if constexpr (BIG && kCHash && RN <= 2) {   // large C: the child hash (kCHash)
-        c = chash_find(cx, live, i, l);
-      } else
       for (int k = live ? hd : -1; __ballot(k >= 0);) {
         int nk = -1;
         if (k >= 0) {
@@ -5041,106 +4535,6 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
     int nev = 0;
     uint64_t done = 0;
     while (true) {
-      if (kSetK && st == kTopSet) {
-        // the set mode's events: the selections and bookkeeping of
-        // heap_events_f32 and its caller's re-offer path, the push a register
-        // write and the new front a DPP minimum
-        const uint64_t liveM = __ballot(live);
-        uint64_t NC = liveM & ~isbm, LB = liveM & isbm, RB = LB & __ballot(cev);
-        float fv = (float)front.v;
-        int fs = front.s;
-        int nfree = nextfree;
-        int nv = uni(nev);
-        bool tie_ev = false;
-#ifdef CTCX_PHASE_SET
-        const uint64_t tsl0 = pc ? __builtin_amdgcn_s_memtime() : 0;
-        int npush = 0;
-#endif
-        int ftied_i = ftied ? 1 : 0;
-        for (;;) {
-          fv = uni(fv); fs = uni(fs); nfree = uni(nfree); nv = uni(nv);
-          if constexpr (kSetK && kSetAsm) {
-            int ka, cnt = 0;
-            int fl = floc;
-            const int est = set_events_f32((float)s, c, sl, sv0, ss0, sv1, ss1, myslot, evr, bat, NC, RB, done, LB,
-                                           fv, fs, fl, ftied_i, nfree, nv, uni(nb), ka, cnt);
-            floc = uni(fl);
-#ifdef CTCX_PHASE_SET
-            npush += uni(cnt);
-#endif
-            if (est == 0) break;
-            if (est == 2) { tie_ev = true; break; }
-            ftied = ftied_i != 0;
-          }
-          const uint64_t gtM = __ballot(s > fv);
-          const uint64_t m = ((gtM & NC) | RB) & ~done;
-          if (m == 0) break;
-          const int k = (int)__builtin_ctzll(m);
-          int slot;
-          if ((kSetK && kSetAsm) || ((LB >> k) & 1ull)) {
-            // a re-offered branch child: was k's turn skipped?
-            if ((__ballot(!(bt > bat)) >> k) & 1ull) {
-              const uint64_t keepM = lowmask(bcast(sl, k));   // that branch and every later one
-              NC &= keepM; LB &= keepM; RB &= keepM;
-              stop = true;
-              continue;
-            }
-            done = m ^ (m - 1ull);
-            const int kc = bcast(c, k);
-            if (!((gtM >> k) & 1ull)) {
-              // re-offered evicted branch rejected -> deactivated (decoder.h:200-205)
-              evr = writelane(evr, kc | kDeactRec, nv);
-              dz = true;
-              nv += 1;
-              const uint64_t dm = ~__ballot(i == kc);
-              NC &= dm; LB &= dm; RB &= dm;
-              continue;
-            }
-            if (ftied) { tie_ev = true; break; }
-            if (fs < nb) {   // accepted: the branch's entry keeps its slot
-              evr = writelane(evr, fs, nv);
-              nv += 1;
-              RB |= LB & __ballot(c == fs);
-            }
-            slot = kc;
-          } else {
-            done = m ^ (m - 1ull);
-            if (ftied) { tie_ev = true; break; }
-            slot = fs;
-            if (fs < nb) {   // the evicted front is a branch's entry: a fresh slot
-              slot = nfree;
-              nfree += 1;
-              evr = writelane(evr, fs, nv);
-              nv += 1;
-              RB |= LB & __ballot(c == fs);
-            }
-          }
-          slot = uni(slot);
-          const float k_s = bcast((float)s, k);
-          myslot = (myslot == fs) ? -1 : myslot;
-          myslot = (lane == k) ? slot : myslot;
-          set_put(sv0, ss0, sv1, ss1, floc, k_s, slot);
-          set_front(sv0, ss0, sv1, ss1, fv, fs, floc, ftied);
-          ftied_i = ftied ? 1 : 0;
-          bat = (sl > k) ? (T)fv : bat;
-#ifdef CTCX_PHASES
-          if (pc) pc[6] += 1;
-#endif
-#ifdef CTCX_PHASE_SET
-          ++npush;
-#endif
-        }
-#ifdef CTCX_PHASE_SET
-        if (pc) { pc[23] += __builtin_amdgcn_s_memtime() - tsl0; pc[18] += npush; }
-#endif
-        if (tie_ev) return kReplay;   // an eviction among equal minima: the heap decides
-        nev = nv;
-        front.v = (T)fv;
-        front.s = fs;
-        bottom = front.v;
-        nextfree = nfree;
-        break;
-      }
       if ((RN == 1 || RN == 2) && st == kTopHeap && W >= 2) {
         // HEAP_SORTED, beams up to 128 (the mask form of the loop below, same
         // decisions): new-child lanes wanting in (NC: live, not a branch) are
@@ -5165,47 +4559,30 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
           const unsigned heb = (unsigned)(uintptr_t)he;   // LDS byte address of he[0]
           const unsigned aj = heb + 8u * (unsigned)(lane + 1), al = heb + 8u * (unsigned)(2 * lane + 2);
           const unsigned ar = al + 8u, dum = heb + 8u * (unsigned)(cx.hdum + lane);
-          // kBatLazy: the front after each push of this path in lane k of fa
-          // (NaN: no push); lane j's bat is then fa at the last push before its
-          // turn start, else bat as this path found it (bat_of)
-          float fa = __builtin_nanf("");
-          auto bat_of = [&](int j) -> float {   // (j uniform)
-            const int sj = bcast(sl, j);
-            const uint64_t pm = sj > 0 ? __ballot(fa == fa) & lowmask(sj) : 0ull;
-            return pm ? bcast(fa, 63 - __builtin_clzll(pm)) : bcast((float)bat, j);
-          };
           for (;;) {
             int k;
             fv = uni(fv); fs = uni(fs); nfree = uni(nfree); nv = uni(nv);
             int nev_asm = 0;
             const uint64_t ta = pc ? __builtin_amdgcn_s_memtime() : 0;
             int est;
-            float& bref = kBatLazy ? fa : bat;
             if constexpr (RN == 1) {
-              est = heap_events_f32(s, c, sl, geo.anc, geo.req, aj, al, ar, dum, myslot, evr, bref, NC, RB, done, LB,
+              est = heap_events_f32(s, c, sl, geo.anc, geo.req, aj, al, ar, dum, myslot, evr, bat, NC, RB, done, LB,
                                     fv, fs, nfree, nv, uni(nb), k, nev_asm);
             } else {
               est = heap_events_m2_f32(s, c, sl, geo.g.anc, geo.g.req, (unsigned)geo.anc1, (unsigned)(geo.anc1 >> 32),
                                        (unsigned)geo.req1, (unsigned)(geo.req1 >> 32), aj, al, ar, aj + 512u,
-                                       al + 1024u, ar + 1024u, dum, myslot, evr, bref, NC, RB, done, LB, fv, fs,
+                                       al + 1024u, ar + 1024u, dum, myslot, evr, bat, NC, RB, done, LB, fv, fs,
                                        nfree, nv, nb, k, nev_asm);
             }
             if (pc) { pc[13] += __builtin_amdgcn_s_memtime() - ta; pc[6] += uni(nev_asm); pc[12] += 1; }
-            if (est == 0) {
-              if constexpr (kBatLazy) {   // the chunk-end turn check reads one lane's bat
-                const int j = (BIG || SQ) ? cqn - 1 : 63;
-                const float bj = bat_of(j);
-                bat = (lane == j) ? bj : bat;
-              }
-              break;
-            }
+            if (est == 0) break;
             k = uni(k);
             // lane k re-offers a branch child.  Only a re-offer can make a closed
             // turn visible (a closed branch's new children score <= its total <=
             // bottom): was k's turn skipped?
             const uint64_t gtM = __ballot(s > fv);
             const uint64_t m = ((gtM & NC) | RB) & ~done;   // its lowest lane is k
-            if (kBatLazy ? !(bcast(bt, k) > bat_of(k)) : ((__ballot(!(bt > bat)) >> k) & 1ull)) {
+            if ((__ballot(!(bt > bat)) >> k) & 1ull) {
               const uint64_t keepM = lowmask(bcast(sl, k));   // that branch and every later one
               NC &= keepM; LB &= keepM; RB &= keepM;
               stop = true;
@@ -5239,8 +4616,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
             mpush<T, RN>(he, geo, k_s, kc, pp, c0, s0, keep);
             fv = keep ? k_s : c0;
             fs = keep ? kc : s0;
-            if constexpr (kBatLazy) fa = writelane(fa, uni(fv), k);
-            else bat = (sl > k) ? fv : bat;
+            bat = (sl > k) ? fv : bat;
           }
         } else {
           for (;;) {
@@ -5429,17 +4805,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
           if (full && lane == 0) he[1].v = NI;
           if (lane == 0) he_st(he, n + 1, nv);
           ++n;
-          if (kSetK && setm && n == W + 1) {
-            // the set: positions 2..W+1 (the front at 1 was evicted)
-            if (lane < W) { sv0 = (float)he[lane + 2].v; ss0 = he[lane + 2].s; }
-            if (lane + 64 < W) { sv1 = (float)he[lane + 66].v; ss1 = he[lane + 66].s; }
-            float fv0;
-            int fs0;
-            set_front(sv0, ss0, sv1, ss1, fv0, fs0, floc, ftied);
-            front.v = (T)fv0;
-            front.s = fs0;
-            st = kTopSet;
-          } else if (n == W + 1) {
+          if (n == W + 1) {
 #ifdef CTCX_FASTLOOP_PROF
             const uint64_t q4 = __builtin_amdgcn_s_memtime();
 #endif
@@ -5512,20 +4878,8 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
 
   // the extract's rank placement on the helper (help_rank_extract): the final
   // heap's copy, then kCtlExt, both ahead of kCtlDone
-  constexpr bool kExt = HW && SQ && RN == 1 && kExtRank && (kExtBig || !BIG);
+  constexpr bool kExt = HW && SQ && RN == 1 && kExtRank && !BIG;
   const bool ext_rank = kExt && st == kTopHeap && W >= kExtMinW;
-  if constexpr (kSetK) {
-    if (st == kTopSet) {   // the set's copy; kCtlExt 2: the helper publishes its ranks' verdict
-      CTCX_LDS float* xv = (CTCX_LDS float*)cx.newpos;
-      const int W4 = (W + 3) & ~3;
-      if (lane < W) { xv[lane] = sv0; cx.alias[lane] = ss0; }
-      else if (lane < W4) xv[lane] = __builtin_nanf("");
-      if (lane + 64 < W) { xv[lane + 64] = sv1; cx.alias[lane + 64] = ss1; }
-      else if (lane + 64 < W4) xv[lane + 64] = __builtin_nanf("");
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      if (lane == 0) __hip_atomic_store(&cx.misc[kCtlExt], 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  }
   if constexpr (kExt) {
     if (ext_rank) {
       CTCX_LDS float* xv = (CTCX_LDS float*)cx.newpos;
@@ -5590,24 +4944,7 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
   }
   // Extract() of the next frame (decoder.h:84): sort_heap, or std::sort
   int nout;
-  if (kSetK && st == kTopSet) {
-    // the set mode: the helper's ranks place every position, unless two
-    // totals tie (-1: the heap's pops decide their order -- replay)
-    int p = 0;
-    uint64_t tw = 0;
-    for (int spin = 0;; ++spin) {
-      p = uni(__hip_atomic_load(&cx.misc[kCtlStop], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if (p != 0) break;
-      if (ctl_ld(cx.misc, kCtlDead) != 0 || wait_expired(spin, tw)) {   // never in a correct run
-        cx.tabdead = 1;
-        __hip_atomic_store(&cx.misc[kCtlDead], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return 1;   // the literal path decodes this frame
-      }
-      __builtin_amdgcn_s_sleep(CTCX_EXT_SLEEP);
-    }
-    if (p != W) return kReplay;
-    nout = W;
-  } else if (RN == 1 && st == kTopHeap && W >= 2) {
+  if (RN == 1 && st == kTopHeap && W >= 2) {
     // sort_heap in mask form (beams up to 128).  pop_heap(len) parks the old
     // front at position len - 1, which no later sift reads: the slot goes
     // straight into a register lane (position p: lane p of srt[p >> 6])
@@ -5630,11 +4967,10 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
 #ifdef CTCX_PHASE_EXTT
       if (lane == 0) cx.misc[14] = (int)(uint32_t)__builtin_amdgcn_s_memtime();
 #endif
-      int cur = W;   // the next position to pop, plus one
+      const int cur = W;   // the first position to pop, plus one (a copy: with W read inside seg part 11's code moves)
       auto seg = [&](int top, int lo, int base, int& srt) {
         const int hi = cur < top ? cur : top;
         const int l = lo > stop ? lo : stop;
-        if constexpr (kExtFirst > 0) cur = hi > l ? l : cur;   // (the segments run in order, contiguous)
 #ifdef CTCX_PHASE_EXTT
         const uint64_t sx0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -5654,14 +4990,6 @@ __device__ __forceinline__ int exact_step(Ctx<T>& cx, int buf, int nb, T norm, b
       };
       // (polls every 16 or 8 pops measured slower: cfg3 +0.4% / +1.2%,
       // profiles/r6i_ab_ext_seg.txt -- the helper's stop rarely lands early)
-      if constexpr (kExtFirst > 0) {
-        if (ext_rank) {   // the first kExtFirst pops, then a poll (uniform)
-          const int f1 = W - kExtFirst > 2 ? W - kExtFirst : 2;
-          seg(128, f1 > 64 ? f1 : 64, 64, srt1);
-          seg(64, f1, 0, srt0);
-          poll();
-        }
-      }
       seg(128, 96, 64, srt1);
       poll();
       seg(96, 64, 64, srt1);
@@ -6423,11 +5751,6 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
       constexpr int kSlots = SQ ? sq_slots(WC) : kQSlots;
       gq = gq_carve<SQ>((CTCX_LDS char*)lds + off, kSlots);
       off += gq_lds_bytes(SQ, kSlots);
-      if constexpr (SQ && !BIG && kCtab) {
-        gq.cmask = (CTCX_LDS uint64_t*)((CTCX_LDS char*)lds + off);
-        gq.ctab = (CTCX_LDS uint8_t*)((CTCX_LDS char*)lds + off + (size_t)WC * 8);
-        off += sq_ctab_bytes(WC, 0);
-      }
       if constexpr (kPf) {   // the second row buffer and its words (sq_rowpf_bytes)
         row2 = (CTCX_LDS T*)((CTCX_LDS char*)lds + off);
         pfw = (CTCX_LDS int*)((CTCX_LDS char*)lds + off + sq_rowpf_bytes(C) - 16);
@@ -6514,14 +5837,9 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     cx.cb[0][0] = T(0); cx.cn[0][0] = T(0);
     cx.ha[0][0] = kRootHa; cx.hb[0][0] = kRootHb;
     cx.head[0] = -1;
-    if constexpr (SQ && !BIG && kCtab) gq.cmask[0] = 0ull;
     cx.alias[0] = 0;
     if constexpr (SC::kStateful) cx.est[0][0] = T(0);   // InitializeState (decoder.h:226)
   }
-#ifndef CTCX_GSTATE
-  if constexpr (BIG && kCHash && RN <= 2)   // the child hash starts empty (the root has no children)
-    for (int q = tid; q < cx.hts; q += NT) cx.htab[q] = -1;
-#endif
   if constexpr (BIG) {   // the child bitmap and window summary start (and stay, between branches) clear
     const int nw = (C - 1 + 63) / 64;
     CTCX_LDS uint64_t* z = row_cbm(cx);
@@ -6533,7 +5851,6 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
   int nb = 1;
   int literal_steps = 0;
   int why_nf = 0, why_fill = 0, dup_frames = 0;
-  bool tiefree = false;  // the previous frame's beam had no tie (kSetMode)
   bool dup = false;   // this frame's beam holds an entry twice (literal frames only)
   int n_leaves = 1;
   // kEarlyRecurse: this frame's recursion is in place already (the last commit
@@ -6541,9 +5858,12 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
   [[maybe_unused]] bool er_hit = false;
   [[maybe_unused]] int early_rec = 0;
 #ifdef CTCX_STREAM
+  // (the header's reserved word, 0 in every image, goes from push to push as
+  // the flag it once was: the stream builds' code stays what it was)
+  bool reserved0 = false;
   if (resume) {   // the scalars a frame hands to the next, and the item's counters so far
     if constexpr (kEr) early_rec = uni(hin.pad[0]);
-    buf = uni(hin.buf); nb = uni(hin.nb); dup = uni(hin.dup) != 0; tiefree = uni(hin.tiefree) != 0;
+    buf = uni(hin.buf); nb = uni(hin.nb); dup = uni(hin.dup) != 0; reserved0 = uni(hin.reserved0) != 0;
     n_leaves = uni(hin.n_leaves); literal_steps = uni(hin.literal_steps); dup_frames = uni(hin.dup_frames);
     why_nf = uni(hin.why_nonfinite); why_fill = uni(hin.why_fill); nrec_all = (int64_t)uni64((uint64_t)hin.records);
   }
@@ -6655,14 +5975,10 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     int nl_fast = 0;
     uint64_t t1 = prof ? __builtin_amdgcn_s_memtime() : 0;
     if (prof) pc[0] += t1 - t0;
-    bool again = false;
-    int pass = 0;
-    [[maybe_unused]] const bool set_try = tiefree;
-    do {
 #ifndef CTCX_GSTATE   // the global-state tier replays every frame literally
     if (!prm.force_literal && !dup)
       why = exact_step<T, RN, BIG, SC, HW, SQ>(cx, buf, nb, norm, last, prm.P, &n, &nl_fast, prof ? pc : PhaseCtr{nullptr}, tb, gq,
-                                               pass == 0 && tiefree, kEr && er_hit);
+                                               kEr && er_hit);
 #endif
     if constexpr (HW) {
       // wave 0's result for both waves; the helper stops if the grow ended
@@ -6714,32 +6030,12 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
         }
       }
 #endif
-      if constexpr (SQ && RN == 1 && kExtRank && (kExtBig || !BIG) && kExtLate)
-        if (helper_wave()) help_rank_extract<T>(cx, (CTCX_LDS int*)gq.p);
       pf_t = -1;
       __syncthreads();
       why = uni(cx.misc[4]);
       n = uni(cx.misc[5]);
       nl_fast = uni(cx.misc[6]);
     }
-    // a set-mode frame that met a tie (kReplay): both waves decode it again on
-    // the heap, from the frame's start (the roll restores every branch entry)
-    again = kSetMode && HW && why == kReplay;
-    if (again) {
-      if (tid < 3) cx.misc[kCtlReady + tid] = 0;
-      if (tid == 3) cx.misc[kCtlBot] = (int)0xff800000u;   // -inf
-      if (tid == 4) cx.misc[kCtlExt] = 0;
-      if (tid == 5) cx.misc[kCtlStop] = 0;
-      __syncthreads();
-      ++pass;
-    }
-    } while (again);
-    // the next frame may keep a set if this one's beam has no tie (the
-    // helper's ranks: kCtlStop == W)
-    if constexpr (kSetMode && HW) tiefree = uni(cx.misc[kCtlStop]) == cx.W;
-#ifdef CTCX_PHASE_SET   // (diagnostics: frames tried in the set mode, and replayed)
-    if (prof) { pc[16] += set_try ? 1 : 0; pc[17] += pass; }
-#endif
     __syncthreads();
     uint64_t t2 = prof ? __builtin_amdgcn_s_memtime() : 0;
     const bool ok = (why == 0);
@@ -6930,7 +6226,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     }
     if (R > 0 && tid == 0) rg.rn[t & (R - 1)] = n;
     __syncthreads();
-    // kEarlyRecurse: the staged recursion into place, as recurse_store would
+    // kEarlyRecurse: the staged recursion into place, as recurse_wave0 would
     // leave entry k next frame.  Every read of e*[sorted[.]] above is behind
     // the barrier; nothing below reads an e* array, bst or bloom.  The two
     // back-pointers name entries by j: through the position map.
@@ -6959,36 +6255,12 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
     buf = nx;
     nb = n;
     dup = dup_next;
-    constexpr bool kCT = SQ && !BIG && kCtab;   // the scored queue's children table (sq_score)
-    constexpr bool kCH = BIG && kCHash && RN <= 2;   // the child hash (chash_find), in htab's room
-    for (int k = tid; k < nb; k += NT) {
-      cx.head[k] = -1;
-      if constexpr (kCT) gq.cmask[k] = 0ull;
-    }
-    if constexpr (kCH)   // (the commit's parent links are done: its prefix-hash entries are dead)
-      for (int q = tid; q < cx.hts; q += NT) cx.htab[q] = -1;
+    for (int k = tid; k < nb; k += NT) cx.head[k] = -1;
     __syncthreads();
     for (int k = tid; k < nb; k += NT) {
       const int pp = sel(cx.par, buf)[k];
-      if (pp >= 0 && (!dup || cx.alias[k] == k)) {
+      if (pp >= 0 && (!dup || cx.alias[k] == k))
         cx.sib[k] = __hip_atomic_exchange(&cx.head[pp], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if constexpr (kCT) {   // (a parent's children have distinct labels)
-          const int lk = sel(cx.lab, buf)[k];
-          __hip_atomic_fetch_or(&gq.cmask[pp], 1ull << (lk & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          gq.ctab[pp * 64 + lk] = (uint8_t)k;
-        }
-        if constexpr (kCH) {   // (parent, label) -> k: parent < 256, label < 65535, k < 256
-          const uint32_t key = ((uint32_t)pp << 16) | (uint32_t)sel(cx.lab, buf)[k];
-          const int w = (int)((key << 8) | (uint32_t)k);
-          int q = chash_slot(key, cx.hts);
-          int expect = -1;
-          while (!__hip_atomic_compare_exchange_strong(&cx.htab[q], &expect, w, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_WORKGROUP)) {
-            q = (q + 1) & (cx.hts - 1);
-            expect = -1;
-          }
-        }
-      }
     }
     if (R == 0) nrec_all += n;
     else if (t - flushed + 1 == R) {   // the ring is full: write its older half
@@ -7062,7 +6334,7 @@ __global__ __launch_bounds__(HW ? 128 : 64) void ctcx_beam_decode(DecodeParams<T
   if (tid == 0) {
     CtcxStreamHdr ho{};
     ho.frames = t0g + sl;
-    ho.buf = buf; ho.nb = nb; ho.dup = dup ? 1 : 0; ho.tiefree = tiefree ? 1 : 0;
+    ho.buf = buf; ho.nb = nb; ho.dup = dup ? 1 : 0; ho.reserved0 = reserved0 ? 1 : 0;
     ho.n_leaves = n_leaves; ho.literal_steps = literal_steps; ho.dup_frames = dup_frames;
     ho.why_nonfinite = why_nf; ho.why_fill = why_fill; ho.records = nrec_all;
     if constexpr (kEr) ho.pad[0] = early_rec;
@@ -7641,14 +6913,6 @@ __global__ __launch_bounds__(64) void ctcx_row_prep(const E* __restrict__ x, con
 #define CTCX_FACTS_COMPACT 768
 #endif
 constexpr int kFactsCompact = CTCX_FACTS_COMPACT;
-#ifndef CTCX_FACTS_INTERP
-#define CTCX_FACTS_INTERP 0
-#endif
-constexpr bool kFactsInterp = CTCX_FACTS_INTERP != 0;   // the top set's threshold by interpolation search
-#ifndef CTCX_FACTS_BALLOT
-#define CTCX_FACTS_BALLOT 0
-#endif
-constexpr bool kFactsBallot = CTCX_FACTS_BALLOT != 0;   // the threshold search's counts by ballot popcounts
 // The (rank)-th largest of the n keys of a wave's compact list (rank <= n):
 // MSB-first radix select, 8-bit digits, a 256-bin LDS histogram per pass.
 // Every key lies in [klo, khi], so the bits above their highest differing bit
@@ -7950,55 +7214,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CTCX_FACTS_
       // list, its outside maximum taken from the registers), or a list past its
       // capacity (tau bisected over the row's keys, S from the registers)
       auto cnt_ge = [&](unsigned tau) __attribute__((always_inline)) {
-        if constexpr (kFactsBallot) {
-          // one compare per key on the vector unit, the counting on the scalar
-          // unit (a ballot's popcount per key): the kernel is VALU issue-bound
-          int c2 = 0;
+        int c2 = 0;
 #pragma unroll
-          for (int u = 0; u < NV; ++u)
+        for (int u = 0; u < NV; ++u)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) c2 += __builtin_popcountll(__ballot(k[u][c] >= tau));
-          return c2;
-        } else {
-          int c2 = 0;
-#pragma unroll
-          for (int u = 0; u < NV; ++u)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) c2 += k[u][c] >= tau ? 1 : 0;
-          return uni(wave_sum_dpp(c2));
-        }
+          for (int c = 0; c < 4; ++c) c2 += k[u][c] >= tau ? 1 : 0;
+        return uni(wave_sum_dpp(c2));
       };
       if constexpr (!kRadix) n = cnt_ge(kt);
       unsigned tau = kt;
       if (n > K) {
         uint64_t lo = kt - 1u, hi = (uint64_t)kmx + 1ull;   // cnt(lo) >= cnt(kt) > K >= cnt(hi) = 0
-        // interpolation search on the counts, safeguarded by bisection: the
-        // count falls from clo at lo to chi at hi, and the next threshold aims
-        // at K + 1/2 linearly between them; a step that does not halve the
-        // bracket is followed by a bisection step (worst case twice the
-        // bisection's steps; ~24 of them over an N(0,1) row's key range,
-        // where the interpolation lands inside the gap between the K-th and
-        // (K+1)-th largest keys in a few).  Any search keeping cnt(lo) > K >=
-        // cnt(hi) ends at the same tau, and a threshold with a count of K
-        // exactly selects the same K keys, so S and xout are unchanged.
-        int clo = n, chi = 0;   // (clo: at least cnt(lo); n = cnt(kt) serves as the estimate)
-        bool bis = false;
+        // bisection on the counts.  Any search keeping cnt(lo) > K >= cnt(hi)
+        // ends at the same tau, and a threshold with a count of K exactly
+        // selects the same K keys.
         while (hi - lo > 1) {
-          const uint64_t span = hi - lo;
-          uint64_t mid;
-          if (!kFactsInterp || bis || clo <= chi) {
-            mid = (lo + hi) >> 1;
-          } else {
-            const float f = ((float)clo - ((float)K + 0.5f)) / (float)(clo - chi);
-            uint64_t d = (uint64_t)(f * (float)span);
-            d = d < 1 ? 1 : (d > span - 1 ? span - 1 : d);
-            mid = lo + d;
-          }
+          const uint64_t mid = (lo + hi) >> 1;
           const int c2 = cnt_ge((unsigned)mid);
-          if (c2 <= K) { hi = mid; chi = c2; }
-          else { lo = mid; clo = c2; }
+          if (c2 <= K) hi = mid;
+          else lo = mid;
           if (c2 == K) break;
-          bis = !bis && 2 * (hi - lo) > span;
         }
         tau = (unsigned)hi;
       }
@@ -8508,7 +7743,7 @@ hipError_t launch_decode_c(const DecodeParams<T>& p, hipStream_t s) {
   size_t lds = decode_lds_bytes(WC > 0 ? WC : p.W, p.C, (int)sizeof(T), SC::kStateful);
   if (HW)
     lds = ((lds + 15) & ~(size_t)15) + ((BIG || SQ) ? gq_lds_bytes(SQ, SQ ? sq_slots(WC) : kQSlots) : tab_lds_bytes()) +
-          ((SQ && !BIG) ? sq_ctab_bytes(WC, 0) + sq_rowpf_bytes(p.C) + sq_stage_bytes(WC, p.C) : 0);
+          ((SQ && !BIG) ? sq_rowpf_bytes(p.C) + sq_stage_bytes(WC, p.C) : 0);
   if (p.ring > 0) lds = ((lds + 15) & ~(size_t)15) + ring_lds_bytes(p.ring, p.W, HW && !BIG ? 4 : 8);
   if (lds > kLdsBytes) return hipErrorInvalidValue;
 #ifdef CTCX_STREAM
@@ -8692,7 +7927,7 @@ size_t pre_ring_lds_bytes(const DecodeParams<T>& p, int hk, int wc) {
   const size_t b = (decode_lds_bytes(wc, p.C, (int)sizeof(T), p.scorer_tab != nullptr) + 15) & ~(size_t)15;
   return hk == 1   ? b + tab_lds_bytes()
          : hk == 2 ? b + gq_lds_bytes(false)
-         : hk == 3 ? b + gq_lds_bytes(true, sq_slots(wc)) + (p.C <= 64 ? sq_ctab_bytes(wc, (int)p.C) + sq_rowpf_bytes(p.C) + sq_stage_bytes(wc, p.C) : 0)
+         : hk == 3 ? b + gq_lds_bytes(true, sq_slots(wc)) + (p.C <= 64 ? sq_rowpf_bytes(p.C) + sq_stage_bytes(wc, p.C) : 0)
                    : b;
 }
 // the two-wave kernel this call runs (0: none), given the kind the host chose

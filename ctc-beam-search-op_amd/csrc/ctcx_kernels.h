@@ -48,7 +48,7 @@ struct CtcxStreamHdr {
   int32_t frames;         // frames decoded so far (the item's global index of the chunk's first frame)
   int32_t buf, nb, dup;   // the kernel's frame-boundary scalars: branch buffer, beam size, duplicate entries
   int32_t n_leaves, literal_steps, dup_frames, why_nonfinite, why_fill;
-  int32_t tiefree;        // (kSetMode builds)
+  int32_t reserved0;      // always 0 (once the set mode's flag): kept so that the header's layout stays
   int64_t records;
   int32_t pad[4];
 };

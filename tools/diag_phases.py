@@ -159,7 +159,4 @@ if os.environ.get("CTCX_DIAG_EXTT"):
 if os.environ.get("CTCX_DIAG_BIRTH"):   # (a build with -DCTCX_PHASE_BIRTH)
     print("  ties: frames ending without a tie %.3f; after such a frame, frames ending with one %.4f (of %.0f per item)"
           % (m[28] / fr, m[31] / max(1.0, m[30]), m[30]))
-if os.environ.get("CTCX_DIAG_SET"):   # (a build with -DCTCX_PHASE_SET -DCTCX_SET_MODE=1)
-    print("  set mode: frames tried %.3f, replayed on the heap %.4f (of frames); set pushes %.1f per frame, %.0f cycles"
-          " each (in the set loop)" % (m[16] / fr, m[17] / fr, m[18] / fr, m[23] / max(1.0, m[18])))
 
