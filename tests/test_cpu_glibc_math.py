@@ -5,7 +5,14 @@ stand-alone checkers in tools/: compiled for the host with the documented
 line (-ffp-contract=off, as the device code) and run CI-sized.  The GPU tests
 compare kernels with the oracle, whose exp and log are the host libm's; this
 is the other half, that the headers themselves agree with that libm, over
-every 97th float pattern and two million samples per double domain."""
+every 97th float pattern and two million samples per double domain.
+
+test_unit_programme_host_mode runs the host mode of the unit programme of the
+device check (tools/glibc_math_unit.hip, tests/test_gpu_glibc_math.py): the
+same input sets as on the GPU, the host pass of the header functions against
+libm, and the sizes and census of the input sets against the committed
+counts.  That is how the sets -- the subnormal-result band of expf, the bands
+around every branch constant, lse's pairs -- are verified without a GPU."""
 import os
 import re
 import shutil
@@ -50,3 +57,36 @@ def test_double_replicas_match_libm(tmp_path):
     for ln in lines:
         m = re.fullmatch(r"(exp|log) .*\S\s+(\d+) samples, (\d+) mismatches", ln)
         assert m and int(m.group(2)) == 2000000 and int(m.group(3)) == 0, out
+
+
+def test_unit_programme_host_mode():
+    import pytest
+
+    from glibc_unit import COUNTS, GROUPS, UNIT, check_counts, parse
+    hipcc = _hipcc()
+    if not (shutil.which(hipcc) or os.path.exists(hipcc)):
+        pytest.skip("hipcc is absent: tools/glibc_math_unit.bin cannot be built")
+    # the way build() makes it: csrc/Makefile's rule, with the library's flags
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "ctc-beam-search-op_amd", "csrc"), "HIPCC=" + hipcc,
+                    os.path.join("..", "..", "tools", "glibc_math_unit.bin")], check=True, timeout=600)
+    lines, total = parse(_run(UNIT, "host"))
+    assert sorted(lines) == sorted(COUNTS), sorted(lines)
+    for group in GROUPS.values():
+        check_counts(lines, group)
+    for name, ln in lines.items():
+        assert ln["host_vs_libm"] == 0 and ln["device_vs_host"] is None and ln["device_vs_libm"] is None, (name, ln)
+    assert total == (0, sum(c["inputs"] for c in COUNTS.values())), total
+    # the committed sizes against the sets as the issue of the check states them
+    band = 0xc2cff1b4 - 0xc2aeac50 + 1          # expf's subnormal results: [kExpfUnder, log(2^-126))
+    assert band == 2180453
+    floats = -(-2**32 // 97) + (band + 128) + 2 * 2**23 + (13 + 3 + 4) * 8193
+    assert COUNTS["expf"]["inputs"] == COUNTS["logf"]["inputs"] == COUNTS["expf_t"]["inputs"] == floats
+    assert COUNTS["log1pf"]["inputs"] == floats + 0x3f800000 // 13 + 1
+    for name in GROUPS["expf_t"] + ["expf"]:     # the whole band, and the sampled patterns that fall in it
+        assert COUNTS[name]["subnormal_results"] >= band, name
+    assert COUNTS["exp"]["inputs"] == 5 * 2000000 + 6 * 8193
+    assert COUNTS["log"]["inputs"] == 5 * 2000000 + 4 * 8193 + 4097
+    pairs = (0xc2d1f1b4 - 0x80000000) // 41 + 1   # d: every 41st pattern of [kExpfUnder - 1, -0]
+    assert COUNTS["lse_f32"]["inputs"] == COUNTS["lse_f64"]["inputs"] == 2 * (pairs + 25)
+    assert COUNTS["widen_f16"]["inputs"] == COUNTS["widen_bf16"]["inputs"] == 65536
+    assert COUNTS["widen2_f16"]["inputs"] == COUNTS["widen2_bf16"]["inputs"] == 2 * 65536
