@@ -1161,15 +1161,38 @@ __device__ __forceinline__ void wave_make_heap_m(CTCX_LDS HE<T>* he, const HeapM
 
 // The HEAP_SORTED event loop for float beams of up to 128 (exact_step), as one
 // hand-scheduled asm block: the same selections, bookkeeping and push_m sift as
-// the C++ loop it replaces (the stop found by s_ff1 of the path nodes meeting
-// the stop condition: path nodes are ancestors of one another, so the
-// shallowest is the lowest lane), in ~50 instructions per accepted offer (the
-// compiled loop took ~85, with the uniform state spilled into VGPR lanes).  It
+// the C++ loop it replaces, in ~42 instructions per accepted offer (the
+// compiled loop took ~85, with the uniform state spilled into VGPR lanes).
+// The stop is found per lane, as in extract_fwd_f32, and on the vector unit
+// alone: a lane is live iff it is on the root's min-child path and no proper
+// ancestor has gt (ancestors of a lane are below 32: gt's low word) -- one
+// v_and_or of the gt mask into the path test and one v_cmp.  The other way to
+// stop, a min child that is not a lane, needs no term there: lanes 32..63
+// are nobody's ancestor, and the one lane below lane 31 is lane 63, its left
+// child, which the path test drops when lane 31 picks right.  The lanes that
+// take their min child are live & ~gt (two selects: gt ? dummy : node, then
+// live ? that : dummy).  The stop is not formed as a mask: a live lane writes
+// v to its node (gt), else to its min child where that is not a lane (alx,
+// arx: the child's address in the lanes whose child on that side is past
+// position 63, the dummy elsewhere), else to its dummy -- and only one live
+// lane has such a place, since every deeper path node has it above itself.
+// No SALU instruction stands between gt and the stores: in
+// tools/push_unit.hip the loop with the stop found by s_ff1 takes 333 cycles
+// per push, the same per-lane test fed from a scalar stop-condition word 345,
+// this form 281, and 277 / 274 with two / four copies of the push body per
+// loop trip (CTCX_PUSH_COPIES, four: only the last copy branches back, each
+// copy has its own evicted-branch stub to return to).  The same programme
+// priced the order below: the new front and the next selection's compare
+// after the stores and the read (before them: +8 cycles), and CTCX_BAT_A
+// and a select between the v_cmp that writes live and the selects that read
+// it (with CTCX_BAT_A after the read and one instruction in that gap: +16).
+// tests/test_cpu_push_stop.py is the rule on the host against the
+// first-set-bit form and libstdc++.  It
 // runs until no live lane wants in (returns 0) or the next wanted lane k
 // re-offers a branch child (returns 1: the caller decides that event).  It is
-// software-pipelined: as soon as a push has its new front, the next event's
-// selection starts, interleaved with the rest of the push (stop, moves,
-// stores); the next push's child pairs are read right after the stores.
+// software-pipelined: the next push's child pairs are read right after the
+// stores, and the new front and the next event's selection run in the shadow
+// of that read.
 //   state (SGPR): NC / RB / done lane masks, the front (fv, fs), the bump
 //   pointer, the eviction-record count; (VGPR): myslot, evr, bat.
 //   he addresses are LDS byte addresses: node j (aj), its child pair (al, ar),
@@ -1194,18 +1217,97 @@ __device__ __forceinline__ void wave_make_heap_m(CTCX_LDS HE<T>* he, const HeapM
 #define CTCX_HEV_CS "v238"
 #define CTCX_HEV_BT "v239"
 #define CTCX_HEV_STORES "ds_write2_b32 v239, v237, v238 offset1:1\n\tds_write2_b32 v236, v240, v241 offset1:1\n\t"
+// One push and the next selection; N is the copy's label suffix.  It ends with
+// SCC = (the next wanted lane k re-offers a branch child).
+#define CTCX_HEV_PUSH(N)                                                                                     \
+      ".Lev_tail" N "_%=:\n\t"                                                                               \
+      "s_lshl_b64 s[80:81], -2, %[k]\n\t"                  /* lanes after k */                              \
+      "v_readlane_b32 s84, %[s], %[k]\n\t"                 /* v = offer k's score */                        \
+      "s_mov_b32 s85, %[fs]\n\t"                           /* slot = the front's */                         \
+      "s_cmp_lt_i32 %[fs], %[nb]\n\t"                                                                        \
+      "s_cbranch_scc1 .Lev_evb" N "_%=\n"                                                                    \
+      ".Lev_slot" N "_%=:\n\t"                                                                               \
+      "v_cmp_eq_u32_e64 s[90:91], %[fs], %[my]\n\t"        /* an entry accepted in this chunk is the evicted front */ \
+      "s_mov_b32 m0, %[k]\n\t"                                                                               \
+      "v_cndmask_b32_e64 %[my], %[my], -1, s[90:91]\n\t"                                                     \
+      "v_writelane_b32 %[my], s85, m0\n\t"                 /* lane k: its entry's slot */                   \
+      CTCX_EVCNT                                                                                             \
+      "s_waitcnt lgkmcnt(0)\n\t"                                                                             \
+      "v_cmp_ngt_f32_e64 s[92:93], v234, v232\n\t"         /* pickR = !(R > L) */                           \
+      "v_mov_b64_e32 v[240:241], s[84:85]\n\t"                                                               \
+      "v_cndmask_b32_e64 " CTCX_HEV_CV ", v232, v234, s[92:93]\n\t"   /* cv */                              \
+      "v_cndmask_b32_e64 " CTCX_HEV_CS ", v233, v235, s[92:93]\n\t"   /* cs */                              \
+      "v_bitop3_b32 " CTCX_HEV_BT ", s92, %[req], %[anc] bitop3:0x28\n\t"  /* (pickR ^ req) & anc */        \
+      "v_cmp_lt_f32_e64 s[96:97], s84, " CTCX_HEV_CV "\n\t"           /* gt: min child > v */               \
+      "v_cndmask_b32_e64 v236, %[alx], %[arx], s[92:93]\n\t"/* the min child's address where v may land there */\
+      "v_readfirstlane_b32 s86, " CTCX_HEV_CV "\n\t"       /* c0: the root's min child */                    \
+      "v_and_or_b32 " CTCX_HEV_BT ", s96, %[anc], " CTCX_HEV_BT "\n\t"/* off the path, or below a gt */      \
+      "v_readfirstlane_b32 s87, " CTCX_HEV_CS "\n\t"                                                         \
+      "v_cmp_eq_u32_e64 s[94:95], 0, " CTCX_HEV_BT "\n\t"  /* live: path nodes at or above the stop */       \
+      "v_cndmask_b32_e64 v236, v236, %[aj], s[96:97]\n\t"  /* v lands on the stop (gt) or in its min child */\
+      "v_cndmask_b32_e64 v243, %[aj], %[dum], s[96:97]\n\t"/* no gt: the node takes its min child */         \
+      CTCX_BAT_A                                                                                             \
+      "v_cndmask_b32_e64 " CTCX_HEV_BT ", %[dum], v243, s[94:95]\n\t"/* up */                                \
+      "v_cndmask_b32_e64 v236, %[dum], v236, s[94:95]\n\t" /* the stop */                                    \
+      CTCX_HEV_STORES                                                                                        \
+      "ds_read_b128 v[232:235], %[al]\n\t"                 /* the next push's child pairs */                 \
+      "s_bitcmp1_b32 s96, 0\n\t"                           /* keep: v stays at the root */                   \
+      "s_cselect_b32 %[fv], s84, s86\n\t"                  /* the new front */                               \
+      "s_cselect_b32 %[fs], s85, s87\n\t"                                                                    \
+      "v_cmp_lt_f32_e64 s[88:89], %[fv], %[s]\n\t"         /* next: s > front */                             \
+      CTCX_BAT_B                                                                                             \
+      CTCX_BAT_C                                                                                             \
+      "s_and_b64 s[88:89], s[88:89], %[nc]\n\t"                                                              \
+      "s_or_b64 s[88:89], s[88:89], %[rb]\n\t"                                                               \
+      "s_and_b64 s[88:89], s[88:89], s[80:81]\n\t"         /* next m */                                     \
+      "s_cbranch_scc0 .Lev_exit_%=\n\t"                                                                      \
+      "s_ff1_i32_b64 %[k], s[88:89]\n\t"                                                                     \
+      "s_bitcmp1_b64 %[lb], %[k]\n\t"
+// into the next copy, unless k is rare
+#define CTCX_HEV_NEXT "s_cbranch_scc1 .Lev_rare_%=\n"
+// the evicted front is a branch's entry: a fresh slot; record the eviction; a
+// live re-offer of that branch is now wanted (back to the copy it left)
+#define CTCX_HEV_EVB(N)                                                                                      \
+      ".Lev_evb" N "_%=:\n\t"                                                                                \
+      "s_mov_b32 s85, %[nfree]\n\t"                                                                          \
+      "s_add_u32 %[nfree], %[nfree], 1\n\t"                                                                  \
+      "s_mov_b32 m0, %[nv]\n\t"                                                                              \
+      "s_add_u32 %[nv], %[nv], 1\n\t"                                                                        \
+      "v_writelane_b32 %[evr], %[fs], m0\n\t"                                                                \
+      "v_cmp_eq_u32_e64 s[90:91], %[fs], %[c]\n\t"                                                           \
+      "s_and_b64 s[90:91], s[90:91], %[lb]\n\t"                                                              \
+      "s_or_b64 %[rb], %[rb], s[90:91]\n\t"                                                                  \
+      "s_branch .Lev_slot" N "_%=\n"
+#ifndef CTCX_PUSH_COPIES
+#define CTCX_PUSH_COPIES 4
+#endif
+#if CTCX_PUSH_COPIES == 1
+#define CTCX_HEV_BODY CTCX_HEV_PUSH("0")
+#define CTCX_HEV_EVBS CTCX_HEV_EVB("0")
+#elif CTCX_PUSH_COPIES == 2
+#define CTCX_HEV_BODY CTCX_HEV_PUSH("0") CTCX_HEV_NEXT CTCX_HEV_PUSH("1")
+#define CTCX_HEV_EVBS CTCX_HEV_EVB("0") CTCX_HEV_EVB("1")
+#elif CTCX_PUSH_COPIES == 4
+#define CTCX_HEV_BODY                                                                                        \
+  CTCX_HEV_PUSH("0") CTCX_HEV_NEXT CTCX_HEV_PUSH("1") CTCX_HEV_NEXT CTCX_HEV_PUSH("2") CTCX_HEV_NEXT CTCX_HEV_PUSH("3")
+#define CTCX_HEV_EVBS CTCX_HEV_EVB("0") CTCX_HEV_EVB("1") CTCX_HEV_EVB("2") CTCX_HEV_EVB("3")
+#else
+#error "CTCX_PUSH_COPIES: 1, 2 or 4"
+#endif
 __device__ __forceinline__ int heap_events_f32(float s, int c, int sl, unsigned anc, unsigned req, unsigned aj,
                                                unsigned al, unsigned ar, unsigned dum, int& myslot, int& evr,
                                                float& bat, uint64_t& NC, uint64_t& RB, uint64_t& done, uint64_t LB,
                                                float& fv, int& fs, int& nfree, int& nv, int nb, int& k, int& cnt) {
   int st;
-  const unsigned k31 = 0x80000000u;
+  // where v lands in a min child that is not a lane (the children of lanes
+  // 32..63, lane 31's right child: al - aj is 8 * (lane + 1)); any other min
+  // child is on the path itself and not the stop: the dummy
+  const unsigned alx = al - aj > 8u * 32u ? al : dum, arx = al - aj > 8u * 31u ? ar : dum;
   // every scalar operand provably uniform (the asm's "s" constraints)
   NC = uni64(NC); RB = uni64(RB); done = uni64(done); LB = uni64(LB);
   fv = uni(fv); fs = uni(fs); nfree = uni(nfree); nv = uni(nv); nb = uni(nb); cnt = uni(cnt);
   asm volatile(
       "s_mov_b32 %[st], 0\n\t"
-      "s_mov_b32 s99, -1\n\t"                              // cnd's high word: lanes 32..63 always stop
       "s_not_b64 s[80:81], %[done]\n\t"                    // lanes still to come
       // select the first event
       "v_cmp_lt_f32_e64 s[88:89], %[fv], %[s]\n\t"          // s > front
@@ -1218,70 +1320,11 @@ __device__ __forceinline__ int heap_events_f32(float s, int c, int sl, unsigned 
       "s_cbranch_scc1 .Lev_rare_%=\n\t"
       "ds_read_b128 v[232:235], %[al]\n"                   // its child pairs (L.v, L.s, R.v, R.s)
       // event k (v = s84, slot = s85): its bookkeeping, then its push, then
-      // the next selection
-      ".Lev_tail_%=:\n\t"
-      "s_lshl_b64 s[80:81], -2, %[k]\n\t"                  // lanes after k
-      "v_readlane_b32 s84, %[s], %[k]\n\t"                 // v = offer k's score
-      "s_mov_b32 s85, %[fs]\n\t"                           // slot = the front's
-      "s_cmp_lt_i32 %[fs], %[nb]\n\t"
-      "s_cbranch_scc1 .Lev_evb_%=\n"
-      ".Lev_slot_%=:\n\t"
-      "v_cmp_eq_u32_e64 s[90:91], %[fs], %[my]\n\t"        // an entry accepted in this chunk is the evicted front
-      "s_mov_b32 m0, %[k]\n\t"
-      "v_cndmask_b32_e64 %[my], %[my], -1, s[90:91]\n\t"
-      "v_writelane_b32 %[my], s85, m0\n\t"                 // lane k: its entry's slot
-      CTCX_EVCNT
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "v_cmp_ngt_f32_e64 s[92:93], v234, v232\n\t"         // pickR = !(R > L)
-      "v_mov_b64_e32 v[240:241], s[84:85]\n\t"
-      "v_cndmask_b32_e64 " CTCX_HEV_CV ", v232, v234, s[92:93]\n\t"   // cv
-      "v_cndmask_b32_e64 " CTCX_HEV_CS ", v233, v235, s[92:93]\n\t"   // cs
-      "v_bitop3_b32 " CTCX_HEV_BT ", s92, %[req], %[anc] bitop3:0x28\n\t"
-      "v_cmp_lt_f32_e64 s[96:97], s84, " CTCX_HEV_CV "\n\t"           // gt: min child > v
-      "v_cndmask_b32_e64 v236, %[al], %[ar], s[92:93]\n\t" // the min child's address
-      "v_readfirstlane_b32 s86, " CTCX_HEV_CV "\n\t"                  // c0: the root's min child
-      "v_cmp_eq_u32_e64 s[94:95], 0, " CTCX_HEV_BT "\n\t"             // onp: on the root's min-child path
-      "v_readfirstlane_b32 s87, " CTCX_HEV_CS "\n\t"
-      "v_cndmask_b32_e64 v236, v236, %[aj], s[96:97]\n\t"  // v lands on the stop (gt) or its min child
-      "s_and_b32 s98, s92, %[k31]\n\t"
-      "s_bitcmp1_b32 s96, 0\n\t"                           // keep: v stays at the root
-      "s_cselect_b32 %[fv], s84, s86\n\t"                  // the new front
-      "s_cselect_b32 %[fs], s85, s87\n\t"
-      "s_or_b32 s98, s98, s96\n\t"                         // cnd: gt, or the min child is a non-lane leaf
-      CTCX_BAT_A
-      "v_cmp_lt_f32_e64 s[88:89], %[fv], %[s]\n\t"         // next: s > front
-      "s_and_b64 s[90:91], s[94:95], s[98:99]\n\t"         // cm (path nodes meeting the stop condition)
-      "s_ff1_i32_b64 s86, s[90:91]\n\t"                    // the stop: the shallowest of them
-      CTCX_BAT_B
-      "s_lshl_b64 s[90:91], -2, s86\n\t"
-      "s_andn2_b64 s[94:95], s[94:95], s[90:91]\n\t"       // live: path nodes at or above the stop
-      "s_andn2_b64 s[90:91], s[94:95], s[96:97]\n\t"       // up: takes its min child
-      "s_lshl_b64 s[94:95], 1, s86\n\t"                    // the stop
-      "v_cndmask_b32_e64 " CTCX_HEV_BT ", %[dum], %[aj], s[90:91]\n\t"
-      "v_cndmask_b32_e64 v236, %[dum], v236, s[94:95]\n\t"
-      CTCX_HEV_STORES
-      "ds_read_b128 v[232:235], %[al]\n\t"                 // the next push's child pairs
-      CTCX_BAT_C
-      "s_and_b64 s[88:89], s[88:89], %[nc]\n\t"
-      "s_or_b64 s[88:89], s[88:89], %[rb]\n\t"
-      "s_and_b64 s[88:89], s[88:89], s[80:81]\n\t"         // next m
-      "s_cbranch_scc0 .Lev_exit_%=\n\t"
-      "s_ff1_i32_b64 %[k], s[88:89]\n\t"
-      "s_bitcmp1_b64 %[lb], %[k]\n\t"
-      "s_cbranch_scc0 .Lev_tail_%=\n\t"                    // the next push, unless k is rare
+      // the next selection; only the last copy branches back
+      CTCX_HEV_BODY
+      "s_cbranch_scc0 .Lev_tail0_%=\n\t"                   // the next push, unless k is rare
       "s_branch .Lev_rare_%=\n"
-      // the evicted front is a branch's entry: a fresh slot; record the
-      // eviction; a live re-offer of that branch is now wanted
-      ".Lev_evb_%=:\n\t"
-      "s_mov_b32 s85, %[nfree]\n\t"
-      "s_add_u32 %[nfree], %[nfree], 1\n\t"
-      "s_mov_b32 m0, %[nv]\n\t"
-      "s_add_u32 %[nv], %[nv], 1\n\t"
-      "v_writelane_b32 %[evr], %[fs], m0\n\t"
-      "v_cmp_eq_u32_e64 s[90:91], %[fs], %[c]\n\t"
-      "s_and_b64 s[90:91], s[90:91], %[lb]\n\t"
-      "s_or_b64 %[rb], %[rb], s[90:91]\n\t"
-      "s_branch .Lev_slot_%=\n"
+      CTCX_HEV_EVBS
       ".Lev_rare_%=:\n\t"
       "s_mov_b32 %[st], 1\n"
       ".Lev_exit_%=:\n\t"
@@ -1290,7 +1333,7 @@ __device__ __forceinline__ int heap_events_f32(float s, int c, int sl, unsigned 
       : [my] "+v"(myslot), [evr] "+v"(evr), [bat] "+v"(bat), [nc] "+s"(NC), [rb] "+s"(RB), [done] "+s"(done),
         [fv] "+s"(fv), [fs] "+s"(fs), [nfree] "+s"(nfree), [nv] "+s"(nv), [k] "=&s"(k), [st] "=&s"(st), [cnt] "+s"(cnt)
       : [s] "v"(s), [c] "v"(c), [sl] "v"(sl), [anc] "v"(anc), [req] "v"(req), [aj] "v"(aj), [al] "v"(al),
-        [ar] "v"(ar), [dum] "v"(dum), [lb] "s"(LB), [nb] "s"(nb), [k31] "s"(k31)
+        [alx] "v"(alx), [arx] "v"(arx), [dum] "v"(dum), [lb] "s"(LB), [nb] "s"(nb)
       : "memory", "vcc", "m0", "s80", "s81", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93",
         "s94", "s95", "s96", "s97", "s98", "s99", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239",
         "v240", "v241", "v242", "v243");

@@ -11,7 +11,7 @@ mkdir -p $D/../include 2>/dev/null || true
 cp $R/include/ctcext.h $D/include/
 sed -i "s#-falign-loops=32#-falign-loops=32 $2#" $D/csrc/Makefile
 sed -i "s#../../include/ctcext.h#../include/ctcext.h#" $D/csrc/Makefile
-sed -i 's#"../../include/ctcext.h"#"../include/ctcext.h"#' $D/csrc/ctcext_capi.hip $D/csrc/ctcx_times_row.cpp $D/csrc/ctcx_skip_row.cpp
+sed -i 's#"../../include/ctcext.h"#"../include/ctcext.h"#' $D/csrc/ctcext_capi.hip $D/csrc/ctcx_times_row.cpp $D/csrc/ctcx_skip_row.cpp $D/csrc/ctcx_scores_row.cpp
 # (the library alone: the default target also builds the unit programme under tools/)
 if [ "$3" = phases ]; then
   make -s -j${JOBS:-10} -C $D/csrc OUT=../ctcext_amd/lib/product.so PHASES_OUT=../ctcext_amd/lib/libctcext.so ../ctcext_amd/lib/libctcext.so 2>&1 | grep -E "error" || true
