@@ -8,6 +8,7 @@
 //   TopPaths errors                decoder.h:237-243
 //   StoreAllDecodedSequences       :163-257 -> ctcx_traceback + ctcx_scan + ctcx_pack
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,6 +25,7 @@
 #include "ctcx_skip.h"
 #include "ctcx_stable.h"
 #include "ctcx_stream_dense.h"
+#include "ctcx_stream_store.h"
 #include "ctcx_times.h"
 
 namespace ctcx {
@@ -1569,6 +1571,17 @@ struct ctcext_stream {
     HostBuf land;              // stream_settle's: the items
   } sk;
   std::vector<int64_t> kept;   // host mirror of the record frames of a skipping stream (frames holds n there)
+  // The score store (ctcext_stream_open_scores; ctcext.h, "Streaming: token
+  // scores"): the logits and the normaliser of every committed frame, on the
+  // original time axis, allocated at open for the stream's life.
+  struct {
+    bool on = false;
+    int32_t fmt = 0;           // sx's element format (CTCEXT_IN_*)
+    void* sx = nullptr;        // [B][max_frames][C]
+    void* snorm = nullptr;     // [max_frames][B] of the compute dtype
+    bool append_timed = false, scores_timed = false;   // events [0], [1] / [2], [3] were recorded for the last push
+    hipEvent_t ev[4] = {};     // CTCEXT_FLAG_PROFILE: around the append kernel, around the token-scores kernel
+  } sc;
 };
 
 // The stream's attributes as the one-shot argument struct, for the shared
@@ -1632,7 +1645,8 @@ extern "C" int ctcext_stream_validate_chunk(const ctcext_stream_args* a, const c
 }
 
 static void stream_free(ctcext_stream* st) {
-  void* ps[] = {st->state[0], st->state[1], st->rec, st->gstate, st->sctab, st->cum, st->stable_cache};
+  void* ps[] = {st->state[0], st->state[1], st->rec,   st->gstate, st->sctab, st->cum, st->stable_cache,
+                st->sc.sx,    st->sc.snorm};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   DevBuf* bufs[] = {&st->x, &st->xw, &st->sl, &st->norm, &st->prep, &st->stable_out, &st->stable_flags};
@@ -1647,6 +1661,8 @@ static void stream_free(ctcext_stream* st) {
   for (DevBuf* b : kbufs) b->release();
   st->sk.land.release();
   for (auto& ev : st->dn.ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : st->sc.ev)
     if (ev) (void)hipEventDestroy(ev);
   delete st;
 }
@@ -1778,9 +1794,28 @@ static int stream_open_skip_state(ctcext_stream* st) {
   return CTCEXT_OK;
 }
 
-// k: the checked skip arguments of ctcext_stream_open_skip, or null.
+// The score store of a stream: sized by the batch, max_frames and num_classes
+// alone, so allocated at open, with the events of its timings (a push
+// allocates nothing).  Rows are written before they are read; nothing to clear.
+static int stream_open_score_store(ctcext_stream* st, int32_t store_format) {
+  const ctcext_stream_args& a = st->a;
+  int64_t xb = 0, nb = 0;
+  if (!ctcx_store_bytes(a.batch_size, a.max_frames, a.num_classes, store_format, a.dtype == CTCEXT_F64, &xb, &nb))
+    return fail(CTCEXT_INVALID_ARGUMENT, "the score store's size leaves 64 bits");
+  st->sc.fmt = store_format;
+  // (+ 256 like the stream's other buffers: never a zero-byte allocation, with batch_size or max_frames 0; the
+  //  kernels stay inside the xb and nb bytes that ctcext_stream_scores_bytes reports)
+  HIP_OR_FAIL(hipMalloc(&st->sc.sx, (size_t)xb + 256));
+  HIP_OR_FAIL(hipMalloc(&st->sc.snorm, (size_t)nb + 256));
+  for (auto& ev : st->sc.ev) HIP_OR_FAIL(hipEventCreate(&ev));
+  st->sc.on = true;
+  return CTCEXT_OK;
+}
+
+// k: the checked skip arguments of ctcext_stream_open_skip, or null; sa: the
+// checked arguments of ctcext_stream_open_scores, or null.
 static int stream_open_common(ctcext_decoder* d, const ctcext_stream_args* a, const ctcext_skip_args* k,
-                              ctcext_stream** out) {
+                              const ctcext_stream_scores_args* sa, ctcext_stream** out) {
   int rc;
   DeviceGuard guard;
   HIP_OR_FAIL(hipSetDevice(d->devs[0].device));
@@ -1797,6 +1832,7 @@ static int stream_open_common(ctcext_decoder* d, const ctcext_stream_args* a, co
     st->sk.kept_out = k->kept;
     rc = stream_open_skip_state(st);
   }
+  if (rc == CTCEXT_OK && sa) rc = stream_open_score_store(st, sa->store_format);
   st->a.scorer_table = nullptr;   // (copied)
   if (rc != CTCEXT_OK) {
     const std::string keep = g_err;
@@ -1814,7 +1850,7 @@ extern "C" int ctcext_stream_open(ctcext_decoder* d, const ctcext_stream_args* a
   const int rc = ctcext_stream_validate(a);
   if (rc != CTCEXT_OK) return rc;
   if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a stream needs a one-device decoder handle");
-  return stream_open_common(d, a, nullptr, out);
+  return stream_open_common(d, a, nullptr, nullptr, out);
 }
 
 // What a skipping stream asks of its arguments beyond ctcext_stream_validate,
@@ -1833,7 +1869,7 @@ extern "C" int ctcext_stream_open_skip(ctcext_decoder* d, const ctcext_stream_ar
                                          "enqueue-only push alone");
   if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a skipping stream needs a one-device decoder handle");
-  return stream_open_common(d, a, k, out);
+  return stream_open_common(d, a, k, nullptr, out);
 }
 
 extern "C" int ctcext_stream_kept(ctcext_stream* st, int64_t* kept) {
@@ -2078,6 +2114,9 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
   if (!st || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   if (st->sk.on)
     return fail(CTCEXT_UNIMPLEMENTED, "a skipping stream has no synchronous push: use ctcext_stream_push_dense");
+  if (st->sc.on)
+    return fail(CTCEXT_UNIMPLEMENTED,
+                "a stream with a score store has no synchronous push: use ctcext_stream_push_dense");
   ctcext_decoder* d = st->dec;
   const ctcext_stream_args& a = st->a;
   const int64_t B = a.batch_size;
@@ -2114,7 +2153,7 @@ extern "C" int ctcext_stream_push(ctcext_stream* st, const ctcext_chunk* c, ctce
   }
   d->have = false;
   d->dense.have = false;   // (the workspace ctcext_dense_check reads is this call's now)
-  d->ss.have = false;      // (a push keeps neither its chunk nor its normaliser: nothing to score)
+  d->ss.have = false;      // (this push keeps neither its chunk nor its normaliser: nothing to score)
   if (B > 0) {
     rc = a.dtype == CTCEXT_F32 ? stream_push_t<float>(st, c, hcl, sizes, s) : stream_push_t<double>(st, c, hcl, sizes, s);
     if (rc != CTCEXT_OK) return rc;
@@ -2309,6 +2348,13 @@ extern "C" int ctcext_stream_stable_reference(ctcext_stream* st, int32_t* decode
 // hand-over held back over state[cur], so cur never changes in this path and
 // a push is the same chain of launches over the same addresses every time.
 
+// A chunk against a score store's element format: a half store holds the bits it is given.
+static int check_store_chunk(int32_t store_format, const ctcext_chunk* c) {
+  if (store_format != CTCEXT_IN_NATIVE && c->inputs_format != store_format)
+    return fail(CTCEXT_INVALID_ARGUMENT, "chunk inputs_format differs from the stream's score store format");
+  return CTCEXT_OK;
+}
+
 // What needs no data, on the host: a is a validated stream's attributes.
 static int check_push_dense(const ctcext_stream_args* a, const ctcext_chunk* c, const ctcext_stream_dense_outputs* o) {
   if (!a || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
@@ -2418,6 +2464,9 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
   else if (Tc <= 1) st_t = st_b * B;
   else if (B <= 1) st_b = st_t * Tc;
   const void* x = c->inputs;
+  const void* const x_in = x;   // the caller's rows as given: what a score store appends
+  const int xfmt_in = xfmt;
+  const int64_t st_t_in = st_t, st_b_in = st_b;
   const int32_t* sl = (const int32_t*)n.sl.p;
   auto& k = st->sk;
   char* const committed = (char*)st->state[st->cur];
@@ -2485,6 +2534,39 @@ static int stream_push_dense_t(ctcext_stream* st, const ctcext_chunk* c, const i
                                            a.blank_index, s));
     else
       HIP_OR_FAIL(ctcx::launch_row_norm<T>(x, xfmt, sl, (T*)st->norm.p, Tc, B, C, st_t, st_b, s));
+  }
+  st->sc.append_timed = st->sc.scores_timed = false;
+  if (st->sc.on && Tc > 0) {
+    // the rows this push takes and their normaliser, behind what each item holds.  The base is committed
+    // state (the header's frames; a skipping stream's n) and the commit comes later: an item that does not
+    // commit keeps its base, and its next push writes these rows again
+    CtcxStreamStoreParams ap{};
+    ap.x = x_in;
+    ap.norm = k.on ? k.norm.p : st->norm.p;   // (of the caller's rows in both)
+    ap.len = (const int32_t*)n.sl.p;
+    // (the kernel reads base as the first 32-bit word of the item's record: a reordering of either struct
+    //  would break the roll-back without a word)
+    static_assert(offsetof(CtcxSkipItem, n) == 0 && sizeof(CtcxSkipItem::n) == 4 && sizeof(CtcxSkipItem) % 4 == 0,
+                  "the append reads CtcxSkipItem.n as the item's first word");
+    static_assert(offsetof(CtcxStreamHdr, frames) == 0 && sizeof(CtcxStreamHdr::frames) == 4,
+                  "the append reads CtcxStreamHdr.frames as the item's first word");
+    if (k.on) {
+      ap.base = (const int32_t*)k.item.p;   // CtcxSkipItem.n
+      ap.base_stride = (int64_t)(sizeof(CtcxSkipItem) / 4);
+    } else {
+      ap.base = (const int32_t*)committed;  // CtcxStreamHdr.frames
+      ap.base_stride = st->stride / 4;
+    }
+    ap.sx = st->sc.sx;
+    ap.snorm = st->sc.snorm;
+    ap.chunk_time = Tc; ap.max_frames = F; ap.B = B; ap.C = C; ap.xst_t = st_t_in; ap.xst_b = st_b_in;
+    ap.xfmt = xfmt_in; ap.sfmt = st->sc.fmt; ap.f64 = ts == 8;
+    if (prof) HIP_OR_FAIL(hipEventRecord(st->sc.ev[0], s));
+    HIP_OR_FAIL(ctcx_launch_stream_store(ap, s));
+    if (prof) {
+      HIP_OR_FAIL(hipEventRecord(st->sc.ev[1], s));
+      st->sc.append_timed = true;
+    }
   }
   if (prof) HIP_OR_FAIL(hipEventRecord(n.ev[1], s));
 
@@ -2604,6 +2686,7 @@ extern "C" int ctcext_stream_push_dense(ctcext_stream* st, const ctcext_chunk* c
   if (!st || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
   const ctcext_stream_args& a = st->a;
   int rc = check_push_dense(&a, c, o);
+  if (rc == CTCEXT_OK && st->sc.on) rc = check_store_chunk(st->sc.fmt, c);
   if (rc != CTCEXT_OK) return rc;
   if (a.batch_size == 0) {
     g_err.clear();
@@ -2881,8 +2964,9 @@ extern "C" int ctcext_stream_token_times_ms(ctcext_stream* st, double* ms) {
 // ---------------------------------------------------------------------------
 // Token scores (ctcext.h, "Token scores"): ctcx_scores.hip's kernel over the
 // walks the traceback left in the workspace, the spans of the token times, the
-// normaliser and the logits the decode read (ScoreSrc).  The decoder's only: a
-// stream keeps neither its chunks nor their normalisers.
+// normaliser and the logits the decode read (ScoreSrc): the decoder's after a
+// dense or a synchronous call; a stream's over its own walks and its score
+// store (further down).
 
 extern "C" int32_t ctcext_token_scores_tile(void) { return kScoresTile; }
 
@@ -3016,5 +3100,133 @@ extern "C" int ctcext_dense_token_scores_ms(ctcext_decoder* d, double* ms) {
   float f = 0;
   HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[7], root.ev[8]));
   *ms = f;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Streaming: token scores (ctcext.h).  The store is a stream's own x / norm in
+// the layout CtcxScoresParams takes, so the kernel above runs unchanged.
+
+extern "C" int ctcext_stream_scores_validate(const ctcext_stream_args* a, const ctcext_stream_scores_args* sa) {
+  if (!a || !sa) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_stream_validate(a);
+  if (rc != CTCEXT_OK) return rc;
+  const int32_t f = sa->store_format;
+  if (f != CTCEXT_IN_NATIVE && f != CTCEXT_IN_F16 && f != CTCEXT_IN_BF16)
+    return fail(CTCEXT_INVALID_ARGUMENT, "store_format must be CTCEXT_IN_NATIVE, CTCEXT_IN_F16 or CTCEXT_IN_BF16");
+  if (f != CTCEXT_IN_NATIVE && a->dtype != CTCEXT_F32)
+    return fail(CTCEXT_INVALID_ARGUMENT, "a half-precision score store needs dtype float32");
+  if (a->on_device != 1)
+    return fail(CTCEXT_INVALID_ARGUMENT, "a stream with a score store needs device chunks (on_device == 1): it has "
+                                         "the enqueue-only push alone");
+  rc = ctcext_token_times_validate(a->num_classes, a->blank_index, a->blank_label);
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+extern "C" int ctcext_stream_scores_validate_chunk(const ctcext_stream_args* a, const ctcext_stream_scores_args* sa,
+                                                   const ctcext_chunk* c) {
+  int rc = ctcext_stream_scores_validate(a, sa);
+  if (rc == CTCEXT_OK) rc = check_push_dense(a, c, nullptr);
+  if (rc == CTCEXT_OK) rc = check_store_chunk(sa->store_format, c);
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+extern "C" int64_t ctcext_stream_scores_bytes(const ctcext_stream_args* a, const ctcext_stream_scores_args* sa) {
+  if (ctcext_stream_scores_validate(a, sa) != CTCEXT_OK) return -1;
+  int64_t xb = 0, nb = 0;
+  if (!ctcx_store_bytes(a->batch_size, a->max_frames, a->num_classes, sa->store_format, a->dtype == CTCEXT_F64, &xb,
+                        &nb)) {
+    (void)fail(CTCEXT_INVALID_ARGUMENT, "the score store's size leaves 64 bits");
+    return -1;
+  }
+  return xb + nb;
+}
+
+// (the order of ctcext_stream_open_skip: everything the host can say first, the handle last)
+extern "C" int ctcext_stream_open_scores(ctcext_decoder* d, const ctcext_stream_args* a, const ctcext_skip_args* k,
+                                         const ctcext_stream_scores_args* sa, ctcext_stream** out) {
+  if (!a || !sa || !out) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_stream_scores_validate(a, sa);
+  if (rc != CTCEXT_OK) return rc;
+  if (k) {
+    rc = ctcext_skip_validate(k);
+    if (rc != CTCEXT_OK) return rc;
+  }
+  if (ctcext_stream_scores_bytes(a, sa) < 0) return CTCEXT_INVALID_ARGUMENT;
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (d->devs.size() != 1)
+    return fail(CTCEXT_UNIMPLEMENTED, "a stream with a score store needs a one-device decoder handle");
+  return stream_open_common(d, a, k, sa, out);
+}
+
+extern "C" int ctcext_stream_token_scores(ctcext_stream* st, const ctcext_token_times* t,
+                                          const ctcext_token_scores* o) {
+  if (!st) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_scores_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!t || !t->start || !t->end)
+    return fail(CTCEXT_INVALID_ARGUMENT, "token scores need the start and end of ctcext_stream_token_times");
+  auto& n = st->dn;
+  const ctcext_stream_args& a = st->a;
+  if (!st->sc.on)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_stream_token_scores on a stream without a score store (ctcext_stream_open_scores)");
+  if (a.batch_size > 0 && (!n.used || !n.results))
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_stream_token_scores without a ctcext_stream_push_dense that had hypothesis outputs");
+  rc = ctcext_token_times_validate(a.num_classes, a.blank_index, a.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (a.batch_size == 0) return CTCEXT_OK;
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  hipStream_t s = n.s;
+  CtcxScoresParams p{};
+  p.seq = (const int32_t*)n.seq.p;
+  p.len = (const int32_t*)n.len.p;
+  p.frames = st->sk.on ? (const int32_t*)st->sk.nfr.p : (const int32_t*)st->cum;
+  p.status = (const int32_t*)n.fin.p;
+  p.start = t->start; p.end = t->end;
+  p.x = st->sc.sx;
+  p.norm = st->sc.snorm;
+  p.Tmax = a.max_frames; p.B = a.batch_size; p.C = a.num_classes;
+  p.xst_t = a.num_classes; p.xst_b = a.max_frames * a.num_classes;
+  p.P = a.top_paths; p.xfmt = st->sc.fmt; p.f64 = a.dtype == CTCEXT_F64 ? 1 : 0;
+  p.blank_index = a.blank_index; p.blank_label = a.blank_label;
+  p.logp_sum = o->logp_sum; p.logp_min = o->logp_min;
+  const bool prof = (n.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(st->sc.ev[2], s));
+  HIP_OR_FAIL(ctcx_launch_token_scores(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(st->sc.ev[3], s));
+    st->sc.scores_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_scores_ms(ctcext_stream* st, double* append_ms, double* scores_ms) {
+  if (!st || !append_ms || !scores_ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!st->sc.on)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_stream_scores_ms on a stream without a score store (ctcext_stream_open_scores)");
+  if (!st->dn.used || !(st->dn.flags & CTCEXT_FLAG_PROFILE))
+    return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE enqueue-only push on this stream yet");
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  *append_ms = *scores_ms = 0;
+  float f = 0;
+  if (st->sc.append_timed) {
+    HIP_OR_FAIL(hipEventSynchronize(st->sc.ev[1]));
+    HIP_OR_FAIL(hipEventElapsedTime(&f, st->sc.ev[0], st->sc.ev[1]));
+    *append_ms = f;
+  }
+  if (st->sc.scores_timed) {
+    HIP_OR_FAIL(hipEventSynchronize(st->sc.ev[3]));
+    HIP_OR_FAIL(hipEventElapsedTime(&f, st->sc.ev[2], st->sc.ev[3]));
+    *scores_ms = f;
+  }
+  g_err.clear();
   return CTCEXT_OK;
 }

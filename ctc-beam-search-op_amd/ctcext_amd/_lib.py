@@ -71,6 +71,11 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_SKIP_SYMBOLS
 TOKEN_SCORES_SYMBOLS = ("ctcext_token_scores_tile", "ctcext_dense_token_scores", "ctcext_fetch_token_scores",
                         "ctcext_token_scores_row", "ctcext_dense_token_scores_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TOKEN_SCORES_SYMBOLS
+# token scores of a stream, from its score store (CTCEXT_HAS_STREAM_SCORES)
+STREAM_SCORES_SYMBOLS = ("ctcext_stream_scores_validate", "ctcext_stream_scores_validate_chunk",
+                         "ctcext_stream_scores_bytes", "ctcext_stream_open_scores", "ctcext_stream_token_scores",
+                         "ctcext_stream_scores_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_SCORES_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -137,6 +142,11 @@ class TokenScoresOut(ctypes.Structure):
 class SkipArgs(ctypes.Structure):
     """ctcext_skip_args: the threshold of a skipping decode and where its kept counts go."""
     _fields_ = [("logp_threshold", ctypes.c_double), ("kept", ctypes.c_void_p)]
+
+
+class StreamScoresArgs(ctypes.Structure):
+    """ctcext_stream_scores_args: the element format of a stream's score store."""
+    _fields_ = [("store_format", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
 class StreamDenseOutputs(ctypes.Structure):
@@ -369,6 +379,25 @@ def load():
         lib.ctcext_token_scores_row.restype = ctypes.c_int
         lib.ctcext_dense_token_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_token_scores_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
+        lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
+        lib.ctcext_stream_scores_validate.restype = ctypes.c_int
+        lib.ctcext_stream_scores_validate_chunk.argtypes = [ctypes.POINTER(StreamArgs),
+                                                            ctypes.POINTER(StreamScoresArgs), ctypes.POINTER(Chunk)]
+        lib.ctcext_stream_scores_validate_chunk.restype = ctypes.c_int
+        lib.ctcext_stream_scores_bytes.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
+        lib.ctcext_stream_scores_bytes.restype = ctypes.c_int64
+        # (decoder, args, skip args or NULL, scores args, ctcext_stream**)
+        lib.ctcext_stream_open_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(StreamArgs),
+                                                  ctypes.POINTER(SkipArgs), ctypes.POINTER(StreamScoresArgs),
+                                                  ctypes.POINTER(ctypes.c_void_p)]
+        lib.ctcext_stream_open_scores.restype = ctypes.c_int
+        lib.ctcext_stream_token_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(TokenTimesOut),
+                                                   ctypes.POINTER(TokenScoresOut)]
+        lib.ctcext_stream_token_scores.restype = ctypes.c_int
+        lib.ctcext_stream_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_stream_scores_ms.restype = ctypes.c_int
     _lib = lib
     return lib
 

@@ -958,13 +958,36 @@ class StreamDecoder:
     skipping decode of everything pushed so far; ``frames``, ``stable()`` and
     the token times stay on the original time axis.  Such a stream takes CUDA
     chunks through ``push_dense`` only: ``push`` raises ``UnimplementedError``.
+
+    ``token_scores=True`` gives the stream a score store (include/ctcext.h,
+    "Streaming: token scores"): the logits and the normaliser of every frame
+    committed since an item's last reset stay on the device, and
+    ``token_scores_dense()`` returns the per-token confidences after any
+    ``push_dense``.  ``score_store`` is the store's element type: None keeps
+    the compute dtype and takes chunks of any accepted dtype; ``"bfloat16"`` or
+    ``"float16"`` (float32 streams) halves the store and takes chunks of that
+    dtype only.  The store is ``batch_size * max_frames * (num_classes * esize
+    + sizeof(dtype))`` bytes, allocated when the stream opens.  Such a stream
+    takes CUDA chunks through ``push_dense`` only as well.
     """
 
     def __init__(self, batch_size, num_classes, beam_width, top_paths, max_frames, *,
                  dtype="float32", merge_repeated=False, blank_index=0, blank_label=-1,
-                 device=None, scorer_table=None, flags=0, skip_blank=None):
+                 device=None, scorer_table=None, flags=0, skip_blank=None, token_scores=False, score_store=None):
         self.lib = _lib.load()
         self._skip = self._kept = None
+        self._scores = None
+        if score_store is not None and not token_scores:
+            raise ValueError("score_store needs token_scores=True")
+        if token_scores:
+            if not hasattr(self.lib, "ctcext_stream_open_scores"):
+                raise UnimplementedError("this libctcext.so has no token scores for streams "
+                                         "(CTCEXT_HAS_STREAM_SCORES)", _lib.CTCEXT_UNIMPLEMENTED)
+            formats = {None: _lib.CTCEXT_IN_NATIVE, "float16": _lib.CTCEXT_IN_F16, "bfloat16": _lib.CTCEXT_IN_BF16}
+            if score_store not in formats:
+                _type_error("score_store", score_store, "None, float16, bfloat16")
+            self._scores = _lib.StreamScoresArgs()
+            self._scores.store_format = formats[score_store]
         if skip_blank is not None:
             if not hasattr(self.lib, "ctcext_stream_open_skip"):
                 raise UnimplementedError("this libctcext.so has no blank-frame skipping for streams "
@@ -996,6 +1019,9 @@ class StreamDecoder:
         # the attribute checks run on the host now; the stream itself opens
         # with the first push, which fixes where the chunks live
         rc = self.lib.ctcext_stream_validate(ctypes.byref(a))
+        if rc == _lib.CTCEXT_OK and self._scores is not None:
+            a.on_device = 1   # (device chunks only)
+            rc = self.lib.ctcext_stream_scores_validate(ctypes.byref(a), ctypes.byref(self._scores))
         if rc != _lib.CTCEXT_OK:
             _raise(self.lib, rc)
         self._device = _device_index(device)
@@ -1015,14 +1041,19 @@ class StreamDecoder:
         a = self._args
         a.on_device = 1 if on_device else 0
         h = ctypes.c_void_p()
-        if self._skip is None:
+        if self._skip is not None and on_device:
+            # the tensor every push writes its kept counts into, for the stream's life
+            import torch
+            self._kept = torch.zeros((int(a.batch_size),), dtype=torch.int32,
+                                     device=torch.device("cuda", self.dec.device))
+            self._skip.kept = self._kept.data_ptr()
+        if self._scores is not None:
+            rc = self.lib.ctcext_stream_open_scores(self.dec.handle, ctypes.byref(a),
+                                                    None if self._skip is None else ctypes.byref(self._skip),
+                                                    ctypes.byref(self._scores), ctypes.byref(h))
+        elif self._skip is None:
             rc = self.lib.ctcext_stream_open(self.dec.handle, ctypes.byref(a), ctypes.byref(h))
         else:
-            if on_device:   # the tensor every push writes its kept counts into, for the stream's life
-                import torch
-                self._kept = torch.zeros((int(a.batch_size),), dtype=torch.int32,
-                                         device=torch.device("cuda", self.dec.device))
-                self._skip.kept = self._kept.data_ptr()
             rc = self.lib.ctcext_stream_open_skip(self.dec.handle, ctypes.byref(a), ctypes.byref(self._skip),
                                                   ctypes.byref(h))
         if rc != _lib.CTCEXT_OK:
@@ -1154,6 +1185,9 @@ class StreamDecoder:
         if self._skip is not None:   # (the library's own answer and message; nothing is opened or touched)
             raise UnimplementedError("a skipping stream has no synchronous push: use ctcext_stream_push_dense",
                                      _lib.CTCEXT_UNIMPLEMENTED)
+        if self._scores is not None:   # (likewise)
+            raise UnimplementedError("a stream with a score store has no synchronous push: use "
+                                     "ctcext_stream_push_dense", _lib.CTCEXT_UNIMPLEMENTED)
         lib = self.lib
         a = self._args
         c, x, sl, on_device, dev, index = self._chunk(chunk, lengths, batch_first, flags)
@@ -1304,7 +1338,11 @@ class StreamDecoder:
             c.flags |= _lib.CTCEXT_FLAG_DENSE_NULL_STREAM
         if not self.handle:
             a.on_device = 1
-            rc = lib.ctcext_stream_dense_validate(ctypes.byref(a), ctypes.byref(c), None)
+            if self._scores is None:
+                rc = lib.ctcext_stream_dense_validate(ctypes.byref(a), ctypes.byref(c), None)
+            else:
+                rc = lib.ctcext_stream_scores_validate_chunk(ctypes.byref(a), ctypes.byref(self._scores),
+                                                             ctypes.byref(c))
             if rc != _lib.CTCEXT_OK:
                 _raise(lib, rc)
             self._open(True, index)
@@ -1351,6 +1389,65 @@ class StreamDecoder:
         if rc != _lib.CTCEXT_OK:
             _raise(lib, rc)
         return out
+
+    def token_scores_dense(self, times=None):
+        """``dense_token_scores`` for the last ``push_dense`` with results of a
+        ``token_scores=True`` stream: ``TokenScores(logp_sum, logp_min)`` of
+        everything pushed so far, CUDA tensors of the compute dtype
+        ``[B, top_paths, max_frames]``, NaN everywhere but the timed tokens,
+        enqueued behind that push on its stream (so the push, the times and
+        the scores can be captured together).  ``times`` is what
+        ``token_times_dense()`` returned for that push; None calls it here.
+        ``FailedPreconditionError`` on a stream without ``token_scores=True``,
+        after a ``results=False`` push or before any ``push_dense``."""
+        self._check_open()
+        lib = self.lib
+        if not hasattr(lib, "ctcext_stream_token_scores"):
+            raise UnimplementedError("this libctcext.so has no token scores for streams "
+                                     "(CTCEXT_HAS_STREAM_SCORES)", _lib.CTCEXT_UNIMPLEMENTED)
+        a = self._args
+        if self._scores is None:
+            raise FailedPreconditionError(
+                "ctcext_stream_token_scores on a stream without a score store (ctcext_stream_open_scores)",
+                _lib.CTCEXT_FAILED_PRECONDITION)
+        if not self.handle:
+            raise FailedPreconditionError(
+                "ctcext_stream_token_scores without a ctcext_stream_push_dense that had hypothesis outputs",
+                _lib.CTCEXT_FAILED_PRECONDITION)
+        import torch
+        dev = torch.device("cuda", self.dec.device)
+        B, P, F = int(a.batch_size), int(a.top_paths), int(a.max_frames)
+        if times is None:
+            times = self.token_times_dense()
+        for name, v in (("start", times.start), ("end", times.end)):
+            if not (_is_torch(v) and v.is_cuda and v.device == dev and tuple(v.shape) == (B, P, F)
+                    and str(v.dtype) == "torch.int32" and v.is_contiguous()):
+                raise ValueError("times.%s must be a contiguous int32 tensor of shape %s on %s" % (name, (B, P, F), dev))
+        t = _lib.TokenTimesOut()
+        t.start, t.end = times.start.data_ptr(), times.end.data_ptr()
+        out, o = _scores_device(dev, B, P, F, torch.float32 if a.dtype == _lib.CTCEXT_F32 else torch.float64)
+        rc = lib.ctcext_stream_token_scores(self.handle, ctypes.byref(t), ctypes.byref(o))
+        if rc != _lib.CTCEXT_OK:
+            _raise(lib, rc)
+        return out
+
+    def scores_ms(self):
+        """Diagnostics: ``(append_ms, scores_ms)``, the times of the score
+        store's append kernel in the last ``flags=CTCEXT_FLAG_PROFILE``
+        ``push_dense`` and of the ``token_scores_dense`` kernel behind it (0
+        where there was none).  Waits."""
+        self._check_open()
+        if not hasattr(self.lib, "ctcext_stream_scores_ms"):
+            raise UnimplementedError("this libctcext.so has no token scores for streams "
+                                     "(CTCEXT_HAS_STREAM_SCORES)", _lib.CTCEXT_UNIMPLEMENTED)
+        if not self.handle:
+            raise FailedPreconditionError("no CTCEXT_FLAG_PROFILE enqueue-only push on this stream yet",
+                                          _lib.CTCEXT_FAILED_PRECONDITION)
+        a_ms, s_ms = ctypes.c_double(), ctypes.c_double()
+        rc = self.lib.ctcext_stream_scores_ms(self.handle, ctypes.byref(a_ms), ctypes.byref(s_ms))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        return a_ms.value, s_ms.value
 
     def token_times_ms(self):
         """Diagnostics: the token-times kernel's time in ms of the last

@@ -908,11 +908,11 @@ int ctcext_skip_plan_chunk_row(const void* logp_blank, int32_t f64, int64_t n, d
  * the workspace).  That memory must still be there, unchanged, when the kernel
  * runs; the library keeps no copy.
  *
- * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED), and
- * streams.  A push keeps neither its chunk nor its normaliser, and an
- * alignment can move to any class at any earlier frame, so a stream would need
- * a per-frame posterior store with the commit's roll-back rules; there is no
- * stream entry point. */
+ * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED).  A
+ * stream's push keeps neither its chunk nor its normaliser, and an alignment
+ * can move to any class at any earlier frame, so these entry points do not
+ * follow a push; a stream opened with a score store has its own
+ * ("Streaming: token scores", below). */
 #define CTCEXT_HAS_TOKEN_SCORES 1
 
 /* Device pointers, [batch][top_paths][max_time] of the compute dtype.  Either
@@ -953,6 +953,108 @@ int ctcext_token_scores_row(const void* x, const void* norm, int32_t f64, int64_
 /* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
  * last token-scores kernel of a dense call in ms.  Waits for it. */
 int ctcext_dense_token_scores_ms(ctcext_decoder* dec, double* ms);
+
+/* ---------------------------------------------------------------------------
+ * Streaming: token scores.  A stream opened with ctcext_stream_open_scores
+ * keeps, on the device, the logits and the normaliser of every frame it has
+ * committed, and ctcext_stream_token_scores applies the definition of "Token
+ * scores" to them after any enqueue-only push.  Opt-in: a stream opened with
+ * ctcext_stream_open or ctcext_stream_open_skip allocates nothing more and
+ * does exactly what it did (CTCEXT_ABI_VERSION and every existing struct are
+ * unchanged; detect the entry points by CTCEXT_HAS_STREAM_SCORES at build
+ * time or by symbol at run time).
+ *
+ * Definition.  After a push, for item b: "Token scores" with
+ *   frames      the item's frames since its last reset (the push's frames[b]),
+ *   x, norm     the rows of every chunk committed to the item since that reset,
+ *               in order, widened exactly to ftype, and the decoder's
+ *               normaliser of each row,
+ *   ali, start, end   of this push (ctcext_stream_token_times),
+ * and width max_frames.  That is what the one-shot calls give for the
+ * concatenated logits.  On a skipping stream it applies as after a skipping
+ * decode: on the original time axis, to the expanded alignment, the caller's
+ * rows -- dropped frames included -- and the normaliser of the caller's rows.
+ *
+ * The store.  Two buffers for the stream's life, allocated at open:
+ *   sx     [batch][max_frames][num_classes], the rows on the original time
+ *          axis, frame 0 being the item's first since its last reset;
+ *   snorm  [max_frames][batch] of ftype.
+ * store_format is sx's element type.  CTCEXT_IN_NATIVE: ftype; a chunk may have
+ * any format the stream accepts, another one every push, and is widened
+ * exactly on the way in.  CTCEXT_IN_F16 / CTCEXT_IN_BF16 (float32 streams
+ * only): two bytes per element, and every chunk must have that inputs_format
+ * (checked on the host before anything is enqueued: CTCEXT_INVALID_ARGUMENT
+ * "chunk inputs_format differs from the stream's score store format", the
+ * stream as it was).  Cost:
+ *   batch * max_frames * (num_classes * esize + sizeof(ftype)) bytes
+ * (ctcext_stream_scores_bytes) -- at batch 256, max_frames 1500,
+ * num_classes 29: 46.1 MB native, 23.8 MB in bf16.
+ *
+ * A push with chunk_time > 0 enqueues one more kernel, behind the prologue and
+ * the normaliser of the caller's rows and in front of the commit: for item b
+ * it copies the chunk_length[b] rows the push takes from the caller's chunk
+ * (through chunk->inputs, its format and strides) to sx[b][base ..], and their
+ * normaliser to snorm[base ..][b], base being the item's frames before the
+ * push.  An item with _LENGTH or _CAPACITY copies nothing.
+ *
+ * Roll-back is by position, not by undo.  The append reads base from committed
+ * state and the commit runs behind it, so an item whose push does not commit
+ * (a helper hand-over timeout, _LENGTH, _CAPACITY) keeps its base, and its next
+ * push writes the same rows again.  Rows at or above an item's frames are
+ * never read: the scores kernel reads inside [0, frames) only.  The prologue's
+ * capacity check gives base + chunk_length[b] <= max_frames, so nothing is
+ * written outside the item's slab.  reset[b] and ctcext_stream_reset put base
+ * to 0: the next push appends at frame 0.
+ *
+ * Such a stream takes device chunks through ctcext_stream_push_dense alone:
+ * ctcext_stream_push answers CTCEXT_UNIMPLEMENTED and leaves the stream as it
+ * was.  _reserve, _check, _frames, _kept, _reset, _stable and _token_times are
+ * unchanged, and a push still allocates nothing after a reserve.
+ *
+ * Not covered: handles of more than one device (CTCEXT_UNIMPLEMENTED); host
+ * chunks and the synchronous push; any mean or exponential of the scores (the
+ * caller's one elementwise op); stability -- like the token times, the scores
+ * of tokens ctcext_stream_stable calls final can still move, because the best
+ * alignment can. */
+#define CTCEXT_HAS_STREAM_SCORES 1
+
+typedef struct {
+  int32_t store_format;   /* CTCEXT_IN_NATIVE, CTCEXT_IN_F16 or CTCEXT_IN_BF16 */
+  int32_t pad_;
+} ctcext_stream_scores_args;
+
+/* Host only, no HIP call: ctcext_stream_validate, then (CTCEXT_INVALID_ARGUMENT)
+ *   "store_format must be CTCEXT_IN_NATIVE, CTCEXT_IN_F16 or CTCEXT_IN_BF16"
+ *   "a half-precision score store needs dtype float32"
+ *   "a stream with a score store needs device chunks (on_device == 1): it has the enqueue-only push alone"
+ * and the blank_label rule of ctcext_token_times_validate, with its message. */
+int ctcext_stream_scores_validate(const ctcext_stream_args* args, const ctcext_stream_scores_args* scores);
+/* Host only: the above, ctcext_stream_dense_validate's chunk checks, and the
+ * chunk's format against a half store. */
+int ctcext_stream_scores_validate_chunk(const ctcext_stream_args* args, const ctcext_stream_scores_args* scores,
+                                        const ctcext_chunk* chunk);
+/* Host only: the store's size in bytes (the formula above); -1 where
+ * ctcext_stream_scores_validate fails or the size leaves int64. */
+int64_t ctcext_stream_scores_bytes(const ctcext_stream_args* args, const ctcext_stream_scores_args* scores);
+/* ctcext_stream_open with the store.  skip may be NULL (no blank-frame
+ * skipping); otherwise as ctcext_stream_open_skip.  A handle of more than one
+ * device: CTCEXT_UNIMPLEMENTED. */
+int ctcext_stream_open_scores(ctcext_decoder* dec, const ctcext_stream_args* args, const ctcext_skip_args* skip,
+                              const ctcext_stream_scores_args* scores, ctcext_stream** out);
+/* Enqueues the token-scores kernel on the stream of the last
+ * ctcext_stream_push_dense, over the stream's own walks and its store.
+ * times->start / times->end are what ctcext_stream_token_times wrote for the
+ * same push (both required; nothing in them is trusted).  out's rows are
+ * [batch][top_paths][max_frames] of ftype, NaN everywhere but the timed
+ * tokens.  No allocation, no host-blocking call, no device-to-host copy;
+ * capturable together with the push and the times.
+ * CTCEXT_FAILED_PRECONDITION on a stream opened without a store, after a push
+ * without hypothesis outputs, and before any enqueue-only push. */
+int ctcext_stream_token_scores(ctcext_stream* s, const ctcext_token_times* times, const ctcext_token_scores* out);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the chunk's flags, the times in ms
+ * of the last push's append kernel and of the last token-scores kernel behind
+ * it (0 where that push had none).  Waits for them. */
+int ctcext_stream_scores_ms(ctcext_stream* s, double* append_ms, double* scores_ms);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,16 @@ calls, the wall time from the first call to the last outputs complete (the
 synchronous rows' summed push times are wall times too: every push waits), and
 the commit kernel's summed time from a CTCEXT_FLAG_PROFILE run of its own.
 
-    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense [--times]] [--input gaussian|peaky|twohot] [--out FILE]
+With --dense --scores every schedule is also run through a stream with a score
+store (StreamDecoder(token_scores=True)), alternating round by round with the
+same schedule on a stream without one, in the same session: the wall times of
+both; from a CTCEXT_FLAG_PROFILE run of their own the append kernel's time per
+push beside the commit kernel's of the same pushes; and the token-scores
+kernel's time over the store after the last push beside the one-shot
+dense_token_scores over the caller's tensor for the same rows.  --score-store
+chooses the store's element type (the chunks are converted to it beforehand).
+
+    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense [--times] [--scores [--score-store bfloat16]]] [--input gaussian|peaky|twohot] [--out FILE]
 
 Prints one table and one JSON line.  It is a report, not a check, and it does
 not touch bench.py.
@@ -97,7 +106,7 @@ def streamed(x, chunk, stable=False, info=None):
     return ms, out, kernel
 
 
-def streamed_dense(x, chunk, every, profile=False):
+def streamed_dense(x, chunk, every, profile=False, **stream_kw):
     """The same schedule through push_dense: (host ms inside the calls, wall ms
     from the first call to the last outputs complete, the last push's outputs,
     summed commit-kernel ms of a CTCEXT_FLAG_PROFILE run).  every: hypothesis
@@ -105,7 +114,7 @@ def streamed_dense(x, chunk, every, profile=False):
     checks after each push to read that push's events: its wall time is not a
     measurement."""
     flags = _lib.CTCEXT_FLAG_PROFILE if profile else 0
-    with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", **KW) as s:
+    with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", **KW, **stream_kw) as s:
         s.reserve(chunk)   # opens the stream: its allocations are not timed
         torch.cuda.synchronize()
         host = commit = 0.0
@@ -172,6 +181,74 @@ def streamed_times(x, chunk):
             per.append((s.token_times_ms(), rest,
                         st["norm_kernel_ms"] + st["decode_kernel_ms"] + s.commit_ms() + rest))
     return per, out, tt
+
+
+def streamed_scores_profile(x, chunk, store):
+    """One CTCEXT_FLAG_PROFILE run of the schedule on a stream with a score
+    store, checked after each push to read its events: per push (append kernel
+    ms, commit kernel ms), and the token-scores kernel's ms over the store after
+    the last push (rows of T frames)."""
+    per = []
+    with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", token_scores=True, score_store=store, **KW) as s:
+        s.reserve(chunk)
+        for t0 in range(0, T, chunk):
+            t1 = min(t0 + chunk, T)
+            s.push_dense(x[t0:t1], batch_first=False, results=t1 == T, flags=_lib.CTCEXT_FLAG_PROFILE)
+            if t1 == T:
+                s.token_scores_dense()
+            s.check()
+            append_ms, scores_ms = s.scores_ms()
+            per.append((append_ms, s.commit_ms()))
+    return per, scores_ms
+
+
+def one_shot_scores_ms(x, sl):
+    """The token-scores kernel's ms of the one-shot dense decode of the same rows."""
+    import ctypes
+    ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, token_scores=True, flags=_lib.CTCEXT_FLAG_PROFILE, **KW)
+    ctcext_amd.dense_token_scores()
+    ctcext_amd.dense_check()
+    dec = ctcext_amd.get_decoder(0)
+    ms = ctypes.c_double()
+    if dec.lib.ctcext_dense_token_scores_ms(dec.handle, ctypes.byref(ms)) != _lib.CTCEXT_OK:
+        raise SystemExit("ctcext_dense_token_scores_ms: %s" % dec.lib.ctcext_last_error().decode())
+    return ms.value
+
+
+def scores_rows(x, sl, chunks, runs, store):
+    """--scores: per chunk size, the schedule with and without a score store in
+    alternating rounds, and the kernels' times of a profile run per round."""
+    xs = x if store is None else x.to(getattr(torch, store))
+    ref = ctcext_amd.decode_dense(xs, sl, W, P, batch_first=False, **KW)
+    torch.cuda.synchronize()
+    med = statistics.median
+    rows = {}
+    for c in chunks:
+        if c >= T:
+            continue
+        kw = dict(token_scores=True, score_store=store)
+        for fn_kw in ({}, kw):   # warm-up, and the results are the one-shot decode's
+            out = streamed_dense(xs, c, False, **fn_kw)[2]
+            if not all(torch.equal(a, b) for a, b in zip(out[:5], ref[:5])):
+                raise SystemExit("%d-frame pushes: the result differs from the one-shot decode_dense" % c)
+        plain, with_store, append, commit, scores, dense = [], [], [], [], [], []
+        for _ in range(runs):
+            plain.append(streamed_dense(xs, c, False)[1])
+            with_store.append(streamed_dense(xs, c, False, **kw)[1])
+            per, sc_ms = streamed_scores_profile(xs, c, store)
+            append.append(med(p[0] for p in per))
+            commit.append(med(p[1] for p in per))
+            scores.append(sc_ms)
+            dense.append(one_shot_scores_ms(xs, sl))
+        n = -(-T // c)
+        rows["%d-frame pushes" % c] = {
+            "pushes": n, "wall_ms": round(med(plain), 3), "wall_store_ms": round(med(with_store), 3),
+            "wall_rounds_ms": [round(v, 3) for v in plain], "wall_store_rounds_ms": [round(v, 3) for v in with_store],
+            "store_ms_per_push": round((med(with_store) - med(plain)) / n, 4),
+            "append_kernel_ms_per_push": round(med(append), 4), "commit_kernel_ms_per_push": round(med(commit), 4),
+            "append_over_commit": round(med(append) / med(commit), 3) if med(commit) > 0 else None,
+            "scores_kernel_ms": round(med(scores), 4), "one_shot_scores_kernel_ms": round(med(dense), 4)}
+    return rows
 
 
 def times_row(x, chunk, runs):
@@ -245,9 +322,18 @@ def main():
     ap.add_argument("--input", default="gaussian", help="gaussian (the bench's logits), peaky or twohot")
     ap.add_argument("--times", action="store_true",
                     help="with --dense: a row for token_times_dense() after every push of the smallest chunk size")
+    ap.add_argument("--scores", action="store_true",
+                    help="with --dense: each multi-push schedule with and without a score store, and its kernels' times")
+    ap.add_argument("--score-store", default=None, help="with --scores: bfloat16 or float16 (default: the compute dtype)")
     ap.add_argument("--out", default=None, help="also write the table and the JSON line here")
     args = ap.parse_args()
     chunks = [int(c) for c in args.chunks.split(",")]
+    if args.scores and not args.dense:
+        raise SystemExit("--scores needs --dense: a stream with a score store has the enqueue-only push alone")
+    if args.scores and not hasattr(_lib.load(), "ctcext_stream_open_scores"):
+        raise SystemExit("--scores: this libctcext.so has no token scores for streams (CTCEXT_HAS_STREAM_SCORES)")
+    if args.score_store and not args.scores:
+        raise SystemExit("--score-store needs --scores")
     x = make_input(args.input)
     with_stable = args.stable and hasattr(_lib.load(), "ctcext_stream_stable")
     sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
@@ -307,6 +393,19 @@ def main():
                                                               tr[k]["token_times_ms"], tr[k]["traceback_pack_ms"],
                                                               tr[k]["push_kernels_ms"]))
             res["times_row"] = tr
+        if args.scores and hasattr(_lib.load(), "ctcext_stream_open_scores"):
+            sr = scores_rows(x, sl, chunks, args.runs, args.score_store)
+            store = args.score_store or "native"
+            lines.append("score store (%s, %.1f MB), %d alternating rounds; medians, ms"
+                         % (store, B * T * (C * (2 if args.score_store else 4) + 4) / 1e6, args.runs))
+            lines.append("  %-18s %9s %11s %10s %11s %11s %8s %12s %14s" % ("", "wall", "wall+store", "per push", "append/push",
+                                                                         "commit/push", "ratio", "scores (T)", "one-shot scores"))
+            for name, v in sr.items():
+                lines.append("  %-18s %9.2f %11.2f %+10.4f %11.4f %11.4f %8s %12.4f %14.4f"
+                             % (name, v["wall_ms"], v["wall_store_ms"], v["store_ms_per_push"], v["append_kernel_ms_per_push"],
+                                v["commit_kernel_ms_per_push"], v["append_over_commit"], v["scores_kernel_ms"],
+                                v["one_shot_scores_kernel_ms"]))
+            res["scores_rows"] = {"store": store, "rows": sr}
     text = "\n".join(lines) + "\n" + json.dumps(res)
     print(text)
     if args.out:

@@ -9,7 +9,7 @@ arch=${2:-gfx950}
 llvm=${ROCM_PATH:-/opt/rocm}/llvm/bin
 tmp=$(mktemp -d)
 trap 'rm -rf "$tmp"' EXIT
-for o in "$dir"/ctcx_decode.*.o "$dir"/ctcx_decode_gs.o "$dir"/ctcx_stable.o "$dir"/ctcx_stream_dense.o "$dir"/ctcx_times.o "$dir"/ctcx_skip.o "$dir"/ctcx_scores.o; do
+for o in "$dir"/ctcx_decode.*.o "$dir"/ctcx_decode_gs.o "$dir"/ctcx_stable.o "$dir"/ctcx_stream_dense.o "$dir"/ctcx_times.o "$dir"/ctcx_skip.o "$dir"/ctcx_scores.o "$dir"/ctcx_stream_store.o; do
   [ -e "$o" ] || continue   # (build/st has the decode objects only; older builds lack the later units)
   n=$(basename "$o")
   "$llvm"/llvm-objcopy -O binary --only-section=.hip_fatbin "$o" "$tmp/fat.bin"
