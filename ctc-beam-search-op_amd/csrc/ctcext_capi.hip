@@ -21,6 +21,7 @@
 #include "../../include/ctcext.h"
 #define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
+#include "ctcx_paths.h"
 #include "ctcx_scores.h"
 #include "ctcx_skip.h"
 #include "ctcx_stable.h"
@@ -163,8 +164,9 @@ struct Dev {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t s = nullptr;   // stream of the current call
-  hipEvent_t ev[9] = {};     // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
-                             // [5], [6] around the token-times kernel of a dense call, [7], [8] the token-scores kernel
+  hipEvent_t ev[11] = {};    // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
+                             // [5], [6] around the token-times kernel of a dense call, [7], [8] the token-scores kernel,
+                             // [9], [10] the path-scores kernels
   hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
@@ -216,6 +218,7 @@ struct ctcext_decoder {
     bool skip = false;          // it was a ctcext_decode_dense_skip
     ScoreSrc sc;                // what ctcext_dense_token_scores reads beside that
     bool scores_timed = false;  // events [7], [8] were recorded
+    bool paths_timed = false;   // events [9], [10] were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -229,7 +232,7 @@ struct ctcext_decoder {
   // ctcext_decode_skip (a stream's push leaves nothing to score), with the
   // staging of its outputs
   ScoreSrc ss;
-  DevBuf sc_sum, sc_min;
+  DevBuf sc_sum, sc_min, ps_out;   // (ps_out: ctcext_fetch_path_scores')
   // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
   // the plan, and what the call that is running reads of it
   struct {
@@ -319,7 +322,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
+                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
   d->h_res.release();
@@ -1401,6 +1404,7 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   // and the normaliser over them: the plan's with skipping, the pre-pass's else
   d->dense.sc = ScoreSrc{};
   d->dense.scores_timed = false;
+  d->dense.paths_timed = false;
   if (a->batch_size > 0) {
     ScoreSrc& q = d->dense.sc;
     q.x = a->inputs;
@@ -3227,6 +3231,159 @@ extern "C" int ctcext_stream_scores_ms(ctcext_stream* st, double* append_ms, dou
     HIP_OR_FAIL(hipEventElapsedTime(&f, st->sc.ev[2], st->sc.ev[3]));
     *scores_ms = f;
   }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Path scores (ctcext.h, "Path scores"): ctcx_paths.hip's kernels over the
+// decoded walks the traceback left in the workspace, the normaliser and the
+// logits the decode read (ScoreSrc); a stream's over its own walks and its
+// score store.
+
+// CTCEXT_PATHS_LDS=1 (diagnostics; read at every call): every row runs in the
+// LDS instantiation, whatever its length
+static int32_t paths_force_lds_from_env() {
+  const char* v = getenv("CTCEXT_PATHS_LDS");
+  return (v && v[0] == '1') ? 1 : 0;
+}
+
+// The widths the LDS instantiation cannot hold are refused before any launch.
+static int check_paths_width(const CtcxPathsParams& p) {
+  if (!ctcx_path_scores_fits(p.Tmax, p.f64, p.force_lds))
+    return fail(CTCEXT_UNIMPLEMENTED, "path scores: rows this wide do not fit the LDS trellis");
+  return CTCEXT_OK;
+}
+
+static void paths_params(CtcxPathsParams& p, const int32_t* seq, const int32_t* len, const ScoreSrc& q, int64_t T_,
+                         int64_t B, int64_t C, int P, int32_t blank_index) {
+  p.seq = seq;
+  p.len = len;
+  p.x = q.x;
+  p.norm = q.norm;
+  p.Tmax = T_; p.B = B; p.C = C; p.xst_t = q.st_t; p.xst_b = q.st_b;
+  p.P = P; p.xfmt = q.xfmt; p.f64 = q.f64 ? 1 : 0;
+  p.blank_index = blank_index;
+  p.force_lds = paths_force_lds_from_env();
+}
+
+extern "C" int ctcext_dense_path_scores(ctcext_decoder* d, void* path_logp) {
+  if (!d || !path_logp) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_path_scores without a ctcext_decode_dense");
+  int rc = ctcext_token_times_validate(d->dense.C, d->dense.blank_index, d->dense.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (d->dense.B == 0) return CTCEXT_OK;
+  if (!d->dense.sc.have) return fail(CTCEXT_INTERNAL, "path scores: the inputs of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  CtcxPathsParams p{};
+  paths_params(p, (const int32_t*)root.seq.p, (const int32_t*)root.len.p, d->dense.sc, d->dense.T, B, d->dense.C,
+               d->dense.P, d->dense.blank_index);
+  p.frames = (const int32_t*)root.dsl.p;
+  p.status = (const int32_t*)root.dstat.p + B;
+  p.path_logp = path_logp;
+  rc = check_paths_width(p);
+  if (rc != CTCEXT_OK) return rc;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[9], s));
+  HIP_OR_FAIL(ctcx_launch_path_scores(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.ev[10], s));
+    d->dense.paths_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_fetch_path_scores(ctcext_decoder* d, void* path_logp, int32_t outputs_on_device) {
+  if (!d || !path_logp) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_fetch_path_scores without a successful ctcext_decode");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "path scores need a one-device decoder handle");
+  int rc = ctcext_token_times_validate(d->tt.C, d->tt.blank_index, d->tt.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  const int64_t B = d->B, T_ = d->T;
+  const int P = d->P;
+  if (B == 0) return CTCEXT_OK;
+  if (!d->ss.have)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_fetch_path_scores after a stream's push: a stream keeps no logits to score");
+  if ((int64_t)d->tt.frames.size() != B)
+    return fail(CTCEXT_INTERNAL, "path scores: the frame counts of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.s;
+  const size_t bytes = (size_t)(B * P) * (d->ss.f64 ? 8 : 4);
+  CtcxPathsParams p{};
+  paths_params(p, (const int32_t*)root.seq.p, (const int32_t*)root.len.p, d->ss, T_, B, d->tt.C, P, d->tt.blank_index);
+  rc = check_paths_width(p);
+  if (rc != CTCEXT_OK) return rc;
+  HIP_OR_FAIL(d->tt_frames.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(hipMemcpyAsync(d->tt_frames.p, d->tt.frames.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  p.frames = (const int32_t*)d->tt_frames.p;
+  p.status = nullptr;   // (a synchronous call with a failing item has failed as a whole)
+  if (outputs_on_device) {
+    p.path_logp = path_logp;
+  } else {
+    HIP_OR_FAIL(d->ps_out.ensure(bytes + 16));
+    p.path_logp = d->ps_out.p;
+  }
+  HIP_OR_FAIL(ctcx_launch_path_scores(p, s));
+  if (!outputs_on_device) HIP_OR_FAIL(hipMemcpyAsync(path_logp, p.path_logp, bytes, hipMemcpyDeviceToHost, s));
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_path_scores_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.paths_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no path scores of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.ev[10]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[9], root.ev[10]));
+  *ms = f;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_stream_path_scores(ctcext_stream* st, void* path_logp) {
+  if (!st || !path_logp) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  auto& n = st->dn;
+  const ctcext_stream_args& a = st->a;
+  if (!st->sc.on)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_stream_path_scores on a stream without a score store (ctcext_stream_open_scores)");
+  if (a.batch_size > 0 && (!n.used || !n.results))
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_stream_path_scores without a ctcext_stream_push_dense that had hypothesis outputs");
+  int rc = ctcext_token_times_validate(a.num_classes, a.blank_index, a.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (a.batch_size == 0) return CTCEXT_OK;
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(st->dec->devs[0].device));
+  ScoreSrc q;
+  q.x = st->sc.sx;
+  q.xfmt = st->sc.fmt;
+  q.st_t = a.num_classes; q.st_b = a.max_frames * a.num_classes;
+  q.norm = st->sc.snorm;
+  q.f64 = a.dtype == CTCEXT_F64;
+  CtcxPathsParams p{};
+  paths_params(p, (const int32_t*)n.seq.p, (const int32_t*)n.len.p, q, a.max_frames, a.batch_size, a.num_classes,
+               a.top_paths, a.blank_index);
+  p.frames = st->sk.on ? (const int32_t*)st->sk.nfr.p : (const int32_t*)st->cum;
+  p.status = (const int32_t*)n.fin.p;
+  p.path_logp = path_logp;
+  rc = check_paths_width(p);
+  if (rc != CTCEXT_OK) return rc;
+  HIP_OR_FAIL(ctcx_launch_path_scores(p, n.s));
   g_err.clear();
   return CTCEXT_OK;
 }

@@ -76,6 +76,10 @@ STREAM_SCORES_SYMBOLS = ("ctcext_stream_scores_validate", "ctcext_stream_scores_
                          "ctcext_stream_scores_bytes", "ctcext_stream_open_scores", "ctcext_stream_token_scores",
                          "ctcext_stream_scores_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_SCORES_SYMBOLS
+# path scores (CTCEXT_HAS_PATH_SCORES)
+PATH_SCORES_SYMBOLS = ("ctcext_dense_path_scores", "ctcext_fetch_path_scores", "ctcext_stream_path_scores",
+                       "ctcext_path_score_row", "ctcext_dense_path_scores_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PATH_SCORES_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -379,6 +383,19 @@ def load():
         lib.ctcext_token_scores_row.restype = ctypes.c_int
         lib.ctcext_dense_token_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_token_scores_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_path_scores"):   # (CTCEXT_HAS_PATH_SCORES; older builds stay loadable for A/B runs)
+        lib.ctcext_dense_path_scores.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.ctcext_dense_path_scores.restype = ctypes.c_int
+        lib.ctcext_fetch_path_scores.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+        lib.ctcext_fetch_path_scores.restype = ctypes.c_int
+        lib.ctcext_stream_path_scores.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.ctcext_stream_path_scores.restype = ctypes.c_int
+        lib.ctcext_path_score_row.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                              ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]
+        lib.ctcext_path_score_row.restype = ctypes.c_int
+        lib.ctcext_dense_path_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_path_scores_ms.restype = ctypes.c_int
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

@@ -751,6 +751,106 @@ def token_scores_row(x, norm, alignment, frames, start, end, blank_index, blank_
     return lsum, lmin
 
 
+def _paths_lib(lib):
+    if not hasattr(lib, "ctcext_dense_path_scores"):
+        raise UnimplementedError("this libctcext.so has no path scores (CTCEXT_HAS_PATH_SCORES)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+_NO_PATHS = "path scores need a decode with token_scores=True"
+
+
+def dense_path_scores(device=None):
+    """How sure the decoder is of every whole hypothesis of the calling
+    thread's last ``decode_dense(..., token_scores=True)`` on ``device`` (None:
+    the current one), without waiting for anything: the exact CTC
+    log-likelihood ``log p(y | x)`` of each returned label row over all of the
+    item's frames, by the forward recursion on the device, enqueued behind the
+    decode on the stream the decode went to (so it can be captured into the
+    same ``torch.cuda.graph``).
+
+    Returns a CUDA tensor ``[B, top_paths]`` of the compute dtype.  Unlike
+    ``log_probability`` it does not depend on ``beam_width``, and after
+    ``skip_blank`` it covers the dropped frames too.  An infeasible row is
+    ``-inf``; every row of an item with a status bit is NaN.  The definition
+    is in ``include/ctcext.h``, "Path scores"; the ``blank_label`` rule of the
+    token times applies."""
+    what = "ctcext_dense_path_scores without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = _paths_lib(dec.lib)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_PATHS, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    import torch
+    with torch.cuda.device(dev):
+        out = torch.empty((B, P), dtype=fdt, device=dev)
+    rc = lib.ctcext_dense_path_scores(dec.handle, out.data_ptr())
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def path_scores(device=None):
+    """``dense_path_scores`` for the synchronous calls: the path scores of the
+    hypotheses the calling thread's last ``ctc_ext_beam_search_decoder`` or
+    ``decode_logits`` with ``token_scores=True`` on ``device`` returned (not
+    after a stream's push).  Waits.  Returns a numpy array ``[B, top_paths]``,
+    or a CUDA tensor where that call's outputs were."""
+    what = "ctcext_fetch_path_scores without a successful ctcext_decode"
+    dec = _thread_decoder(device, what)
+    lib = _paths_lib(dec.lib)
+    if getattr(dec, "_times_sync", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_sync", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_PATHS, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, to_device, f64 = shape
+    if to_device:
+        import torch
+        dev = torch.device("cuda", dec.device)
+        with torch.cuda.device(dev):
+            out = torch.empty((B, P), dtype=torch.float64 if f64 else torch.float32, device=dev)
+        ptr = out.data_ptr()
+    else:
+        out = np.empty((B, P), np.float64 if f64 else np.float32)
+        ptr = out.ctypes.data
+    rc = lib.ctcext_fetch_path_scores(dec.handle, ptr, 1 if to_device else 0)
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def path_score_row(x, norm, decoded, frames, blank_index, blank_label=-1):
+    """The definition of the path score for one row, on the host (no GPU), in
+    long double: ``x`` is one item's logits ``[frames, num_classes]`` (float32
+    or float64, the compute dtype), ``norm`` its rows' normaliser ``[frames]``,
+    ``decoded`` one path's label row (without padding).  Returns a numpy
+    scalar of ``x``'s dtype."""
+    lib = _paths_lib(_lib.load())
+    x = np.asarray(x)
+    dt = np.float64 if x.dtype == np.float64 else np.float32
+    frames = int(frames)
+    if x.ndim != 2:
+        raise ValueError("path_score_row: x must be [frames, num_classes]")
+    C = int(x.shape[1])
+    x = np.ascontiguousarray(x[:frames], dtype=dt)
+    nm = np.ascontiguousarray(np.asarray(norm).reshape(-1)[:frames], dtype=dt)
+    if x.shape[0] != frames or nm.size != frames:
+        raise ValueError("path_score_row: x and norm must hold the item's frames")
+    y = np.ascontiguousarray(np.asarray(decoded, dtype=np.int64).reshape(-1))
+    out = np.empty((1,), dt)
+    rc = lib.ctcext_path_score_row(x.ctypes.data, nm.ctypes.data, 1 if dt == np.float64 else 0, frames, C,
+                                   _ptr(y, ctypes.c_int64), int(y.size), int(blank_index), int(blank_label),
+                                   out.ctypes.data)
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_path_score_row: bad arguments", rc)
+    return out[0]
+
+
 def kept_frames(device=None):
     """The frames each item kept in the calling thread's last decode with
     ``skip_blank`` on ``device`` (None: the current one): a numpy int32 ``[B]``
@@ -1427,6 +1527,38 @@ class StreamDecoder:
         t.start, t.end = times.start.data_ptr(), times.end.data_ptr()
         out, o = _scores_device(dev, B, P, F, torch.float32 if a.dtype == _lib.CTCEXT_F32 else torch.float64)
         rc = lib.ctcext_stream_token_scores(self.handle, ctypes.byref(t), ctypes.byref(o))
+        if rc != _lib.CTCEXT_OK:
+            _raise(lib, rc)
+        return out
+
+    def path_scores_dense(self):
+        """``dense_path_scores`` for the last ``push_dense`` with results of a
+        ``token_scores=True`` stream: the exact CTC log-likelihood of every
+        hypothesis over everything pushed to its item since the item's last
+        reset, a CUDA tensor ``[B, top_paths]`` of the compute dtype, enqueued
+        behind that push on its stream.  ``FailedPreconditionError`` on a
+        stream without ``token_scores=True``, after a ``results=False`` push
+        or before any ``push_dense``."""
+        self._check_open()
+        lib = self.lib
+        if not hasattr(lib, "ctcext_stream_path_scores"):
+            raise UnimplementedError("this libctcext.so has no path scores (CTCEXT_HAS_PATH_SCORES)",
+                                     _lib.CTCEXT_UNIMPLEMENTED)
+        a = self._args
+        if self._scores is None:
+            raise FailedPreconditionError(
+                "ctcext_stream_path_scores on a stream without a score store (ctcext_stream_open_scores)",
+                _lib.CTCEXT_FAILED_PRECONDITION)
+        if not self.handle:
+            raise FailedPreconditionError(
+                "ctcext_stream_path_scores without a ctcext_stream_push_dense that had hypothesis outputs",
+                _lib.CTCEXT_FAILED_PRECONDITION)
+        import torch
+        dev = torch.device("cuda", self.dec.device)
+        with torch.cuda.device(dev):
+            out = torch.empty((int(a.batch_size), int(a.top_paths)),
+                              dtype=torch.float32 if a.dtype == _lib.CTCEXT_F32 else torch.float64, device=dev)
+        rc = lib.ctcext_stream_path_scores(self.handle, out.data_ptr())
         if rc != _lib.CTCEXT_OK:
             _raise(lib, rc)
         return out

@@ -1056,6 +1056,94 @@ int ctcext_stream_token_scores(ctcext_stream* s, const ctcext_token_times* times
  * it (0 where that push had none).  Waits for them. */
 int ctcext_stream_scores_ms(ctcext_stream* s, double* append_ms, double* scores_ms);
 
+/* ---------------------------------------------------------------------------
+ * Path scores: the exact CTC log-likelihood log p(y | x) of every returned
+ * path, on the device -- how sure the decoder is of the whole hypothesis, and
+ * how its top paths rank under the model itself.  log_probability does not say
+ * that: it sums only the alignments whose prefixes survived in the beam (a
+ * pruned lower bound that depends on beam_width), and after a skipping decode
+ * it is not corrected for the dropped frames.  New entry points only
+ * (CTCEXT_ABI_VERSION is unchanged; detect them by CTCEXT_HAS_PATH_SCORES at
+ * build time or by symbol at run time).
+ *
+ * Definition.  For path p of item b:
+ *
+ * - y[0..m) is the decoded row as the op returns it.  That is walk 0,
+ *   un-reversed, after merge_repeated.
+ * - frames is the item's length.
+ * - lp[f][c] = x[f][c] - norm[f], with x widened exactly as the decode widens
+ *   it and norm the decoder's normaliser (root.norm).  After a skipping call,
+ *   lp is taken over the caller's rows on the original time axis with
+ *   skip.norm, so the score covers every frame, dropped ones included.
+ * - blank = blank_index of the call.
+ * - S = 2m + 1 states with z[2j] = blank and z[2j+1] = y[j].
+ * - alpha_0[0] = lp[0][blank], alpha_0[1] = lp[0][y[0]] when m > 0, and every
+ *   other state is -inf.
+ * - alpha_f[s] = LSE(alpha_{f-1}[s], alpha_{f-1}[s-1], [alpha_{f-1}[s-2] if s
+ *   odd and s >= 3 and z[s] != z[s-2]]) + lp[f][z[s]].
+ * - score = LSE(alpha_{frames-1}[S-1], alpha_{frames-1}[S-2]).
+ *
+ * Conventions:
+ *
+ * - LSE of all -inf is -inf, never NaN.
+ * - frames == 0 gives 0 for m == 0.
+ * - An infeasible row gives -inf.  A row is infeasible when m plus its
+ *   adjacent equal pairs exceeds frames.
+ * - A row of an item with a status bit is NaN.
+ * - A label outside [0, C) makes the row NaN.
+ *
+ * With merge_repeated the row is the merged row and the score is the standard
+ * CTC likelihood of that row; where merging dropped a repeat, the decoder's
+ * own alignment is not among the alignments summed.  The number is well
+ * defined and is what a rescorer of the returned strings wants.
+ *
+ * The output is path_logp [batch][top_paths] of the compute dtype: float32 for
+ * float32, f16 and bf16 inputs, float64 for float64 inputs.  The kernels
+ * evaluate the recursion in that dtype in the log domain (float32 rows are
+ * renormalised every 16 frames, the shift kept in a double), so the value
+ * agrees with the definition evaluated in long double (ctcext_path_score_row)
+ * to within the rounding of the recursion, not bit for bit.
+ *
+ * The logits contract and the blank_label rule of "Token scores" apply
+ * unchanged.  Rows wider than the kernels hold (max_time above 13000, 8000
+ * for float64): CTCEXT_UNIMPLEMENTED.
+ *
+ * Not covered: scoring transcripts the decode did not return; a Viterbi
+ * re-alignment; handles of more than one device (CTCEXT_UNIMPLEMENTED);
+ * scorer-table (bigram) terms -- the score is the acoustic CTC likelihood
+ * only. */
+#define CTCEXT_HAS_PATH_SCORES 1
+
+/* Enqueues the path-scores kernels on the stream of the last
+ * ctcext_decode_dense / ctcext_decode_dense_skip, behind whatever that stream
+ * holds, over that call's rows.  path_logp is a device pointer,
+ * [batch][top_paths] of the compute dtype.  No allocation, no host-blocking
+ * call, no device-to-host copy; capturable into the same graph as the decode.
+ * Without a preceding dense decode: CTCEXT_FAILED_PRECONDITION. */
+int ctcext_dense_path_scores(ctcext_decoder* dec, void* path_logp);
+/* Synchronous; valid after ctcext_decode / ctcext_decode_skip (not after a
+ * stream's push: CTCEXT_FAILED_PRECONDITION).  path_logp is a device pointer
+ * with outputs_on_device, a host pointer without.  One-device handles only:
+ * CTCEXT_UNIMPLEMENTED otherwise. */
+int ctcext_fetch_path_scores(ctcext_decoder* dec, void* path_logp, int32_t outputs_on_device);
+/* The same after a ctcext_stream_push_dense that had hypothesis outputs, over
+ * the stream's own walks and its score store (ctcext_stream_open_scores; the
+ * native and the two-byte stores alike): what the one-shot calls give for the
+ * frames committed since each item's last reset.  Enqueues only, like
+ * ctcext_stream_token_scores, with its CTCEXT_FAILED_PRECONDITION cases. */
+int ctcext_stream_path_scores(ctcext_stream* s, void* path_logp);
+/* Host only, no HIP call: the definition above for one row, evaluated in long
+ * double, in plain C++ that shares no code with the kernels.  x is one item's
+ * rows, dense [frames][num_classes], and norm [frames], both of the compute
+ * dtype (f64: doubles, else floats); decoded holds the row's m labels; score
+ * receives one value of the compute dtype.  blank_label is checked by the
+ * blank_label rule only. */
+int ctcext_path_score_row(const void* x, const void* norm, int32_t f64, int64_t frames, int64_t num_classes,
+                          const int64_t* decoded, int64_t m, int32_t blank_index, int64_t blank_label, void* score);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
+ * last path-scores kernels of a dense call in ms.  Waits for them. */
+int ctcext_dense_path_scores_ms(ctcext_decoder* dec, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,10 @@ same run and the whole call's (events around decode_dense + dense_token_times).
 With --scores, instead: the token-scores kernel (dense_token_scores) on the
 same two inputs, beside the token-times and the pack kernels' of the same run.
 
+With --paths, instead: the path-scores kernels (dense_path_scores) on the same
+two inputs, beside the decode kernel, the whole call, and the token-scores and
+pack kernels of the same run.
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -197,6 +201,52 @@ def scores_report(args):
     return lines, res
 
 
+def paths_report(args):
+    """--paths: one row per input family at cfg3."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    lines = ["%-10s %12s %12s %12s %12s %12s %8s %11s   (median of %d, ms; cfg3 B=%d T=%d C=%d W=%d P=%d)"
+             % ("inputs", "path scores", "token scores", "pack kernel", "decode", "whole call", "ps/dec", "labels/row",
+                args.runs, B, T, C, W, P)]
+    res = {"runs": args.runs, "shape": [B, T, C, W, P], "paths": {}}
+    for kind in ("gaussian", "peaky"):
+        x = times_inputs(kind, T, B, C)
+        ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, token_scores=True, **KW)   # warm-up: workspace, kernels
+        ctcext_amd.dense_token_scores()
+        ctcext_amd.dense_path_scores()
+        ctcext_amd.dense_check()
+        ps_ms, sc_ms, pack_ms, dec_ms, call_ms = [], [], [], [], []
+        for _ in range(args.runs):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE,
+                                          token_scores=True, **KW)
+            ctcext_amd.dense_token_scores()
+            ps = ctcext_amd.dense_path_scores()
+            e1.record()
+            e1.synchronize()
+            dec_ms.append(ctcext_amd.dense_check()["decode_kernel_ms"])
+            ms = ctypes.c_double()
+            for fn, acc in ((dec.lib.ctcext_dense_path_scores_ms, ps_ms), (dec.lib.ctcext_dense_token_scores_ms, sc_ms),
+                            (dec.lib.ctcext_dense_pack_ms, pack_ms)):
+                if fn(dec.handle, ctypes.byref(ms)) != _lib.CTCEXT_OK:
+                    raise SystemExit(dec.lib.ctcext_last_error().decode())
+                acc.append(ms.value)
+            call_ms.append(e0.elapsed_time(e1))
+        lens = out.decoded_lengths.float()
+        ratio = statistics.median(ps_ms) / statistics.median(dec_ms)
+        lines.append("%-10s %12.4f %12.4f %12.4f %12.3f %12.3f %8.4f %5d..%-5d"
+                     % (kind, statistics.median(ps_ms), statistics.median(sc_ms), statistics.median(pack_ms),
+                        statistics.median(dec_ms), statistics.median(call_ms), ratio, int(lens.min()), int(lens.max())))
+        res["paths"][kind] = {"path_scores": stat(ps_ms), "token_scores": stat(sc_ms), "pack": stat(pack_ms),
+                              "decode": stat(dec_ms), "call": stat(call_ms), "paths_over_decode": round(ratio, 4),
+                              "labels_min": int(lens.min()), "labels_max": int(lens.max()),
+                              "finite": int(torch.isfinite(ps).sum()), "rows": B * P}
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -209,9 +259,11 @@ def main():
     ap.add_argument("--times", action="store_true", help="the token-times kernel's cost at cfg3 instead")
     ap.add_argument("--scores", action="store_true",
                     help="the token-scores kernel's cost at cfg3, beside the token-times and pack kernels' of the same run")
+    ap.add_argument("--paths", action="store_true",
+                    help="the path-scores kernels' cost at cfg3, beside the decode, token-scores and pack kernels' of the same run")
     args = ap.parse_args()
-    if args.times or args.scores:
-        lines, res = scores_report(args) if args.scores else times_report(args)
+    if args.times or args.scores or args.paths:
+        lines, res = paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
