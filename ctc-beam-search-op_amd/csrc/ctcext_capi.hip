@@ -22,6 +22,7 @@
 #define CTCX_STREAM_HOST   // the stream builds' parameter structs (not their DecodeParams member)
 #include "ctcx_kernels.h"
 #include "ctcx_paths.h"
+#include "ctcx_align.h"
 #include "ctcx_scores.h"
 #include "ctcx_skip.h"
 #include "ctcx_stable.h"
@@ -168,6 +169,7 @@ struct Dev {
                              // [5], [6] around the token-times kernel of a dense call, [7], [8] the token-scores kernel,
                              // [9], [10] the path-scores kernels
   hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
+  hipEvent_t al[6] = {};     // ... of a dense call's path alignments: around the forward, walk back, emit, times, scores
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
   int64_t lo = 0, nb = 0;    // this call's shard [lo, lo + nb)
@@ -219,6 +221,8 @@ struct ctcext_decoder {
     ScoreSrc sc;                // what ctcext_dense_token_scores reads beside that
     bool scores_timed = false;  // events [7], [8] were recorded
     bool paths_timed = false;   // events [9], [10] were recorded
+    int64_t pad_value = -1;     // what ctcext_dense_path_alignments pads its rows with
+    int align_timed = 0;        // events al[0 .. align_timed) were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -233,6 +237,10 @@ struct ctcext_decoder {
   // staging of its outputs
   ScoreSrc ss;
   DevBuf sc_sum, sc_min, ps_out;   // (ps_out: ctcext_fetch_path_scores')
+  // the path alignments' grow-only workspace (ctcx_align.h): decision bits, the
+  // forward's results, the second walk buffer and its lengths; al_out stages the
+  // outputs of ctcext_fetch_path_alignments for host callers
+  DevBuf al_bp, al_fin, al_vseq, al_vlen, al_out;
   // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
   // the plan, and what the call that is running reads of it
   struct {
@@ -253,6 +261,8 @@ static void release_dev(Dev& d) {
   for (auto& ev : d.ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.sk)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : d.al)
     if (ev) (void)hipEventDestroy(ev);
   if (d.own_stream) (void)hipStreamDestroy(d.own_stream);
   d.own_stream = nullptr;
@@ -297,6 +307,7 @@ extern "C" int ctcext_create_sharded(const int* devices, int n_devices, ctcext_d
     }
     for (auto& ev : v.ev) (void)hipEventCreate(&ev);
     for (auto& ev : v.sk) (void)hipEventCreate(&ev);
+    for (auto& ev : v.al) (void)hipEventCreate(&ev);
     // the shard inputs and the gathered walks move between the root and this
     // device by peer copies (xGMI); "already enabled" is fine
     if (v.device != devices[0]) {
@@ -322,7 +333,8 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
+                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out,
+                    &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
   d->h_res.release();
@@ -1405,6 +1417,8 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   d->dense.sc = ScoreSrc{};
   d->dense.scores_timed = false;
   d->dense.paths_timed = false;
+  d->dense.pad_value = o ? o->pad_value : -1;
+  d->dense.align_timed = 0;
   if (a->batch_size > 0) {
     ScoreSrc& q = d->dense.sc;
     q.x = a->inputs;
@@ -3385,5 +3399,221 @@ extern "C" int ctcext_stream_path_scores(ctcext_stream* st, void* path_logp) {
   if (rc != CTCEXT_OK) return rc;
   HIP_OR_FAIL(ctcx_launch_path_scores(p, n.s));
   g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Path alignments (ctcext.h, "Path alignments"): ctcx_align.hip's kernels over
+// the same sources as the path scores, then the unchanged token-times and
+// token-scores kernels over the walk buffer the walk back writes (merge = 0).
+
+static int check_align_out(const ctcext_path_alignments_out* o) {
+  if (!o || !o->alignment || !o->alignment_length || !o->logp)
+    return fail(CTCEXT_INVALID_ARGUMENT, "path alignments need alignment, alignment_length and logp");
+  const bool times = o->start || o->end || o->trailing_blank, scores = o->logp_sum || o->logp_min;
+  if (times && !(o->start && o->end && o->trailing_blank))
+    return fail(CTCEXT_INVALID_ARGUMENT, "path alignments: start, end and trailing_blank come together or not at all");
+  if (scores && !times) return fail(CTCEXT_INVALID_ARGUMENT, "path alignments: the scores need the times");
+  return CTCEXT_OK;
+}
+
+// The workspace of a call of this shape; a call that has to grow it may block,
+// and is refused while the stream is capturing.
+static int align_workspace(ctcext_decoder* d, CtcxAlignParams& p, hipStream_t s) {
+  const size_t rows = (size_t)(p.B * p.P);
+  const size_t want[4] = {rows * (size_t)ctcx_align_row_bytes(p.Tmax), rows * 16, rows * 2 * (size_t)p.Tmax * 4 + 16,
+                          rows * 2 * 4};
+  DevBuf* const buf[4] = {&d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen};
+  bool grow = false;
+  for (int i = 0; i < 4; ++i) grow |= want[i] > buf[i]->cap;
+  if (grow) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &st) != hipSuccess) (void)hipGetLastError();
+    if (st != hipStreamCaptureStatusNone)
+      return fail(CTCEXT_FAILED_PRECONDITION,
+                  "path alignments: the workspace must grow and the stream is capturing; call once with this shape "
+                  "before the capture");
+    for (int i = 0; i < 4; ++i) HIP_OR_FAIL(buf[i]->ensure(want[i]));
+  }
+  p.bp = (uint32_t*)d->al_bp.p;
+  p.fin = d->al_fin.p;
+  p.vseq = (int32_t*)d->al_vseq.p;
+  p.vlen = (int32_t*)d->al_vlen.p;
+  return CTCEXT_OK;
+}
+
+static void align_params(CtcxAlignParams& p, const Dev& root, const ScoreSrc& q, int64_t T_, int64_t B, int64_t C,
+                         int P, int32_t blank_index, int32_t blank_label, int64_t pad_value) {
+  p.seq = (const int32_t*)root.seq.p;
+  p.len = (const int32_t*)root.len.p;
+  p.x = q.x;
+  p.norm = q.norm;
+  p.Tmax = T_; p.B = B; p.C = C; p.xst_t = q.st_t; p.xst_b = q.st_b;
+  p.P = P; p.xfmt = q.xfmt; p.f64 = q.f64 ? 1 : 0;
+  p.blank_index = blank_index; p.blank_label = blank_label;
+  p.force_lds = paths_force_lds_from_env();
+  p.pad_value = pad_value;
+}
+
+// forward, walk back, emit, times, scores; ev (or null): six events around them
+static int align_enqueue(const CtcxAlignParams& p, const ctcext_path_alignments_out* o, hipStream_t s, hipEvent_t* ev,
+                         int* timed) {
+  auto mark = [&](int i) -> hipError_t {
+    if (!ev) return hipSuccess;
+    *timed = i + 1;
+    return hipEventRecord(ev[i], s);
+  };
+  HIP_OR_FAIL(mark(0));
+  HIP_OR_FAIL(ctcx_launch_path_align(p, s));
+  HIP_OR_FAIL(mark(1));
+  HIP_OR_FAIL(ctcx_launch_path_align_back(p, s));
+  HIP_OR_FAIL(mark(2));
+  HIP_OR_FAIL(ctcx_launch_path_align_emit(p, s));
+  HIP_OR_FAIL(mark(3));
+  if (o->start) {
+    CtcxTimesParams tp{};
+    tp.seq = p.vseq; tp.len = p.vlen; tp.frames = p.frames; tp.status = p.status;
+    tp.Tmax = p.Tmax; tp.B = p.B; tp.P = p.P;
+    tp.merge = 0; tp.blank_label = p.blank_label;
+    tp.start = (int32_t*)o->start; tp.end = (int32_t*)o->end; tp.trailing_blank = (int32_t*)o->trailing_blank;
+    HIP_OR_FAIL(ctcx_launch_token_times(tp, s));
+    HIP_OR_FAIL(mark(4));
+    if (o->logp_sum || o->logp_min) {
+      CtcxScoresParams sp{};
+      sp.seq = p.vseq; sp.len = p.vlen; sp.frames = p.frames; sp.status = p.status;
+      sp.start = (const int32_t*)o->start; sp.end = (const int32_t*)o->end;
+      sp.x = p.x; sp.norm = p.norm;
+      sp.Tmax = p.Tmax; sp.B = p.B; sp.C = p.C; sp.xst_t = p.xst_t; sp.xst_b = p.xst_b;
+      sp.P = p.P; sp.xfmt = p.xfmt; sp.f64 = p.f64;
+      sp.blank_index = p.blank_index; sp.blank_label = p.blank_label;
+      sp.logp_sum = o->logp_sum; sp.logp_min = o->logp_min;
+      HIP_OR_FAIL(ctcx_launch_token_scores(sp, s));
+      HIP_OR_FAIL(mark(5));
+    }
+  }
+  return CTCEXT_OK;
+}
+
+static int check_align_width(const CtcxAlignParams& p) {
+  if (!ctcx_path_align_fits(p.Tmax, p.f64, p.force_lds))
+    return fail(CTCEXT_UNIMPLEMENTED, "path alignments: rows this wide do not fit the LDS trellis");
+  return CTCEXT_OK;
+}
+
+extern "C" int64_t ctcext_path_alignments_row_bytes(int64_t max_time) {
+  return max_time < 0 ? -1 : ctcx_align_row_bytes(max_time);
+}
+
+extern "C" int ctcext_dense_path_alignments(ctcext_decoder* d, const ctcext_path_alignments_out* o) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_align_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_path_alignments without a ctcext_decode_dense");
+  rc = ctcext_token_times_validate(d->dense.C, d->dense.blank_index, d->dense.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  if (d->dense.B == 0) return CTCEXT_OK;
+  if (!d->dense.sc.have) return fail(CTCEXT_INTERNAL, "path alignments: the inputs of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  CtcxAlignParams p{};
+  align_params(p, root, d->dense.sc, d->dense.T, B, d->dense.C, d->dense.P, d->dense.blank_index,
+               d->dense.blank_label, d->dense.pad_value);
+  p.frames = (const int32_t*)root.dsl.p;
+  p.status = (const int32_t*)root.dstat.p + B;
+  p.logp = o->logp; p.alignment = (int64_t*)o->alignment; p.alignment_length = (int32_t*)o->alignment_length;
+  rc = check_align_width(p);
+  if (rc != CTCEXT_OK) return rc;
+  rc = align_workspace(d, p, s);
+  if (rc != CTCEXT_OK) return rc;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  d->dense.align_timed = 0;
+  rc = align_enqueue(p, o, s, prof ? root.al : nullptr, &d->dense.align_timed);
+  if (rc != CTCEXT_OK) return rc;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_fetch_path_alignments(ctcext_decoder* d, const ctcext_path_alignments_out* o,
+                                            int32_t outputs_on_device) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = check_align_out(o);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_fetch_path_alignments without a successful ctcext_decode");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "path alignments need a one-device decoder handle");
+  rc = ctcext_token_times_validate(d->tt.C, d->tt.blank_index, d->tt.blank_label);
+  if (rc != CTCEXT_OK) return rc;
+  const int64_t B = d->B, T_ = d->T;
+  const int P = d->P;
+  if (B == 0) return CTCEXT_OK;
+  if (!d->ss.have)
+    return fail(CTCEXT_FAILED_PRECONDITION,
+                "ctcext_fetch_path_alignments after a stream's push: a stream keeps no logits to align");
+  if ((int64_t)d->tt.frames.size() != B)
+    return fail(CTCEXT_INTERNAL, "path alignments: the frame counts of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = root.s;
+  CtcxAlignParams p{};
+  align_params(p, root, d->ss, T_, B, d->tt.C, P, d->tt.blank_index, d->tt.blank_label, -1);
+  rc = check_align_width(p);
+  if (rc != CTCEXT_OK) return rc;
+  rc = align_workspace(d, p, s);
+  if (rc != CTCEXT_OK) return rc;
+  HIP_OR_FAIL(d->tt_frames.ensure(4 * (size_t)B));
+  HIP_OR_FAIL(hipMemcpyAsync(d->tt_frames.p, d->tt.frames.data(), 4 * (size_t)B, hipMemcpyHostToDevice, s));
+  p.frames = (const int32_t*)d->tt_frames.p;
+  p.status = nullptr;   // (a synchronous call with a failing item has failed as a whole)
+  // the outputs, or for a host caller their staging: eight arrays, each aligned to 16 bytes
+  const size_t rows = (size_t)(B * P), cells = rows * (size_t)T_, ts = d->ss.f64 ? 8 : 4;
+  void* const host[8] = {o->alignment, o->alignment_length, o->logp, o->start, o->end, o->trailing_blank, o->logp_sum,
+                         o->logp_min};
+  const size_t bytes[8] = {8 * cells, 4 * rows, ts * rows, 4 * cells, 4 * cells, 4 * rows, ts * cells, ts * cells};
+  ctcext_path_alignments_out dv = *o;
+  if (!outputs_on_device) {
+    size_t off[8], total = 0;
+    for (int i = 0; i < 8; ++i) {
+      off[i] = total;
+      if (host[i]) total += (bytes[i] + 15) & ~(size_t)15;
+    }
+    HIP_OR_FAIL(d->al_out.ensure(total + 16));
+    void** const dst[8] = {&dv.alignment, &dv.alignment_length, &dv.logp, &dv.start, &dv.end, &dv.trailing_blank,
+                           &dv.logp_sum, &dv.logp_min};
+    for (int i = 0; i < 8; ++i)
+      if (host[i]) *dst[i] = (char*)d->al_out.p + off[i];
+  }
+  p.logp = dv.logp; p.alignment = (int64_t*)dv.alignment; p.alignment_length = (int32_t*)dv.alignment_length;
+  rc = align_enqueue(p, &dv, s, nullptr, nullptr);
+  if (rc != CTCEXT_OK) return rc;
+  if (!outputs_on_device) {
+    void* const src[8] = {dv.alignment, dv.alignment_length, dv.logp, dv.start, dv.end, dv.trailing_blank, dv.logp_sum,
+                          dv.logp_min};
+    for (int i = 0; i < 8; ++i)
+      if (host[i] && bytes[i]) HIP_OR_FAIL(hipMemcpyAsync(host[i], src[i], bytes[i], hipMemcpyDeviceToHost, s));
+  }
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_path_alignments_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || d->dense.align_timed < 4)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no path alignments of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  const int n = d->dense.align_timed;
+  HIP_OR_FAIL(hipEventSynchronize(root.al[n - 1]));
+  for (int i = 0; i < 5; ++i) {
+    float f = 0;
+    if (i + 1 < n) HIP_OR_FAIL(hipEventElapsedTime(&f, root.al[i], root.al[i + 1]));
+    ms[i] = f;
+  }
   return CTCEXT_OK;
 }

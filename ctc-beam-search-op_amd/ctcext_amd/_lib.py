@@ -80,6 +80,9 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + STREAM_SCORES_SYMBOLS
 PATH_SCORES_SYMBOLS = ("ctcext_dense_path_scores", "ctcext_fetch_path_scores", "ctcext_stream_path_scores",
                        "ctcext_path_score_row", "ctcext_dense_path_scores_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PATH_SCORES_SYMBOLS
+PATH_ALIGNMENTS_SYMBOLS = ("ctcext_dense_path_alignments", "ctcext_fetch_path_alignments", "ctcext_path_alignment_row",
+                           "ctcext_path_alignments_row_bytes", "ctcext_dense_path_alignments_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PATH_ALIGNMENTS_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -141,6 +144,13 @@ class TokenTimesOut(ctypes.Structure):
 class TokenScoresOut(ctypes.Structure):
     """ctcext_token_scores: the outputs of the token-scores calls."""
     _fields_ = [("logp_sum", ctypes.c_void_p), ("logp_min", ctypes.c_void_p)]
+
+
+class PathAlignmentsOut(ctypes.Structure):
+    """ctcext_path_alignments_out: the outputs of the path-alignment calls."""
+    _fields_ = [("alignment", ctypes.c_void_p), ("alignment_length", ctypes.c_void_p), ("logp", ctypes.c_void_p),
+                ("start", ctypes.c_void_p), ("end", ctypes.c_void_p), ("trailing_blank", ctypes.c_void_p),
+                ("logp_sum", ctypes.c_void_p), ("logp_min", ctypes.c_void_p)]
 
 
 class SkipArgs(ctypes.Structure):
@@ -396,6 +406,20 @@ def load():
         lib.ctcext_path_score_row.restype = ctypes.c_int
         lib.ctcext_dense_path_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_path_scores_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_path_alignments"):   # (CTCEXT_HAS_PATH_ALIGNMENTS; older builds stay loadable)
+        lib.ctcext_dense_path_alignments.argtypes = [ctypes.c_void_p, ctypes.POINTER(PathAlignmentsOut)]
+        lib.ctcext_dense_path_alignments.restype = ctypes.c_int
+        lib.ctcext_fetch_path_alignments.argtypes = [ctypes.c_void_p, ctypes.POINTER(PathAlignmentsOut), ctypes.c_int32]
+        lib.ctcext_fetch_path_alignments.restype = ctypes.c_int
+        lib.ctcext_path_alignment_row.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                                  ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                                  ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
+        lib.ctcext_path_alignment_row.restype = ctypes.c_int
+        lib.ctcext_path_alignments_row_bytes.argtypes = [ctypes.c_int64]
+        lib.ctcext_path_alignments_row_bytes.restype = ctypes.c_int64
+        lib.ctcext_dense_path_alignments_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_path_alignments_ms.restype = ctypes.c_int
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

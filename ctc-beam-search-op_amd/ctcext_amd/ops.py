@@ -851,6 +851,141 @@ def path_score_row(x, norm, decoded, frames, blank_index, blank_label=-1):
     return out[0]
 
 
+PathAlignments = collections.namedtuple("PathAlignments", ["alignment", "alignment_lengths", "logp", "times", "scores"])
+
+_NO_ALIGN = "path alignments need a decode with token_scores=True"
+
+
+def _align_lib(lib):
+    if not hasattr(lib, "ctcext_dense_path_alignments"):
+        raise UnimplementedError("this libctcext.so has no path alignments (CTCEXT_HAS_PATH_ALIGNMENTS)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+def _align_outputs(B, P, T, fdt, times, scores, dev):
+    """Uninitialised outputs of a path-alignments call (CUDA tensors on dev, numpy arrays for dev None), their
+    struct, and the PathAlignments that holds them."""
+    if scores and not times:
+        raise ValueError("path alignments: scores=True needs times=True")
+    if dev is None:
+        ft = np.float64 if fdt == "float64" else np.float32
+        new = lambda shape, dt: np.empty(shape, {"int64": np.int64, "int32": np.int32, "f": ft}[dt])
+        ptr = lambda t: t.ctypes.data
+    else:
+        import torch
+        ft = torch.float64 if fdt == "float64" else torch.float32
+        def new(shape, dt):
+            with torch.cuda.device(dev):
+                return torch.empty(shape, dtype={"int64": torch.int64, "int32": torch.int32, "f": ft}[dt], device=dev)
+        ptr = lambda t: t.data_ptr()
+    o = _lib.PathAlignmentsOut()
+    ali, alen, logp = new((B, P, T), "int64"), new((B, P), "int32"), new((B, P), "f")
+    o.alignment, o.alignment_length, o.logp = ptr(ali), ptr(alen), ptr(logp)
+    tt = sc = None
+    if times:
+        tt = TokenTimes(new((B, P, T), "int32"), new((B, P, T), "int32"), new((B, P), "int32"))
+        o.start, o.end, o.trailing_blank = [ptr(t) for t in tt]
+    if scores:
+        sc = TokenScores(new((B, P, T), "f"), new((B, P, T), "f"))
+        o.logp_sum, o.logp_min = [ptr(t) for t in sc]
+    return o, PathAlignments(ali, alen, logp, tt, sc)
+
+
+def dense_path_alignments(times=True, scores=False, device=None):
+    """The Viterbi alignment of every returned label row of the calling
+    thread's last ``decode_dense(..., token_scores=True)`` on ``device`` (None:
+    the current one): the single most likely CTC alignment of the row over all
+    of the item's frames, by a trellis on the device, enqueued behind the
+    decode on the stream the decode went to.  It waits for nothing; the first
+    call of a shape sizes a workspace (``max_time * words * 256`` bytes per
+    row, ``include/ctcext.h``, "Path alignments") and may block, and inside a
+    ``torch.cuda.graph`` capture a call that would have to grow it raises
+    ``FailedPreconditionError``: call once with the shape before capturing.
+
+    Returns ``PathAlignments(alignment, alignment_lengths, logp, times,
+    scores)``: ``alignment`` int64 ``[B, top_paths, T]`` padded with the
+    decode's ``pad_value``, ``alignment_lengths`` int32 ``[B, top_paths]``
+    (the item's frames, or 0 for an unaligned row), ``logp`` ``[B, top_paths]``
+    of the compute dtype (the alignment's log-probability), ``times`` a
+    ``TokenTimes`` and ``scores`` a ``TokenScores`` of that alignment (None
+    when not asked for; ``scores`` needs ``times``).  Unlike the decode's
+    alignment rows it is complete -- every token is timed -- does not depend on
+    ``beam_width``, belongs to the returned (merged) string, and covers the
+    frames ``skip_blank`` dropped.  A row with ``logp`` ``-inf`` or NaN is
+    unaligned: length 0, times -1, scores NaN."""
+    what = "ctcext_dense_path_alignments without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = _align_lib(dec.lib)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_ALIGN, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    o, out = _align_outputs(B, P, T, str(fdt).replace("torch.", ""), times, scores, dev)
+    rc = lib.ctcext_dense_path_alignments(dec.handle, ctypes.byref(o))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def path_alignments(times=True, scores=False, device=None):
+    """``dense_path_alignments`` for the synchronous calls: the alignments of
+    the hypotheses the calling thread's last ``ctc_ext_beam_search_decoder`` or
+    ``decode_logits`` with ``token_scores=True`` on ``device`` returned (not
+    after a stream's push).  Waits.  Rows are padded with -1.  Returns numpy
+    arrays, or CUDA tensors where that call's outputs were."""
+    what = "ctcext_fetch_path_alignments without a successful ctcext_decode"
+    dec = _thread_decoder(device, what)
+    lib = _align_lib(dec.lib)
+    if getattr(dec, "_times_sync", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_sync", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_ALIGN, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, to_device, f64 = shape
+    dev = None
+    if to_device:
+        import torch
+        dev = torch.device("cuda", dec.device)
+    o, out = _align_outputs(B, P, T, "float64" if f64 else "float32", times, scores, dev)
+    rc = lib.ctcext_fetch_path_alignments(dec.handle, ctypes.byref(o), 1 if to_device else 0)
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def path_alignment_row(x, norm, decoded, frames, blank_index, blank_label=-1):
+    """The definition of the path alignment for one row, on the host (no GPU),
+    in the compute dtype: ``x`` is one item's logits ``[frames, num_classes]``
+    (float32 or float64), ``norm`` its rows' normaliser ``[frames]``,
+    ``decoded`` one path's label row (without padding).  Returns ``(alignment,
+    logp)``: an int64 array of ``frames`` values (empty for an unaligned row)
+    and a numpy scalar of ``x``'s dtype."""
+    lib = _align_lib(_lib.load())
+    x = np.asarray(x)
+    dt = np.float64 if x.dtype == np.float64 else np.float32
+    frames = int(frames)
+    if x.ndim != 2:
+        raise ValueError("path_alignment_row: x must be [frames, num_classes]")
+    C = int(x.shape[1])
+    x = np.ascontiguousarray(x[:frames], dtype=dt)
+    nm = np.ascontiguousarray(np.asarray(norm).reshape(-1)[:frames], dtype=dt)
+    if x.shape[0] != frames or nm.size != frames:
+        raise ValueError("path_alignment_row: x and norm must hold the item's frames")
+    y = np.ascontiguousarray(np.asarray(decoded, dtype=np.int64).reshape(-1))
+    ali = np.empty((max(frames, 1),), np.int64)
+    n = ctypes.c_int64()
+    logp = np.empty((1,), dt)
+    rc = lib.ctcext_path_alignment_row(x.ctypes.data, nm.ctypes.data, 1 if dt == np.float64 else 0, frames, C,
+                                       _ptr(y, ctypes.c_int64), int(y.size), int(blank_index), int(blank_label),
+                                       _ptr(ali, ctypes.c_int64), ctypes.byref(n), logp.ctypes.data)
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_path_alignment_row: bad arguments", rc)
+    return ali[:n.value].copy(), logp[0]
+
+
 def kept_frames(device=None):
     """The frames each item kept in the calling thread's last decode with
     ``skip_blank`` on ``device`` (None: the current one): a numpy int32 ``[B]``

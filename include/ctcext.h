@@ -1144,6 +1144,128 @@ int ctcext_path_score_row(const void* x, const void* norm, int32_t f64, int64_t 
  * last path-scores kernels of a dense call in ms.  Waits for them. */
 int ctcext_dense_path_scores_ms(ctcext_decoder* dec, double* ms);
 
+/* ---------------------------------------------------------------------------
+ * Path alignments: the Viterbi alignment of every returned path, on the
+ * device -- the single most likely CTC alignment of the returned label row
+ * over all of the item's frames, with the token times and token scores of that
+ * alignment.  The alignment rows of the decode are the best alignment among
+ * the prefixes that survived in the beam: they can be shorter than the item,
+ * belong to the unmerged string under merge_repeated, and read blank_label at
+ * frames a skipping decode dropped.  A re-alignment is complete: every token
+ * is timed and scored, it does not depend on beam_width, and it covers the
+ * dropped frames.  New entry points only (CTCEXT_ABI_VERSION is unchanged;
+ * detect them by CTCEXT_HAS_PATH_ALIGNMENTS at build time or by symbol at run
+ * time).
+ *
+ * Definition.  For path p of item b, the following are exactly the path
+ * scores' (same sources in every mode, including after skip_blank, where they
+ * are the caller's rows on the original time axis with skip.norm):
+ *
+ * - y[0..m), frames, lp[f][c] = x[f][c] - norm[f] as one rounded subtraction
+ *   in the compute dtype, and blank;
+ * - the S = 2m + 1 states z;
+ * - the skip permission z[s] != z[s-2].
+ *
+ * All arithmetic is in the compute dtype.  No operation may be contracted or
+ * reassociated.
+ *
+ * - v_0[0] = lp[0][blank], v_0[1] = lp[0][y[0]] when m > 0, and every other
+ *   state is -inf.
+ * - v_f[s] = best + lp[f][z[s]].  best starts as v_{f-1}[s] (decision 0).
+ * - It is replaced by v_{f-1}[s-1] if that is strictly greater (decision 1).
+ * - It is then replaced by v_{f-1}[s-2] if the skip is allowed and that is
+ *   strictly greater than the current best (decision 2).
+ * - A comparison with a NaN is false.
+ * - The end state is S-1, unless m > 0 and v[S-2] > v[S-1].  logp is that
+ *   state's value.
+ * - The alignment is obtained by following the decisions from the end state at
+ *   frame frames - 1 down to frame 0.  Frame f reads y[(s-1)/2] at an odd
+ *   state and blank_label at an even one.
+ * - frames == 0 with m == 0 gives logp = 0 and an empty alignment; frames == 0
+ *   with m > 0 gives logp = -inf.
+ * - A row whose logp is -inf or NaN is unaligned.  This covers an infeasible
+ *   row, a label outside [0, C) (logp = NaN), and an item with a status bit
+ *   (logp = NaN).  Its alignment length is 0, its row is all pad_value, its
+ *   times are -1, its trailing_blank is 0 and its scores are NaN.
+ * - The blank_label rule of the token times applies
+ *   (ctcext_token_times_validate).
+ *
+ * Token times and token scores of the re-alignment are the existing
+ * definitions ("Token times", "Token scores") applied to the new alignment
+ * row, with merge = 0.  In a trellis alignment, runs and tokens correspond one
+ * to one, whatever merge_repeated was.
+ *
+ * Because no exp or log is involved, the kernels are held to this definition
+ * bit for bit (ctcext_path_alignment_row).
+ *
+ * Workspace.  The forward keeps a decision per state and frame.  One row of
+ * that back-pointer workspace is a function of max_time alone:
+ *   max_time * words(max_time) * 256 bytes  (ctcext_path_alignments_row_bytes),
+ * words(max_time) being the larger of ceil((3 K + 1) / 32), K the labels a
+ * lane holds for a row of max_time labels (1, 2, 4, 8, 16, 24 for up to 64,
+ * 128, 256, 512, 1024, 1536), and ceil(ceil((max_time + 1) / 64) / 10), the
+ * need of the wide-row kernel.  At max_time 1500: 3 words, 1.15 MB per row,
+ * batch * top_paths rows.  It is grow-only, sized with a second walk buffer at
+ * the first call of a shape; that call may block (it allocates).  Rows wider
+ * than the kernels hold (max_time above 13000, 8000 for float64):
+ * CTCEXT_UNIMPLEMENTED.
+ *
+ * The logits contract of "Token scores" applies unchanged.
+ *
+ * Not covered: streams; handles of more than one device
+ * (CTCEXT_UNIMPLEMENTED); scorer-table terms; aligning transcripts the decode
+ * did not return; checkpointing the back-pointers to shrink the workspace. */
+#define CTCEXT_HAS_PATH_ALIGNMENTS 1
+
+/* Device pointers (host pointers for ctcext_fetch_path_alignments without
+ * outputs_on_device).  alignment is int64 [batch][top_paths][max_time],
+ * alignment_length int32 [batch][top_paths], logp [batch][top_paths] of the
+ * compute dtype; start / end / trailing_blank as ctcext_token_times, logp_sum /
+ * logp_min as ctcext_token_scores.  The times group (start, end,
+ * trailing_blank) may be NULL as a whole; the scores group may be NULL (either
+ * or both) and requires the times group. */
+typedef struct {
+  void* alignment;
+  void* alignment_length;
+  void* logp;
+  void* start;
+  void* end;
+  void* trailing_blank;
+  void* logp_sum;
+  void* logp_min;
+} ctcext_path_alignments_out;
+
+/* Host only: bytes of one row of the back-pointer workspace (the formula
+ * above); -1 for a negative max_time. */
+int64_t ctcext_path_alignments_row_bytes(int64_t max_time);
+/* Enqueues the forward kernels, the walk back, the emit and (where asked for)
+ * the token-times and token-scores kernels on the stream of the last
+ * ctcext_decode_dense / ctcext_decode_dense_skip, behind whatever that stream
+ * holds, over that call's rows; rows are padded with that call's pad_value.
+ * Waits for nothing.  The first call of a shape sizes the workspace and may
+ * block; a call that would have to grow it while the stream is capturing
+ * returns CTCEXT_FAILED_PRECONDITION and allocates nothing.  Without a
+ * preceding dense decode: CTCEXT_FAILED_PRECONDITION. */
+int ctcext_dense_path_alignments(ctcext_decoder* dec, const ctcext_path_alignments_out* out);
+/* Synchronous; valid after ctcext_decode / ctcext_decode_skip (not after a
+ * stream's push: CTCEXT_FAILED_PRECONDITION).  Rows are padded with -1.
+ * One-device handles only: CTCEXT_UNIMPLEMENTED otherwise. */
+int ctcext_fetch_path_alignments(ctcext_decoder* dec, const ctcext_path_alignments_out* out,
+                                 int32_t outputs_on_device);
+/* Host only, no HIP call: the definition above for one row, in the compute
+ * dtype, in plain C++ that shares no code with the kernels.  x is one item's
+ * rows, dense [frames][num_classes], and norm [frames], both of the compute
+ * dtype (f64: doubles, else floats); decoded holds the row's m labels;
+ * alignment receives alignment_length (0 or frames) values, logp one value of
+ * the compute dtype. */
+int ctcext_path_alignment_row(const void* x, const void* norm, int32_t f64, int64_t frames, int64_t num_classes,
+                              const int64_t* decoded, int64_t m, int32_t blank_index, int64_t blank_label,
+                              int64_t* alignment, int64_t* alignment_length, void* logp);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the times in ms
+ * of the last dense call's forward kernels, walk back, emit, token-times and
+ * token-scores kernels (ms[5]; 0 for those not asked for).  Waits for them. */
+int ctcext_dense_path_alignments_ms(ctcext_decoder* dec, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,11 @@ With --paths, instead: the path-scores kernels (dense_path_scores) on the same
 two inputs, beside the decode kernel, the whole call, and the token-scores and
 pack kernels of the same run.
 
+With --align, instead: the path-alignment kernels (dense_path_alignments with
+times and scores) on the same two inputs: the forward, walk back, emit,
+token-times and token-scores launches, beside the path-scores kernels of the
+same run and inputs, the decode kernel and the whole call.
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -247,6 +252,53 @@ def paths_report(args):
     return lines, res
 
 
+def align_report(args):
+    """--align: one row per input family at cfg3."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    names = ("forward", "walk_back", "emit", "token_times", "token_scores")
+    lines = ["%-10s %9s %9s %9s %9s %9s %11s %10s %11s %8s   (median of %d, ms; cfg3 B=%d T=%d C=%d W=%d P=%d)"
+             % (("inputs",) + tuple(n[:9] for n in names) + ("path scores", "decode", "whole call", "all/call", args.runs,
+                                                             B, T, C, W, P))]
+    res = {"runs": args.runs, "shape": [B, T, C, W, P],
+           "workspace_row_bytes": int(dec.lib.ctcext_path_alignments_row_bytes(T)), "align": {}}
+    for kind in ("gaussian", "peaky"):
+        x = times_inputs(kind, T, B, C)
+        ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, token_scores=True, **KW)   # warm-up: workspaces, kernels
+        ctcext_amd.dense_path_scores()
+        ctcext_amd.dense_path_alignments(scores=True)
+        ctcext_amd.dense_check()
+        parts, ps_ms, dec_ms, call_ms = [[] for _ in names], [], [], []
+        for _ in range(args.runs):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True, **KW)
+            ctcext_amd.dense_path_scores()
+            pa = ctcext_amd.dense_path_alignments(scores=True)
+            e1.record()
+            e1.synchronize()
+            dec_ms.append(ctcext_amd.dense_check()["decode_kernel_ms"])
+            ms, five = ctypes.c_double(), (ctypes.c_double * 5)()
+            if dec.lib.ctcext_dense_path_scores_ms(dec.handle, ctypes.byref(ms)) != _lib.CTCEXT_OK or \
+                    dec.lib.ctcext_dense_path_alignments_ms(dec.handle, five) != _lib.CTCEXT_OK:
+                raise SystemExit(dec.lib.ctcext_last_error().decode())
+            ps_ms.append(ms.value)
+            for acc, v in zip(parts, five):
+                acc.append(v)
+            call_ms.append(e0.elapsed_time(e1))
+        total = sum(statistics.median(v) for v in parts)
+        share = total / statistics.median(call_ms)
+        lines.append("%-10s %9.4f %9.4f %9.4f %9.4f %9.4f %11.4f %10.3f %11.3f %8.4f"
+                     % ((kind,) + tuple(statistics.median(v) for v in parts)
+                        + (statistics.median(ps_ms), statistics.median(dec_ms), statistics.median(call_ms), share)))
+        res["align"][kind] = dict({n: stat(v) for n, v in zip(names, parts)}, path_scores=stat(ps_ms), decode=stat(dec_ms),
+                                  call=stat(call_ms), all_over_call=round(share, 4),
+                                  aligned=int((pa.alignment_lengths > 0).sum()), rows=B * P)
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -261,9 +313,11 @@ def main():
                     help="the token-scores kernel's cost at cfg3, beside the token-times and pack kernels' of the same run")
     ap.add_argument("--paths", action="store_true",
                     help="the path-scores kernels' cost at cfg3, beside the decode, token-scores and pack kernels' of the same run")
+    ap.add_argument("--align", action="store_true",
+                    help="the path-alignment kernels' cost at cfg3, beside the path-scores kernels' of the same run")
     args = ap.parse_args()
-    if args.times or args.scores or args.paths:
-        lines, res = paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.times or args.scores or args.paths or args.align:
+        lines, res = align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
