@@ -23,6 +23,7 @@
 #include "ctcx_kernels.h"
 #include "ctcx_paths.h"
 #include "ctcx_align.h"
+#include "ctcx_greedy.h"
 #include "ctcx_scores.h"
 #include "ctcx_skip.h"
 #include "ctcx_stable.h"
@@ -171,6 +172,7 @@ struct Dev {
   hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
   hipEvent_t al[6] = {};     // ... of a dense call's path alignments: around the forward, walk back, emit, times, scores
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
+  DevBuf gk, glp;            // the greedy decode: the rows' arg-max [T][B] and max - norm [T][B]
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
   int64_t lo = 0, nb = 0;    // this call's shard [lo, lo + nb)
   int ring = 0;              // this call's record-ring frames (ctcx::ring_frames)
@@ -223,6 +225,7 @@ struct ctcext_decoder {
     bool paths_timed = false;   // events [9], [10] were recorded
     int64_t pad_value = -1;     // what ctcext_dense_path_alignments pads its rows with
     int align_timed = 0;        // events al[0 .. align_timed) were recorded
+    bool greedy = false;        // it was a ctcext_decode_greedy (events [0] .. [2] around its two kernels)
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -256,7 +259,7 @@ static void release_dev(Dev& d) {
   (void)hipSetDevice(d.device);
   if (d.own_stream) (void)hipStreamSynchronize(d.own_stream);
   DevBuf* bufs[] = {&d.x, &d.xw, &d.sl, &d.norm, &d.prep, &d.rec, &d.foff, &d.item, &d.top_pos, &d.top_kind, &d.logp,
-                    &d.seq, &d.len, &d.phase, &d.sctab, &d.gstate, &d.dsl, &d.dstat};
+                    &d.seq, &d.len, &d.phase, &d.sctab, &d.gstate, &d.dsl, &d.dstat, &d.gk, &d.glp};
   for (DevBuf* b : bufs) b->release();
   for (auto& ev : d.ev)
     if (ev) (void)hipEventDestroy(ev);
@@ -1419,6 +1422,7 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   d->dense.paths_timed = false;
   d->dense.pad_value = o ? o->pad_value : -1;
   d->dense.align_timed = 0;
+  d->dense.greedy = false;
   if (a->batch_size > 0) {
     ScoreSrc& q = d->dense.sc;
     q.x = a->inputs;
@@ -1524,6 +1528,166 @@ extern "C" int ctcext_dense_pack_ms(ctcext_decoder* d, double* ms) {
   if (!d->dense.have || !(d->dense.flags & CTCEXT_FLAG_PROFILE))
     return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE dense decode checked yet");
   *ms = d->dense.pack_ms;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Greedy decode (ctcext.h, "Greedy decode"): the dense call's prologue, then
+// the per-row kernel and the collapse of ctcx_greedy.hip, which fill what
+// ctcx_pack_dense and the traceback would have: the outputs, the walks and
+// their lengths, the status words, the per-item counters (zero) and the path
+// kinds ctcext_dense_check reads.
+
+static_assert(sizeof(ctcx::ItemOut) == 4 * kGreedyItemWords, "the collapse zeroes the decode's per-item result");
+static_assert(kGreedyInNative == CTCEXT_IN_NATIVE && kGreedyInF16 == CTCEXT_IN_F16 && kGreedyInBF16 == CTCEXT_IN_BF16,
+              "ctcx_greedy.h restates the element formats");
+
+extern "C" int ctcext_greedy_validate(const ctcext_decode_args* a, const ctcext_dense_outputs* o) {
+  int rc = ctcext_dense_validate(a, o);
+  if (rc != CTCEXT_OK) return rc;
+  if (a->top_paths != 1)
+    return fail(CTCEXT_INVALID_ARGUMENT, "the greedy decode returns one path per item: top_paths must be 1");
+  if (a->scorer != CTCEXT_SCORER_BASE)
+    return fail(CTCEXT_INVALID_ARGUMENT, "the greedy decode takes no beam scorer: scorer must be CTCEXT_SCORER_BASE");
+  if (a->flags & ~(CTCEXT_FLAG_PROFILE | CTCEXT_FLAG_DENSE_NULL_STREAM))
+    return fail(CTCEXT_INVALID_ARGUMENT,
+                "the greedy decode's flags may hold only CTCEXT_FLAG_PROFILE and CTCEXT_FLAG_DENSE_NULL_STREAM");
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// The workspace of a greedy call (grow-only); launches nothing.
+static int greedy_plan(ctcext_decoder* d, const ctcext_decode_args* a) {
+  const size_t B = (size_t)a->batch_size, cells = (size_t)(a->max_time * a->batch_size);
+  const size_t ts = a->dtype == CTCEXT_F64 ? 8 : 4;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(root.dsl.ensure(4 * B));
+  HIP_OR_FAIL(root.dstat.ensure(4 * (2 * B + 1)));
+  HIP_OR_FAIL(d->h_item.ensure(sizeof(ctcx::ItemOut) * B + 16));
+  HIP_OR_FAIL(d->h_kind.ensure(4 * B + 16));
+  HIP_OR_FAIL(d->h_status.ensure(4 * B + 16));
+  HIP_OR_FAIL(root.norm.ensure(ts * cells));
+  HIP_OR_FAIL(root.gk.ensure(4 * cells));
+  HIP_OR_FAIL(root.glp.ensure(ts * cells));
+  HIP_OR_FAIL(root.item.ensure(sizeof(ctcx::ItemOut) * B));
+  HIP_OR_FAIL(root.top_kind.ensure(4 * B));
+  HIP_OR_FAIL(root.seq.ensure(4 * 2 * cells));
+  HIP_OR_FAIL(root.len.ensure(4 * 2 * B));
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_greedy_reserve(ctcext_decoder* d, const ctcext_decode_args* a) {
+  if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = validate_shapes(a);
+  if (rc == CTCEXT_OK) rc = check_limits(a);
+  if (rc == CTCEXT_OK) rc = check_layout(a);
+  if (rc != CTCEXT_OK) return rc;
+  hipStream_t s;
+  rc = dense_begin(d, a, &s);
+  if (rc != CTCEXT_OK || a->batch_size == 0) return rc;
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(d->devs[0].device));
+  // (the handle's state of the last call -- fetch, check, stats -- is not touched)
+  rc = greedy_plan(d, a);
+  if (rc == CTCEXT_OK) g_err.clear();
+  return rc;
+}
+
+extern "C" int ctcext_decode_greedy(ctcext_decoder* d, const ctcext_decode_args* a, const ctcext_dense_outputs* o) {
+  if (!d || !a) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  d->have = false;
+  d->dense.have = false;
+  d->ss.have = false;
+  int rc = ctcext_greedy_validate(a, o);
+  if (rc != CTCEXT_OK) return rc;
+  hipStream_t s;
+  rc = dense_begin(d, a, &s);
+  if (rc != CTCEXT_OK) return rc;
+  if (a->batch_size > 0 && (((uintptr_t)o->decoded | (uintptr_t)o->alignment) & 7))
+    return fail(CTCEXT_INVALID_ARGUMENT, "dense outputs decoded and alignment need 8-byte alignment");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  root.s = s;
+  d->stats = ctcext_stats{};
+  const int64_t T_ = a->max_time, B = a->batch_size;
+  int64_t st_t, st_b;
+  input_strides(a, st_t, st_b);
+  if (B > 0) {
+    rc = greedy_plan(d, a);   // (nothing to grow after a reserve or a call of this shape)
+    if (rc != CTCEXT_OK) return rc;
+    const bool prof = (a->flags & CTCEXT_FLAG_PROFILE) != 0;
+    int32_t* const pre = (int32_t*)root.dstat.p;
+    ctcx::DensePrologueParams pp{};
+    pp.seq_len = a->sequence_length;
+    pp.sl = (int32_t*)root.dsl.p;
+    pp.pre = pre;
+    pp.Tmax = T_; pp.B = B;
+    HIP_OR_FAIL(ctcx::launch_dense_prologue(pp, nullptr, 0, a->dtype == CTCEXT_F64, pre + 2 * B, s));
+    CtcxGreedyParams p{};
+    p.x = a->inputs; p.sl = pp.sl; p.pre = pre;
+    p.Tmax = T_; p.B = B; p.C = a->num_classes; p.xst_t = st_t; p.xst_b = st_b;
+    p.xfmt = a->inputs_format; p.f64 = a->dtype == CTCEXT_F64 ? 1 : 0;
+    p.blank_index = a->blank_index; p.blank_label = a->blank_label; p.merge = a->merge_repeated ? 1 : 0;
+    p.pad_value = o->pad_value;
+    p.norm = root.norm.p; p.k = (int32_t*)root.gk.p; p.lp = root.glp.p;
+    p.seq = (int32_t*)root.seq.p; p.len = (int32_t*)root.len.p;
+    p.status_ws = pre + B; p.item = (int32_t*)root.item.p; p.top_kind = (int32_t*)root.top_kind.p;
+    p.decoded = o->decoded; p.alignment = o->alignment;
+    p.decoded_length = o->decoded_length; p.alignment_length = o->alignment_length;
+    p.log_probability = o->log_probability; p.status = o->status;
+    // the events ctcext_dense_check reads: [0], [1] around the per-row kernel
+    // (norm_kernel_ms), [2] behind the collapse (decode_kernel_ms); no
+    // traceback and no pack
+    if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[0], s));
+    HIP_OR_FAIL(ctcx_launch_greedy_frames(p, s));
+    if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[1], s));
+    HIP_OR_FAIL(ctcx_launch_greedy_collapse(p, s));
+    if (prof)
+      for (int i = 2; i <= 4; ++i) HIP_OR_FAIL(hipEventRecord(root.ev[i], s));
+  }
+  d->B = B;
+  d->dense.have = true;
+  d->dense.B = B; d->dense.T = T_; d->dense.P = 1; d->dense.flags = a->flags;
+  d->dense.s = s;
+  d->dense.pack_ms = 0;
+  d->dense.C = a->num_classes; d->dense.blank_index = a->blank_index; d->dense.blank_label = a->blank_label;
+  d->dense.merge = a->merge_repeated ? 1 : 0;
+  d->dense.times_timed = false;
+  d->dense.skip = false;
+  d->dense.sc = ScoreSrc{};
+  d->dense.scores_timed = false;
+  d->dense.paths_timed = false;
+  d->dense.pad_value = o ? o->pad_value : -1;
+  d->dense.align_timed = 0;
+  d->dense.greedy = true;
+  if (B > 0) {
+    ScoreSrc& q = d->dense.sc;
+    q.x = a->inputs;
+    q.xfmt = a->inputs_format;
+    q.st_t = st_t; q.st_b = st_b;
+    q.norm = root.norm.p;
+    q.f64 = a->dtype == CTCEXT_F64;
+    q.have = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_greedy_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.greedy || !(d->dense.flags & CTCEXT_FLAG_PROFILE) || d->dense.B == 0)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE greedy decode yet");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.ev[2]));
+  for (int i = 0; i < 2; ++i) {
+    float f = 0;
+    HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[i], root.ev[i + 1]));
+    ms[i] = f;
+  }
+  g_err.clear();
   return CTCEXT_OK;
 }
 

@@ -83,6 +83,10 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PATH_SCORES_SYMBOLS
 PATH_ALIGNMENTS_SYMBOLS = ("ctcext_dense_path_alignments", "ctcext_fetch_path_alignments", "ctcext_path_alignment_row",
                            "ctcext_path_alignments_row_bytes", "ctcext_dense_path_alignments_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PATH_ALIGNMENTS_SYMBOLS
+# the greedy decode (CTCEXT_HAS_GREEDY)
+GREEDY_SYMBOLS = ("ctcext_greedy_validate", "ctcext_greedy_reserve", "ctcext_decode_greedy", "ctcext_greedy_row",
+                  "ctcext_greedy_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + GREEDY_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -420,6 +424,24 @@ def load():
         lib.ctcext_path_alignments_row_bytes.restype = ctypes.c_int64
         lib.ctcext_dense_path_alignments_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_path_alignments_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_decode_greedy"):   # (CTCEXT_HAS_GREEDY; older builds stay loadable for A/B runs)
+        lib.ctcext_greedy_validate.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.POINTER(DenseOutputs)]
+        lib.ctcext_greedy_validate.restype = ctypes.c_int
+        lib.ctcext_greedy_reserve.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs)]
+        lib.ctcext_greedy_reserve.restype = ctypes.c_int
+        lib.ctcext_decode_greedy.argtypes = [ctypes.c_void_p, ctypes.POINTER(DecodeArgs), ctypes.POINTER(DenseOutputs)]
+        lib.ctcext_decode_greedy.restype = ctypes.c_int
+        # (x[frames][num_classes] and norm[frames] of the compute dtype, f64, frames, num_classes, blank_index,
+        #  blank_label, merge_repeated, int64 decoded[frames], int64* decoded_length, int64 alignment[frames],
+        #  int64* alignment_length, logp)
+        lib.ctcext_greedy_row.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.c_void_p]
+        lib.ctcext_greedy_row.restype = ctypes.c_int
+        lib.ctcext_greedy_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_greedy_ms.restype = ctypes.c_int
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

@@ -536,6 +536,131 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
     return out
 
 
+def _greedy_lib(lib):
+    if not hasattr(lib, "ctcext_decode_greedy"):
+        raise UnimplementedError("this libctcext.so has no greedy decode (CTCEXT_HAS_GREEDY)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+def decode_greedy(logits, lengths, *, batch_first=True, merge_repeated=False, blank_index=0, blank_label=-1,
+                  pad_value=-1, flags=0, out=None, token_scores=False):
+    """The best-path ("greedy") decode of GPU logits into padded GPU tensors,
+    without waiting for anything: per frame the class of the largest logit
+    (the lowest index of a tie), repeats and blanks collapsed, and with
+    ``merge_repeated`` a label equal to the one before it in the collapsed row
+    dropped as the op drops it.  Two kernels read the logits once, where the
+    beam search walks a serial chain per item: use it for partial results
+    between beam decodes, as a first pass, or for large vocabularies.
+
+    ``logits``, ``lengths``, ``out`` and the deferred errors are
+    ``decode_dense``'s (CUDA torch tensors, its dtypes, strides and in-place
+    rules; a host tensor raises ``ValueError``), the call is enqueued on
+    ``torch.cuda.current_stream()`` and can be captured into a
+    ``torch.cuda.graph`` after one call of the shape.  Returns ``DenseDecode``
+    with ``top_paths`` 1: ``alignment`` row ``[b, 0]`` holds the item's frames
+    (``blank_label`` at a blank frame), ``log_probability`` the best path's
+    log-probability under the decoder's own normaliser.  The definition is in
+    ``include/ctcext.h``, "Greedy decode" (``greedy_row`` on the host).
+
+    ``dense_check``, ``dense_token_times``, ``dense_token_scores``,
+    ``dense_path_scores`` and ``dense_path_alignments`` follow it as they
+    follow ``decode_dense`` (the last three with ``token_scores=True``)."""
+    lib = _greedy_lib(_lib.load())
+    if not (_is_torch(logits) and logits.is_cuda):
+        raise ValueError("decode_greedy takes CUDA torch tensors")
+    import torch
+    formats = {torch.float16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+               torch.bfloat16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_BF16),
+               torch.float32: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+               torch.float64: (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+    if logits.dtype not in formats:
+        _type_error("logits", str(logits.dtype).replace("torch.", ""), "float16, bfloat16, float32, float64")
+    code, fmt = formats[logits.dtype]
+    x = logits.detach()
+    if x.dim() == 3:
+        copy, shape, st_t, st_b = logits_layout(tuple(x.shape), x.stride(), batch_first)
+        if copy:
+            x = x.contiguous()
+    else:   # the C ABI raises the reference's "inputs is not a 3-Tensor"
+        x = x.contiguous()
+        shape, st_t, st_b = tuple(x.shape), 0, 0
+    dev = x.device
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    sl = _lengths_device(lengths, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if not stream:   # torch's legacy default stream: the null stream itself, not the decoder's own
+        flags = int(flags) | _lib.CTCEXT_FLAG_DENSE_NULL_STREAM
+    a = _args(x.data_ptr(), shape, code, True, sl.data_ptr(), tuple(sl.shape), 1, 1, merge_repeated, blank_index,
+              blank_label, flags, stream)
+    a.inputs_format = fmt
+    a.inputs_stride_t, a.inputs_stride_b = int(st_t), int(st_b)
+    fdt = torch.float32 if code == _lib.CTCEXT_F32 else torch.float64
+    # every check that needs no data, on the host, before anything is allocated
+    rc = lib.ctcext_validate(ctypes.byref(a))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    T, B = int(shape[0]), int(shape[1])
+    want = (((B, 1, T), torch.int64), ((B, 1), torch.int32), ((B, 1, T), torch.int64), ((B, 1), torch.int32),
+            ((B, 1), fdt), ((B,), torch.int32))
+    if out is None:
+        with torch.cuda.device(dev):
+            out = DenseDecode(*[torch.empty(s, dtype=dt, device=dev) for s, dt in want])
+    else:
+        out = DenseDecode(*out)
+        for name, t, (s, dt) in zip(DenseDecode._fields, out, want):
+            if not (_is_torch(t) and t.is_cuda and t.device == dev and tuple(t.shape) == s and t.dtype == dt
+                    and t.is_contiguous()):
+                raise ValueError("out.%s must be a contiguous %s tensor of shape %s on %s"
+                                 % (name, str(dt).replace("torch.", ""), s, dev))
+    o = _lib.DenseOutputs()
+    (o.decoded, o.decoded_length, o.alignment, o.alignment_length, o.log_probability,
+     o.status) = [t.data_ptr() for t in out]
+    o.pad_value = int(pad_value)
+    dec = get_decoder(index)
+    dec._scores_keep = dec._scores_dense = dec._scores_sync = None
+    rc = lib.ctcext_decode_greedy(dec.handle, ctypes.byref(a), ctypes.byref(o))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    dec._kept = None
+    dec.last_stats = dec.stats()
+    dec._times_dense = (B, 1, T, dev)   # (the follow-up calls' state, as decode_dense sets it)
+    if token_scores:
+        dec._scores_keep = x
+        dec._scores_dense = (B, 1, T, dev, fdt)
+    del x, sl
+    return out
+
+
+def greedy_row(x, norm, frames, blank_index, blank_label=-1, merge_repeated=False):
+    """The definition of the greedy decode for one item, on the host (no GPU),
+    in the compute dtype: ``x`` is the item's logits ``[frames, num_classes]``
+    (float32 or float64), ``norm`` its rows' normaliser ``[frames]``.  Returns
+    ``(decoded, alignment, logp)``: two int64 arrays and a numpy scalar of
+    ``x``'s dtype."""
+    lib = _greedy_lib(_lib.load())
+    x = np.asarray(x)
+    dt = np.float64 if x.dtype == np.float64 else np.float32
+    frames = int(frames)
+    if x.ndim != 2:
+        raise ValueError("greedy_row: x must be [frames, num_classes]")
+    C = int(x.shape[1])
+    x = np.ascontiguousarray(x[:frames], dtype=dt)
+    nm = np.ascontiguousarray(np.asarray(norm).reshape(-1)[:frames], dtype=dt)
+    if x.shape[0] != frames or nm.size != frames:
+        raise ValueError("greedy_row: x and norm must hold the item's frames")
+    dec, ali = np.empty((max(frames, 1),), np.int64), np.empty((max(frames, 1),), np.int64)
+    nd, na = ctypes.c_int64(), ctypes.c_int64()
+    logp = np.empty((1,), dt)
+    rc = lib.ctcext_greedy_row(x.ctypes.data, nm.ctypes.data, 1 if dt == np.float64 else 0, frames, C,
+                               int(blank_index), int(blank_label), 1 if merge_repeated else 0,
+                               _ptr(dec, ctypes.c_int64), ctypes.byref(nd), _ptr(ali, ctypes.c_int64),
+                               ctypes.byref(na), logp.ctypes.data)
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_greedy_row: bad arguments", rc)
+    return dec[:nd.value].copy(), ali[:na.value].copy(), logp[0]
+
+
 TokenTimes = collections.namedtuple("TokenTimes", ["start", "end", "trailing_blank"])
 TokenScores = collections.namedtuple("TokenScores", ["logp_sum", "logp_min"])
 

@@ -1266,6 +1266,84 @@ int ctcext_path_alignment_row(const void* x, const void* norm, int32_t f64, int6
  * token-scores kernels (ms[5]; 0 for those not asked for).  Waits for them. */
 int ctcext_dense_path_alignments_ms(ctcext_decoder* dec, double* ms);
 
+/* ---------------------------------------------------------------------------
+ * Greedy decode: the best-path decoder beside the beam search -- per frame the
+ * class of the largest logit, collapsed over time -- as an enqueue-only call
+ * with the dense decode's outputs.  It costs one read of the logits, where the
+ * beam search walks a serial chain per item: partial results between beam
+ * decodes, a first pass before rescoring, large vocabularies.  beam_width = 1
+ * does not replace it (that is still the prefix beam search, and its output is
+ * not the best path).  New entry points only (CTCEXT_ABI_VERSION is unchanged;
+ * detect them by CTCEXT_HAS_GREEDY at build time or by symbol at run time).
+ *
+ * Definition, for item b with n frames.  n is its sanitised length: a negative
+ * length reads as 0; a length above max_time sets CTCEXT_ITEM_LENGTH and
+ * leaves the item's rows empty, exactly as in the dense decode.  ftype is the
+ * compute dtype, x the item's rows, widened exactly as the decode widens them.
+ *
+ *   def greedy_row(x, norm, n, C, blank_index, blank_label, merge_repeated):
+ *       ks, ali, dec, prev_k, prev_lab, logp = [], [], [], None, None, ftype(0)
+ *       for f in range(n):
+ *           m, k = x[f][0], 0
+ *           for j in range(1, C):                  # class order, strict: the lowest index wins a tie;
+ *               if x[f][j] > m: m, k = x[f][j], j  # a comparison with NaN is false (a leading NaN stays, k = 0)
+ *           lp = ftype(m - norm[f])                # one rounded subtraction in ftype
+ *           logp = lp if f == 0 else ftype(logp + lp)   # frame order, one rounded add each, no fma
+ *           ali.append(blank_label if k == blank_index else k)
+ *           if k != blank_index and k != prev_k:   # CTC collapse, always
+ *               if not (merge_repeated and k == prev_lab):   # the op's merge_repeated: drops a label equal to
+ *                   dec.append(k)                            # the one before it in the collapsed row
+ *               prev_lab = k                                 # (A blank A -> A)
+ *           prev_k = k
+ *       return dec, ali, logp                      # n == 0: [], [], 0
+ *
+ * - norm[f] is the decoder's own normaliser of that row, bit for bit: a
+ *   sequential max, a class-order sum of exp(x_j - max) with the glibc
+ *   replicas, then max + log(sum).
+ * - The alignment row is always n long.
+ * - log_probability is the best path's log-probability.  There is one path per
+ *   item: top_paths must be 1.
+ *
+ * Every step's order is fixed, so the kernels are held to this bit for bit,
+ * NaN cells and signs included (ctcext_greedy_row).
+ *
+ * After ctcext_decode_greedy the handle is in the state a ctcext_decode_dense
+ * with top_paths = 1 leaves it in: ctcext_dense_check, ctcext_dense_token_times,
+ * ctcext_dense_token_scores, ctcext_dense_path_scores and
+ * ctcext_dense_path_alignments follow it unchanged, and ctcext_fetch answers
+ * CTCEXT_FAILED_PRECONDITION.  ctcext_stats after it: tier 0, kernel without
+ * CTCEXT_KERNEL_LAUNCHED, counters 0; with CTCEXT_FLAG_PROFILE norm_kernel_ms
+ * is the per-row kernel's time and decode_kernel_ms the collapse's.
+ *
+ * Not covered: streams; skip_blank; host inputs and a synchronous form;
+ * handles of more than one device (CTCEXT_UNIMPLEMENTED); the bigram scorer. */
+#define CTCEXT_HAS_GREEDY 1
+
+/* Host only: ctcext_dense_validate's checks, then: top_paths must be 1, scorer
+ * must be CTCEXT_SCORER_BASE, flags may hold only CTCEXT_FLAG_PROFILE and
+ * CTCEXT_FLAG_DENSE_NULL_STREAM (each CTCEXT_INVALID_ARGUMENT).  beam_width is
+ * validated as always and not read. */
+int ctcext_greedy_validate(const ctcext_decode_args* args, const ctcext_dense_outputs* out);
+/* ctcext_dense_reserve / ctcext_decode_dense for the greedy decode, with their
+ * contract: after a reserve, or a call of the same or a larger shape, the call
+ * allocates and frees nothing, blocks on nothing, copies nothing to the host
+ * and can be captured into a HIP graph.  It enqueues the length check, the
+ * per-row kernel and the collapse on args->stream. */
+int ctcext_greedy_reserve(ctcext_decoder* dec, const ctcext_decode_args* args);
+int ctcext_decode_greedy(ctcext_decoder* dec, const ctcext_decode_args* args, const ctcext_dense_outputs* out);
+/* Host only, no HIP call: the definition above for one item, in the compute
+ * dtype, in plain C++ that shares no code with the kernels.  x is the item's
+ * rows, dense [frames][num_classes], and norm [frames], both of the compute
+ * dtype (f64: doubles, else floats); decoded and alignment have room for
+ * frames values each and receive decoded_length / alignment_length of them,
+ * logp one value of the compute dtype. */
+int ctcext_greedy_row(const void* x, const void* norm, int32_t f64, int64_t frames, int64_t num_classes,
+                      int32_t blank_index, int64_t blank_label, int32_t merge_repeated, int64_t* decoded,
+                      int64_t* decoded_length, int64_t* alignment, int64_t* alignment_length, void* logp);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the call's flags, the times in ms of
+ * the last greedy call's per-row kernel and collapse (ms[2]).  Waits for them. */
+int ctcext_greedy_ms(ctcext_decoder* dec, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,12 @@ times and scores) on the same two inputs: the forward, walk back, emit,
 token-times and token-scores launches, beside the path-scores kernels of the
 same run and inputs, the decode kernel and the whole call.
 
+With --greedy, instead: the greedy decode (decode_greedy) on the same two
+inputs: its per-row kernel and its collapse under CTCEXT_FLAG_PROFILE and the
+whole call (events around it), beside the beam call of the same run
+(decode_dense, W and P of cfg3): its normaliser kernel -- the same read and the
+same class-order chain as the per-row kernel -- and its whole call.
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -299,6 +305,55 @@ def align_report(args):
     return lines, res
 
 
+def greedy_report(args):
+    """--greedy: one row per input family at cfg3."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    lines = ["%-10s %10s %10s %11s %10s %8s %9s %11s %10s   (median of %d, ms; cfg3 B=%d T=%d C=%d; beam W=%d P=%d)"
+             % ("inputs", "frames", "collapse", "greedy call", "beam norm", "fr/norm", "read GB/s", "beam call", "labels/row",
+                args.runs, B, T, C, W, P)]
+    res = {"runs": args.runs, "shape": [B, T, C, W, P], "logit_bytes": 4 * B * T * C, "sum_chain_adds": T, "greedy": {}}
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    for kind in ("gaussian", "peaky"):
+        x = times_inputs(kind, T, B, C)
+        ctcext_amd.decode_greedy(x, sl, batch_first=False, **KW)   # warm-up: workspaces, kernels
+        ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, **KW)
+        ctcext_amd.dense_check()
+        fr_ms, co_ms, call_ms, norm_ms, beam_ms = [], [], [], [], []
+        for _ in range(args.runs):   # alternating
+            ms, out = timed(lambda: ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, **KW))
+            call_ms.append(ms)
+            two = (ctypes.c_double * 2)()
+            if dec.lib.ctcext_greedy_ms(dec.handle, two) != _lib.CTCEXT_OK:
+                raise SystemExit(dec.lib.ctcext_last_error().decode())
+            fr_ms.append(two[0])
+            co_ms.append(two[1])
+            ctcext_amd.dense_check()
+            ms, _ = timed(lambda: ctcext_amd.decode_dense(x, sl, W, P, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, **KW))
+            beam_ms.append(ms)
+            norm_ms.append(ctcext_amd.dense_check()["norm_kernel_ms"])
+        lens = out.decoded_lengths.float()
+        ratio = statistics.median(fr_ms) / statistics.median(norm_ms)
+        gbs = res["logit_bytes"] / statistics.median(fr_ms) / 1e6
+        lines.append("%-10s %10.4f %10.4f %11.4f %10.4f %8.3f %9.1f %11.3f %4d..%-5d"
+                     % (kind, statistics.median(fr_ms), statistics.median(co_ms), statistics.median(call_ms),
+                        statistics.median(norm_ms), ratio, gbs, statistics.median(beam_ms), int(lens.min()), int(lens.max())))
+        res["greedy"][kind] = {"frames": stat(fr_ms), "collapse": stat(co_ms), "call": stat(call_ms),
+                               "beam_norm": stat(norm_ms), "beam_call": stat(beam_ms), "frames_over_norm": round(ratio, 3),
+                               "read_gb_per_s": round(gbs, 1), "labels_min": int(lens.min()), "labels_max": int(lens.max())}
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -313,11 +368,13 @@ def main():
                     help="the token-scores kernel's cost at cfg3, beside the token-times and pack kernels' of the same run")
     ap.add_argument("--paths", action="store_true",
                     help="the path-scores kernels' cost at cfg3, beside the decode, token-scores and pack kernels' of the same run")
+    ap.add_argument("--greedy", action="store_true",
+                    help="the greedy decode's two kernels at cfg3, beside the beam call's normaliser kernel of the same run")
     ap.add_argument("--align", action="store_true",
                     help="the path-alignment kernels' cost at cfg3, beside the path-scores kernels' of the same run")
     args = ap.parse_args()
-    if args.times or args.scores or args.paths or args.align:
-        lines, res = align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.times or args.scores or args.paths or args.align or args.greedy:
+        lines, res = greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
