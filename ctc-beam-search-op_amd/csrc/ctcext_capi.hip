@@ -24,6 +24,7 @@
 #include "ctcx_paths.h"
 #include "ctcx_align.h"
 #include "ctcx_greedy.h"
+#include "ctcx_greedy_stream.h"
 #include "ctcx_scores.h"
 #include "ctcx_skip.h"
 #include "ctcx_stable.h"
@@ -3779,5 +3780,308 @@ extern "C" int ctcext_dense_path_alignments_ms(ctcext_decoder* d, double* ms) {
     if (i + 1 < n) HIP_OR_FAIL(hipEventElapsedTime(&f, root.al[i], root.al[i + 1]));
     ms[i] = f;
   }
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Streaming: greedy (ctcext.h, "Streaming: greedy").  An object of its own
+// beside ctcext_stream: the items' state words, the deferred record and the
+// rows, all allocated at open; a push is ctcx_greedy_stream.hip's one kernel.
+
+static_assert(kGreedyStreamInNative == CTCEXT_IN_NATIVE && kGreedyStreamInF16 == CTCEXT_IN_F16 &&
+                  kGreedyStreamInBF16 == CTCEXT_IN_BF16 && kGreedyStreamItemLength == CTCEXT_ITEM_LENGTH &&
+                  kGreedyStreamItemCapacity == CTCEXT_ITEM_CAPACITY,
+              "ctcx_greedy_stream.h restates the element formats and the status bits");
+
+struct ctcext_greedy_stream {
+  ctcext_decoder* dec = nullptr;
+  ctcext_stream_args a{};
+  ctcext_greedy_stream_want want{};
+  DevBuf item, acc, rs;         // [B] CtcxGreedyStreamItem, CtcxGreedyStreamAcc, the host reset's mask
+  DevBuf decoded, alignment, dlen, alen, logp, status, frames, start, end, trail, lsum, lmin;
+  HostBuf land;                 // the check's landing buffer: items | acc
+  bool used = false;            // a push has been enqueued
+  hipStream_t s = nullptr;      // the HIP stream of the last one
+  bool timed = false;           // ... which recorded the events
+  hipEvent_t ev[2] = {};
+  bool wide = false;            // the row evaluator of the stream's life (greedy_stream_wide at open)
+};
+
+// Rows of at least this many classes take the wide-row evaluator (DESIGN.md,
+// "Streaming: greedy": where the measurement put the switch-over).
+constexpr int64_t kGreedyStreamWideClasses = 64;
+
+// Diagnostics: CTCEXT_GREEDY_ROWS=lane / =wide, read at open, forces an evaluator (tests, tools/stream_bench.py).
+static bool greedy_stream_wide(int64_t num_classes) {
+  const char* e = getenv("CTCEXT_GREEDY_ROWS");
+  if (e && !strcmp(e, "lane")) return false;
+  if (e && !strcmp(e, "wide")) return true;
+  return num_classes >= kGreedyStreamWideClasses;
+}
+
+extern "C" int ctcext_greedy_stream_validate(const ctcext_stream_args* a, const ctcext_greedy_stream_want* w) {
+  if (!a || !w) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_stream_validate(a);
+  if (rc != CTCEXT_OK) return rc;
+  if (a->top_paths != 1)
+    return fail(CTCEXT_INVALID_ARGUMENT, "a greedy stream returns one path per item: top_paths must be 1");
+  if (a->scorer != CTCEXT_SCORER_BASE)
+    return fail(CTCEXT_INVALID_ARGUMENT, "a greedy stream takes no beam scorer: scorer must be CTCEXT_SCORER_BASE");
+  if (a->flags & ~CTCEXT_FLAG_PROFILE)
+    return fail(CTCEXT_INVALID_ARGUMENT, "a greedy stream's flags may hold only CTCEXT_FLAG_PROFILE");
+  if (!a->on_device) return fail(CTCEXT_INVALID_ARGUMENT, "ctcext_greedy_stream_push needs device chunks");
+  if (w->token_times || w->token_scores) {
+    rc = ctcext_token_times_validate(a->num_classes, a->blank_index, a->blank_label);
+    if (rc != CTCEXT_OK) return rc;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+static void greedy_stream_free(ctcext_greedy_stream* g) {
+  for (DevBuf* q : {&g->item, &g->acc, &g->rs, &g->decoded, &g->alignment, &g->dlen, &g->alen, &g->logp, &g->status,
+                    &g->frames, &g->start, &g->end, &g->trail, &g->lsum, &g->lmin})
+    q->release();
+  g->land.release();
+  for (auto& e : g->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete g;
+}
+
+// Allocates one buffer of n elements of V and fills it with v.
+template <typename V>
+static int greedy_stream_filled(DevBuf& q, size_t n, V v) {
+  HIP_OR_FAIL(q.ensure(sizeof(V) * n + 16));
+  const std::vector<V> h(n, v);
+  if (n) HIP_OR_FAIL(hipMemcpy(q.p, h.data(), sizeof(V) * n, hipMemcpyHostToDevice));
+  return CTCEXT_OK;
+}
+
+static int greedy_stream_alloc(ctcext_greedy_stream* g) {
+  const size_t B = (size_t)g->a.batch_size, cells = B * (size_t)g->a.max_frames;
+  const bool f64 = g->a.dtype == CTCEXT_F64;
+  int rc = greedy_stream_filled<uint64_t>(g->item, B * sizeof(CtcxGreedyStreamItem) / 8, 0);
+  if (rc == CTCEXT_OK) rc = greedy_stream_filled<uint64_t>(g->acc, B * sizeof(CtcxGreedyStreamAcc) / 8, 0);
+  if (rc == CTCEXT_OK) rc = greedy_stream_filled<int32_t>(g->rs, B, 0);
+  if (rc == CTCEXT_OK) rc = greedy_stream_filled<int64_t>(g->decoded, cells, g->want.pad_value);
+  if (rc == CTCEXT_OK) rc = greedy_stream_filled<int64_t>(g->alignment, cells, g->want.pad_value);
+  for (DevBuf* q : {&g->dlen, &g->alen, &g->status, &g->frames})
+    if (rc == CTCEXT_OK) rc = greedy_stream_filled<int32_t>(*q, B, 0);
+  if (rc == CTCEXT_OK) rc = greedy_stream_filled<uint64_t>(g->logp, B, 0);   // (+0 in either dtype)
+  if (rc == CTCEXT_OK && g->want.token_times) {
+    rc = greedy_stream_filled<int32_t>(g->start, cells, -1);
+    if (rc == CTCEXT_OK) rc = greedy_stream_filled<int32_t>(g->end, cells, -1);
+    if (rc == CTCEXT_OK) rc = greedy_stream_filled<int32_t>(g->trail, B, 0);
+  }
+  if (rc == CTCEXT_OK && g->want.token_scores)
+    for (DevBuf* q : {&g->lsum, &g->lmin}) {
+      if (rc != CTCEXT_OK) break;
+      rc = f64 ? greedy_stream_filled<double>(*q, cells, __builtin_nan(""))
+               : greedy_stream_filled<float>(*q, cells, __builtin_nanf(""));
+    }
+  if (rc != CTCEXT_OK) return rc;
+  HIP_OR_FAIL(g->land.ensure((sizeof(CtcxGreedyStreamItem) + sizeof(CtcxGreedyStreamAcc)) * B + 16));
+  for (auto& e : g->ev) HIP_OR_FAIL(hipEventCreate(&e));
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_greedy_stream_open(ctcext_decoder* d, const ctcext_stream_args* a,
+                                         const ctcext_greedy_stream_want* w, ctcext_greedy_stream** out) {
+  if (!out) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_greedy_stream_validate(a, w);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "a greedy stream needs a one-device decoder handle");
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(d->devs[0].device));
+  ctcext_greedy_stream* g = new ctcext_greedy_stream();
+  g->dec = d;
+  g->a = *a;
+  g->want = *w;
+  g->wide = greedy_stream_wide(a->num_classes);
+  rc = greedy_stream_alloc(g);
+  if (rc != CTCEXT_OK) {
+    const std::string keep = g_err;
+    greedy_stream_free(g);
+    g_err = keep;
+    return rc;
+  }
+  *out = g;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// The one launch of a push (c == null: no chunk, the host reset's), on s.
+static int greedy_stream_launch(ctcext_greedy_stream* g, const ctcext_chunk* c, const int32_t* reset, hipStream_t s) {
+  const ctcext_stream_args& a = g->a;
+  const int64_t B = a.batch_size, C = a.num_classes, Tc = c ? c->chunk_time : 0;
+  CtcxGreedyStreamParams p{};
+  if (c) {
+    // the chunk's element strides, as ctcext_stream_push_dense takes them
+    int64_t st_t = c->inputs_stride_t ? c->inputs_stride_t : B * C;
+    int64_t st_b = c->inputs_stride_b ? c->inputs_stride_b : C;
+    if (Tc <= 1 && B <= 1) st_t = st_b = C;
+    else if (Tc <= 1) st_t = st_b * B;
+    else if (B <= 1) st_b = st_t * Tc;
+    p.x = c->inputs; p.chunk_length = c->chunk_length;
+    p.xst_t = st_t; p.xst_b = st_b; p.xfmt = c->inputs_format;
+  }
+  p.reset = reset;
+  p.chunk_time = Tc; p.max_frames = a.max_frames; p.B = B; p.C = C;
+  p.f64 = a.dtype == CTCEXT_F64 ? 1 : 0;
+  p.blank_index = a.blank_index; p.blank_label = a.blank_label; p.merge = a.merge_repeated ? 1 : 0;
+  p.want = (g->want.token_times ? kGreedyStreamTimes : 0) | (g->want.token_scores ? kGreedyStreamScores : 0);
+  p.wide = g->wide ? 1 : 0;
+  p.pad_value = g->want.pad_value;
+  p.item = (CtcxGreedyStreamItem*)g->item.p; p.acc = (CtcxGreedyStreamAcc*)g->acc.p;
+  p.decoded = (int64_t*)g->decoded.p; p.alignment = (int64_t*)g->alignment.p;
+  p.decoded_length = (int32_t*)g->dlen.p; p.alignment_length = (int32_t*)g->alen.p;
+  p.log_probability = g->logp.p; p.status = (int32_t*)g->status.p; p.frames = (int32_t*)g->frames.p;
+  p.start = (int32_t*)g->start.p; p.end = (int32_t*)g->end.p; p.trailing_blank = (int32_t*)g->trail.p;
+  p.logp_sum = g->lsum.p; p.logp_min = g->lmin.p;
+  HIP_OR_FAIL(ctcx_launch_greedy_push(p, s));
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_greedy_stream_push(ctcext_greedy_stream* g, const ctcext_chunk* c, const int32_t* reset,
+                                         ctcext_greedy_stream_outputs* o) {
+  if (!g || !c) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ctcext_stream_args& a = g->a;
+  if (c->flags & ~(CTCEXT_FLAG_PROFILE | CTCEXT_FLAG_DENSE_NULL_STREAM))
+    return fail(CTCEXT_INVALID_ARGUMENT, "chunk flags of a greedy stream: CTCEXT_FLAG_PROFILE and _DENSE_NULL_STREAM only");
+  int rc = check_chunk(&a, c, nullptr);
+  if (rc != CTCEXT_OK) return rc;
+  if (o) {
+    o->decoded = (int64_t*)g->decoded.p; o->decoded_length = (int32_t*)g->dlen.p;
+    o->alignment = (int64_t*)g->alignment.p; o->alignment_length = (int32_t*)g->alen.p;
+    o->log_probability = g->logp.p; o->status = (int32_t*)g->status.p; o->frames = (int32_t*)g->frames.p;
+    o->start = (int32_t*)g->start.p; o->end = (int32_t*)g->end.p; o->trailing_blank = (int32_t*)g->trail.p;
+    o->logp_sum = g->lsum.p; o->logp_min = g->lmin.p;
+  }
+  if (a.batch_size == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  Dev& root = g->dec->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  // (the null stream itself with the flag: dense_begin)
+  hipStream_t s = c->stream ? (hipStream_t)c->stream
+                  : (c->flags & CTCEXT_FLAG_DENSE_NULL_STREAM) ? (hipStream_t) nullptr : root.own_stream;
+  const bool prof = ((a.flags | c->flags) & CTCEXT_FLAG_PROFILE) != 0;
+  g->used = true;
+  g->s = s;
+  g->timed = false;
+  if (prof) HIP_OR_FAIL(hipEventRecord(g->ev[0], s));
+  rc = greedy_stream_launch(g, c, reset, s);
+  if (rc != CTCEXT_OK) return rc;
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(g->ev[1], s));
+    g->timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+// Waits for the pushes so far and lands the items and the deferred record.
+static int greedy_stream_settle(ctcext_greedy_stream* g) {
+  const size_t B = (size_t)g->a.batch_size;
+  if (g->used) HIP_OR_FAIL(hipStreamSynchronize(g->s));
+  char* const h = (char*)g->land.p;
+  HIP_OR_FAIL(hipMemcpy(h, g->item.p, sizeof(CtcxGreedyStreamItem) * B, hipMemcpyDeviceToHost));
+  HIP_OR_FAIL(hipMemcpy(h + sizeof(CtcxGreedyStreamItem) * B, g->acc.p, sizeof(CtcxGreedyStreamAcc) * B,
+                        hipMemcpyDeviceToHost));
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_greedy_stream_check(ctcext_greedy_stream* g) {
+  if (!g) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const int64_t B = g->a.batch_size;
+  if (!g->used || B == 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(g->dec->devs[0].device));
+  int rc = greedy_stream_settle(g);
+  if (rc != CTCEXT_OK) return rc;
+  const CtcxGreedyStreamAcc* acc =
+      (const CtcxGreedyStreamAcc*)((const char*)g->land.p + sizeof(CtcxGreedyStreamItem) * (size_t)B);
+  int64_t first_len = -1, first_cap = -1;
+  for (int64_t b = 0; b < B; ++b) {
+    if ((acc[b].status & CTCEXT_ITEM_LENGTH) && first_len < 0) first_len = b;
+    if ((acc[b].status & CTCEXT_ITEM_CAPACITY) && first_cap < 0) first_cap = b;
+  }
+  if (first_len < 0 && first_cap < 0) {
+    g_err.clear();
+    return CTCEXT_OK;
+  }
+  // (on the pushes' stream, so that a later push there is ordered behind it)
+  HIP_OR_FAIL(hipMemsetAsync(g->acc.p, 0, sizeof(CtcxGreedyStreamAcc) * (size_t)B, g->s));
+  HIP_OR_FAIL(hipStreamSynchronize(g->s));
+  if (first_len >= 0)
+    return fail(CTCEXT_FAILED_PRECONDITION, "sequence_length(" + std::to_string(first_len) + ") <= " +
+                                                std::to_string(acc[first_len].len_chunk));
+  return fail(CTCEXT_INVALID_ARGUMENT, "stream capacity exceeded: item " + std::to_string(first_cap) + " would hold " +
+                                           std::to_string(acc[first_cap].cap_total) + " frames of max_frames " +
+                                           std::to_string(g->a.max_frames));
+}
+
+extern "C" int ctcext_greedy_stream_frames(ctcext_greedy_stream* g, int64_t* frames) {
+  if (!g || !frames) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (g->a.batch_size == 0) return CTCEXT_OK;
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(g->dec->devs[0].device));
+  const int rc = greedy_stream_settle(g);
+  if (rc != CTCEXT_OK) return rc;
+  const CtcxGreedyStreamItem* it = (const CtcxGreedyStreamItem*)g->land.p;
+  for (int64_t b = 0; b < g->a.batch_size; ++b) frames[b] = it[b].frames;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_greedy_stream_reset(ctcext_greedy_stream* g, const int32_t* items, int64_t n) {
+  if (!g) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const int64_t B = g->a.batch_size;
+  if (items) {
+    if (n < 0) return fail(CTCEXT_INVALID_ARGUMENT, "negative item count");
+    for (int64_t i = 0; i < n; ++i)
+      if (items[i] < 0 || items[i] >= B) return fail(CTCEXT_INVALID_ARGUMENT, "stream item out of range [0, batch_size)");
+  }
+  if (B == 0) return CTCEXT_OK;
+  DeviceGuard guard;
+  Dev& root = g->dec->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  // the push kernel without a chunk, behind the pushes so far: it pads the named items' rows again
+  const hipStream_t s = g->used ? g->s : root.own_stream;
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  std::vector<int32_t> mask((size_t)B, items ? 0 : 1);
+  for (int64_t i = 0; items && i < n; ++i) mask[(size_t)items[i]] = 1;
+  HIP_OR_FAIL(hipMemcpy(g->rs.p, mask.data(), 4 * (size_t)B, hipMemcpyHostToDevice));
+  const int rc = greedy_stream_launch(g, nullptr, (const int32_t*)g->rs.p, s);
+  if (rc != CTCEXT_OK) return rc;
+  HIP_OR_FAIL(hipStreamSynchronize(s));
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" void ctcext_greedy_stream_close(ctcext_greedy_stream* g) {
+  if (!g) return;
+  DeviceGuard guard;
+  (void)hipSetDevice(g->dec->devs[0].device);
+  if (g->used) (void)hipStreamSynchronize(g->s);   // pushes still in flight
+  greedy_stream_free(g);
+}
+
+extern "C" int ctcext_greedy_stream_push_ms(ctcext_greedy_stream* g, double* ms) {
+  if (!g || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!g->used || !g->timed) return fail(CTCEXT_FAILED_PRECONDITION, "no CTCEXT_FLAG_PROFILE push of the greedy stream yet");
+  DeviceGuard guard;
+  HIP_OR_FAIL(hipSetDevice(g->dec->devs[0].device));
+  HIP_OR_FAIL(hipEventSynchronize(g->ev[1]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, g->ev[0], g->ev[1]));
+  *ms = f;
+  g_err.clear();
   return CTCEXT_OK;
 }

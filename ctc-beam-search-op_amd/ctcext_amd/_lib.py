@@ -87,6 +87,11 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PATH_ALIGNMENTS_SYMBOLS
 GREEDY_SYMBOLS = ("ctcext_greedy_validate", "ctcext_greedy_reserve", "ctcext_decode_greedy", "ctcext_greedy_row",
                   "ctcext_greedy_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + GREEDY_SYMBOLS
+# the greedy stream (CTCEXT_HAS_GREEDY_STREAM)
+GREEDY_STREAM_SYMBOLS = ("ctcext_greedy_stream_validate", "ctcext_greedy_stream_open", "ctcext_greedy_stream_push",
+                         "ctcext_greedy_stream_check", "ctcext_greedy_stream_frames", "ctcext_greedy_stream_reset",
+                         "ctcext_greedy_stream_close", "ctcext_greedy_stream_push_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + GREEDY_STREAM_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -175,6 +180,20 @@ class StreamDenseOutputs(ctypes.Structure):
                 ("frames", ctypes.c_void_p),
                 ("stable_length", ctypes.c_void_p), ("stable_frames", ctypes.c_void_p),
                 ("pad_value", ctypes.c_int64)]
+
+
+class GreedyStreamWant(ctypes.Structure):
+    """ctcext_greedy_stream_want: what a greedy stream keeps beside the hypothesis, and its padding."""
+    _fields_ = [("token_times", ctypes.c_int32), ("token_scores", ctypes.c_int32), ("pad_value", ctypes.c_int64)]
+
+
+class GreedyStreamOutputs(ctypes.Structure):
+    """ctcext_greedy_stream_outputs: the device pointers of a greedy stream's own rows."""
+    _fields_ = [("decoded", ctypes.c_void_p), ("decoded_length", ctypes.c_void_p),
+                ("alignment", ctypes.c_void_p), ("alignment_length", ctypes.c_void_p),
+                ("log_probability", ctypes.c_void_p), ("status", ctypes.c_void_p), ("frames", ctypes.c_void_p),
+                ("start", ctypes.c_void_p), ("end", ctypes.c_void_p), ("trailing_blank", ctypes.c_void_p),
+                ("logp_sum", ctypes.c_void_p), ("logp_min", ctypes.c_void_p)]
 
 
 class PathSizes(ctypes.Structure):
@@ -442,6 +461,26 @@ def load():
         lib.ctcext_greedy_row.restype = ctypes.c_int
         lib.ctcext_greedy_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_greedy_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_greedy_stream_open"):   # (CTCEXT_HAS_GREEDY_STREAM; older builds stay loadable for A/B runs)
+        lib.ctcext_greedy_stream_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(GreedyStreamWant)]
+        lib.ctcext_greedy_stream_validate.restype = ctypes.c_int
+        lib.ctcext_greedy_stream_open.argtypes = [ctypes.c_void_p, ctypes.POINTER(StreamArgs),
+                                                  ctypes.POINTER(GreedyStreamWant), ctypes.POINTER(ctypes.c_void_p)]
+        lib.ctcext_greedy_stream_open.restype = ctypes.c_int
+        # (stream, chunk, int32 reset[B] on the device or NULL, outputs or NULL)
+        lib.ctcext_greedy_stream_push.argtypes = [ctypes.c_void_p, ctypes.POINTER(Chunk), ctypes.c_void_p,
+                                                  ctypes.POINTER(GreedyStreamOutputs)]
+        lib.ctcext_greedy_stream_push.restype = ctypes.c_int
+        lib.ctcext_greedy_stream_check.argtypes = [ctypes.c_void_p]
+        lib.ctcext_greedy_stream_check.restype = ctypes.c_int
+        lib.ctcext_greedy_stream_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.ctcext_greedy_stream_frames.restype = ctypes.c_int
+        lib.ctcext_greedy_stream_reset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        lib.ctcext_greedy_stream_reset.restype = ctypes.c_int
+        lib.ctcext_greedy_stream_close.argtypes = [ctypes.c_void_p]
+        lib.ctcext_greedy_stream_close.restype = None
+        lib.ctcext_greedy_stream_push_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_greedy_stream_push_ms.restype = ctypes.c_int
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

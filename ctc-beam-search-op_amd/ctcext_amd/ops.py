@@ -1283,6 +1283,75 @@ def _host_empty():
     return np.empty
 
 
+def _stream_chunk(a, np_dtype, fixed, chunk, lengths, batch_first, flags):
+    """The ``ctcext_chunk`` of one push of a stream with attributes ``a``: ``(c, x, sl, on_device, dev, index)``,
+    x and sl being the tensors or arrays c points into.  ``fixed``: where the stream's chunks live (None: not
+    fixed yet)."""
+    allowed = "float16, bfloat16, float32" if a.dtype == _lib.CTCEXT_F32 else "float64"
+    if _is_torch(chunk):
+        import torch
+        formats = {torch.float16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+                   torch.bfloat16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_BF16),
+                   torch.float32: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+                   torch.float64: (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+        if chunk.dtype not in formats:
+            _type_error("chunk", str(chunk.dtype).replace("torch.", ""), allowed)
+        x = chunk.detach()
+        strides = x.stride()
+        dname = str(x.dtype).replace("torch.", "")
+    else:
+        x = chunk if isinstance(chunk, np.ndarray) else np.asarray(chunk, dtype=np_dtype)
+        formats = {np.dtype(np.float16): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
+                   np.dtype(np.float32): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
+                   np.dtype(np.float64): (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
+        if x.dtype not in formats:
+            _type_error("chunk", x.dtype.name, allowed)
+        strides = tuple(s // x.itemsize if s % x.itemsize == 0 else 0 for s in x.strides)
+        dname = x.dtype.name
+    code, fmt = formats[x.dtype]
+    if fmt == _lib.CTCEXT_IN_NATIVE and code != a.dtype:
+        _type_error("chunk", dname, allowed)
+    if len(x.shape) != 3:
+        raise InvalidArgumentError("inputs is not a 3-Tensor", _lib.CTCEXT_INVALID_ARGUMENT)
+    copy, shape, st_t, st_b = logits_layout(tuple(x.shape), strides, batch_first)
+    if (shape[1], shape[2]) != (a.batch_size, a.num_classes):
+        raise InvalidArgumentError("chunk has batch_size %d and num_classes %d, the stream %d and %d"
+                                   % (shape[1], shape[2], a.batch_size, a.num_classes),
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    if copy:
+        x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
+    if shape[0] == 0:   # no frame: nothing is addressed, whatever strides an empty view reports
+        st_t = st_b = 0
+    on_device = bool(_is_torch(x) and x.is_cuda)
+    if fixed is not None and on_device != fixed:
+        raise ValueError("this stream's chunks live on the %s (fixed by its first push)"
+                         % ("device" if fixed else "host"))
+    c = _lib.Chunk()
+    c.chunk_time = int(shape[0])
+    c.inputs_format, c.flags = fmt, int(flags)
+    c.inputs_stride_t, c.inputs_stride_b = int(st_t), int(st_b)
+    sl = None
+    if on_device:
+        dev = x.device
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        if lengths is not None:
+            sl = _lengths_device(lengths, dev)
+            c.chunk_length = sl.data_ptr()
+        c.inputs = x.data_ptr()
+        c.stream = torch.cuda.current_stream(dev).cuda_stream
+    else:
+        dev = index = None
+        if lengths is not None:
+            sl = _lengths_host(lengths)
+            c.chunk_length = sl.ctypes.data
+        c.inputs = x.data_ptr() if _is_torch(x) else x.ctypes.data
+    if sl is not None and tuple(sl.shape) != (int(a.batch_size),):
+        raise FailedPreconditionError("len(sequence_length) != batch_size.  len(sequence_length):  %d batch_size: %d"
+                                      % (sl.shape[0] if len(sl.shape) else 0, a.batch_size),
+                                      _lib.CTCEXT_FAILED_PRECONDITION)
+    return c, x, sl, on_device, dev, index
+
+
 StablePrefix = collections.namedtuple("StablePrefix", ["decoded_length", "frames"])
 StreamDense = collections.namedtuple(
     "StreamDense",
@@ -1580,72 +1649,7 @@ class StreamDecoder:
         return out
 
     def _chunk(self, chunk, lengths, batch_first, flags):
-        """The ``ctcext_chunk`` of one push: ``(c, x, sl, on_device, dev, index)``,
-        x and sl being the tensors or arrays c points into."""
-        a = self._args
-        allowed = "float16, bfloat16, float32" if a.dtype == _lib.CTCEXT_F32 else "float64"
-        if _is_torch(chunk):
-            import torch
-            formats = {torch.float16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
-                       torch.bfloat16: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_BF16),
-                       torch.float32: (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
-                       torch.float64: (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
-            if chunk.dtype not in formats:
-                _type_error("chunk", str(chunk.dtype).replace("torch.", ""), allowed)
-            x = chunk.detach()
-            strides = x.stride()
-            dname = str(x.dtype).replace("torch.", "")
-        else:
-            x = chunk if isinstance(chunk, np.ndarray) else np.asarray(chunk, dtype=self._np_dtype)
-            formats = {np.dtype(np.float16): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_F16),
-                       np.dtype(np.float32): (_lib.CTCEXT_F32, _lib.CTCEXT_IN_NATIVE),
-                       np.dtype(np.float64): (_lib.CTCEXT_F64, _lib.CTCEXT_IN_NATIVE)}
-            if x.dtype not in formats:
-                _type_error("chunk", x.dtype.name, allowed)
-            strides = tuple(s // x.itemsize if s % x.itemsize == 0 else 0 for s in x.strides)
-            dname = x.dtype.name
-        code, fmt = formats[x.dtype]
-        if fmt == _lib.CTCEXT_IN_NATIVE and code != a.dtype:
-            _type_error("chunk", dname, allowed)
-        if len(x.shape) != 3:
-            raise InvalidArgumentError("inputs is not a 3-Tensor", _lib.CTCEXT_INVALID_ARGUMENT)
-        copy, shape, st_t, st_b = logits_layout(tuple(x.shape), strides, batch_first)
-        if (shape[1], shape[2]) != (a.batch_size, a.num_classes):
-            raise InvalidArgumentError("chunk has batch_size %d and num_classes %d, the stream %d and %d"
-                                       % (shape[1], shape[2], a.batch_size, a.num_classes),
-                                       _lib.CTCEXT_INVALID_ARGUMENT)
-        if copy:
-            x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
-        if shape[0] == 0:   # no frame: nothing is addressed, whatever strides an empty view reports
-            st_t = st_b = 0
-        on_device = bool(_is_torch(x) and x.is_cuda)
-        if self.on_device is not None and on_device != self.on_device:
-            raise ValueError("this stream's chunks live on the %s (fixed by its first push)"
-                             % ("device" if self.on_device else "host"))
-        c = _lib.Chunk()
-        c.chunk_time = int(shape[0])
-        c.inputs_format, c.flags = fmt, int(flags)
-        c.inputs_stride_t, c.inputs_stride_b = int(st_t), int(st_b)
-        sl = None
-        if on_device:
-            dev = x.device
-            index = dev.index if dev.index is not None else torch.cuda.current_device()
-            if lengths is not None:
-                sl = _lengths_device(lengths, dev)
-                c.chunk_length = sl.data_ptr()
-            c.inputs = x.data_ptr()
-            c.stream = torch.cuda.current_stream(dev).cuda_stream
-        else:
-            dev = index = None
-            if lengths is not None:
-                sl = _lengths_host(lengths)
-                c.chunk_length = sl.ctypes.data
-            c.inputs = x.data_ptr() if _is_torch(x) else x.ctypes.data
-        if sl is not None and tuple(sl.shape) != (int(a.batch_size),):
-            raise FailedPreconditionError("len(sequence_length) != batch_size.  len(sequence_length):  %d batch_size: %d"
-                                          % (sl.shape[0] if len(sl.shape) else 0, a.batch_size),
-                                          _lib.CTCEXT_FAILED_PRECONDITION)
-        return c, x, sl, on_device, dev, index
+        return _stream_chunk(self._args, self._np_dtype, self.on_device, chunk, lengths, batch_first, flags)
 
     # -- the enqueue-only push -----------------------------------------------
     def push_dense(self, chunk, lengths=None, *, reset=None, batch_first=True, results=True, stable=False,
@@ -1886,6 +1890,230 @@ class StreamDecoder:
         self._check_open()
         ms = ctypes.c_double()
         rc = self.lib.ctcext_stream_commit_ms(self.handle, ctypes.byref(ms))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        return ms.value
+
+
+GreedyPush = collections.namedtuple(
+    "GreedyPush",
+    ["decoded", "decoded_lengths", "alignment", "alignment_lengths", "log_probability", "status", "frames", "times",
+     "scores"])
+
+
+class _DeviceRows:
+    """Device memory the library owns, as ``__cuda_array_interface__``: torch wraps it without a copy."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr or 0), False),
+                                         "version": 2, "strides": None}
+
+
+class GreedyStream:
+    """Streaming greedy decode: push the logits of a batch in chunks of frames
+    and read, after each push, the best-path hypothesis of everything pushed so
+    far, with its token times and token confidences -- bit for bit what
+    ``decode_greedy``, ``dense_token_times`` and ``dense_token_scores`` give for
+    the concatenated frames (include/ctcext.h, "Streaming: greedy").  A push is
+    one kernel over the chunk alone: its cost does not grow with the frames
+    pushed so far, and the stream keeps neither logits nor beam records.
+
+        with GreedyStream(batch_size, num_classes, max_frames, token_scores=True) as s:
+            for chunk in chunks:                 # [B, t, C] each (batch_first), t may vary
+                out = s.push(chunk, lengths)     # lengths: frames of this chunk per item (None: all t)
+            s.check()
+
+    ``max_frames`` is the capacity per item and the width of every row.
+    ``dtype`` is the compute and output type; ``"float32"`` streams take
+    float16 / bfloat16 / float32 chunks, ``"float64"`` ones float64.  With
+    ``token_times`` / ``token_scores`` the stream keeps ``TokenTimes`` /
+    ``TokenScores`` as well; both need a ``blank_label`` that is no class label.
+    Not covered: ``skip_blank``, host chunks, a scorer, path scores and path
+    alignments over the stream."""
+
+    def __init__(self, batch_size, num_classes, max_frames, *, dtype="float32", merge_repeated=False, blank_index=0,
+                 blank_label=-1, pad_value=-1, device=None, token_times=True, token_scores=False, flags=0):
+        self.lib = _lib.load()
+        if not hasattr(self.lib, "ctcext_greedy_stream_open"):
+            raise UnimplementedError("this libctcext.so has no greedy stream (CTCEXT_HAS_GREEDY_STREAM)",
+                                     _lib.CTCEXT_UNIMPLEMENTED)
+        name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
+        if name not in ("float32", "float64"):
+            _type_error("dtype", name, "float32, float64")
+        self._np_dtype = np.dtype(name)
+        a = _lib.StreamArgs()
+        a.dtype = _lib.CTCEXT_F32 if name == "float32" else _lib.CTCEXT_F64
+        a.on_device = 1
+        a.batch_size, a.num_classes, a.max_frames = int(batch_size), int(num_classes), int(max_frames)
+        a.beam_width, a.top_paths = 1, 1
+        a.merge_repeated = 1 if merge_repeated else 0
+        a.blank_index, a.blank_label, a.flags = int(blank_index), int(blank_label), int(flags)
+        w = _lib.GreedyStreamWant()
+        w.token_times, w.token_scores, w.pad_value = int(bool(token_times)), int(bool(token_scores)), int(pad_value)
+        self._args, self._want = a, w
+        # the attribute checks run on the host now; the stream itself opens with the first push
+        rc = self.lib.ctcext_greedy_stream_validate(ctypes.byref(a), ctypes.byref(w))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        self._device = _device_index(device)
+        self.on_device = True
+        self.dec = self.handle = self._out = None
+        self.closed = False
+
+    # -- lifetime ----------------------------------------------------------
+    def _open(self, index):
+        if self._device is not None and index != self._device:
+            raise ValueError("the chunk lives on cuda:%d, the stream on cuda:%d" % (index, self._device))
+        self.dec = get_decoder(index)
+        h = ctypes.c_void_p()
+        rc = self.lib.ctcext_greedy_stream_open(self.dec.handle, ctypes.byref(self._args), ctypes.byref(self._want),
+                                                ctypes.byref(h))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        self.handle = h
+
+    def _wrap(self, o, dev):
+        """The stream's rows as torch tensors over the library's memory (made once)."""
+        import torch
+        a = self._args
+        B, F = int(a.batch_size), int(a.max_frames)
+        f = "<f4" if a.dtype == _lib.CTCEXT_F32 else "<f8"
+
+        def t(ptr, shape, typestr):
+            return None if not ptr else torch.as_tensor(_DeviceRows(ptr, shape, typestr), device=dev)
+        times = scores = None
+        if self._want.token_times:
+            times = TokenTimes(t(o.start, (B, 1, F), "<i4"), t(o.end, (B, 1, F), "<i4"),
+                               t(o.trailing_blank, (B, 1), "<i4"))
+        if self._want.token_scores:
+            scores = TokenScores(t(o.logp_sum, (B, 1, F), f), t(o.logp_min, (B, 1, F), f))
+        return GreedyPush(t(o.decoded, (B, 1, F), "<i8"), t(o.decoded_length, (B, 1), "<i4"),
+                          t(o.alignment, (B, 1, F), "<i8"), t(o.alignment_length, (B, 1), "<i4"),
+                          t(o.log_probability, (B, 1), f), t(o.status, (B,), "<i4"), t(o.frames, (B,), "<i4"),
+                          times, scores)
+
+    def close(self):
+        """Frees the stream and its rows: the tensors a push returned must not be touched afterwards."""
+        if self.handle and self.dec is not None and self.dec.handle:
+            self.lib.ctcext_greedy_stream_close(self.handle)
+        self.handle = self._out = None
+        self.closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_open(self):
+        if self.closed:
+            raise FailedPreconditionError("the stream is closed", _lib.CTCEXT_FAILED_PRECONDITION)
+
+    # -- the push ------------------------------------------------------------
+    def push(self, chunk, lengths=None, *, reset=None, batch_first=True):
+        """Take the chunk's frames without waiting for anything: one kernel on
+        ``torch.cuda.current_stream()``, behind whatever produced the chunk.
+        With ``lengths`` and ``reset`` None or contiguous int32 CUDA tensors,
+        and a chunk whose layout needs no copy, a push after the first
+        allocates nothing and can be captured into a ``torch.cuda.graph`` as a
+        single kernel node; a CUDA tensor of another integer dtype or layout is
+        converted on the device first, which allocates.
+
+        ``chunk`` is a CUDA tensor ``[B, t, C]`` (``[t, B, C]`` without
+        ``batch_first``), strided views included; ``lengths`` and ``reset``
+        are CUDA tensors of ``[B]`` (anything else raises ``ValueError``).
+        ``reset[b] != 0`` starts a new utterance in item b with this chunk.
+
+        Returns ``GreedyPush(decoded [B, 1, max_frames], decoded_lengths,
+        alignment, alignment_lengths, log_probability, status, frames, times,
+        scores)``; ``times`` is a ``TokenTimes`` or None, ``scores`` a
+        ``TokenScores`` or None.  These are the stream's own tensors, the same
+        objects after every push, updated in place by the next one: clone what
+        must outlive the next push, and touch none of them after ``close()``.
+
+        An item whose length is above the chunk's frames
+        (``CTCEXT_ITEM_LENGTH``) or would pass ``max_frames``
+        (``CTCEXT_ITEM_CAPACITY``) takes no frame: ``status[b]`` carries the bit
+        for this push only and its rows stay as they were.  ``check()`` waits
+        and raises."""
+        self._check_open()
+        if not (_is_torch(chunk) and chunk.is_cuda):
+            raise ValueError("GreedyStream.push takes CUDA torch tensors")
+        for name, t in (("lengths", lengths), ("reset", reset)):
+            if t is not None and not (_is_torch(t) and t.is_cuda):
+                raise ValueError("GreedyStream.push takes %s as a CUDA torch tensor" % name)
+        c, x, sl, _, dev, index = _stream_chunk(self._args, self._np_dtype, True, chunk, lengths, batch_first, 0)
+        B = int(self._args.batch_size)
+        rs = None
+        if reset is not None:
+            rs = _lengths_device(reset, dev)
+            if tuple(rs.shape) != (B,):
+                raise ValueError("reset must have shape [batch_size] = [%d], got %s" % (B, tuple(rs.shape)))
+        if not c.stream:   # torch's legacy default stream: the null stream itself, not the decoder's own
+            c.flags |= _lib.CTCEXT_FLAG_DENSE_NULL_STREAM
+        if not self.handle:
+            self._open(index)
+        o = _lib.GreedyStreamOutputs()
+        rc = self.lib.ctcext_greedy_stream_push(self.handle, ctypes.byref(c), None if rs is None else rs.data_ptr(),
+                                                ctypes.byref(o))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+        if self._out is None:
+            self._out = self._wrap(o, dev)
+        # x, sl and rs may be temporaries: they were allocated on this stream, and
+        # the caching allocator hands their memory out again in stream order
+        del x, sl, rs
+        return self._out
+
+    def check(self):
+        """Wait for the torch stream of the last push (pushes made on other
+        streams are the caller's to order) and raise what ``StreamDecoder.check()``
+        raises for a length above its chunk's frames (lowest item) or the
+        stream's capacity exceeded (lowest item), over all pushes since the
+        previous ``check()``, which it then forgets."""
+        self._check_open()
+        if self.handle:
+            rc = self.lib.ctcext_greedy_stream_check(self.handle)
+            if rc != _lib.CTCEXT_OK:
+                _raise(self.lib, rc)
+
+    @property
+    def frames(self):
+        """Frames taken so far per item: numpy int64 [batch_size].  Waits for the stream of the last push."""
+        self._check_open()
+        out = np.zeros((int(self._args.batch_size),), np.int64)
+        if self.handle:
+            rc = self.lib.ctcext_greedy_stream_frames(self.handle, out.ctypes.data)
+            if rc != _lib.CTCEXT_OK:
+                _raise(self.lib, rc)
+        return out
+
+    def reset(self, items=None):
+        """Put ``items`` (None: all) back to no frames and empty rows; the others' rows and state are untouched.
+        Waits; afterwards ``status`` reads 0 and ``frames`` the counts, as after a push without frames."""
+        self._check_open()
+        if not self.handle:
+            return
+        if items is None:
+            rc = self.lib.ctcext_greedy_stream_reset(self.handle, None, 0)
+        else:
+            arr = np.ascontiguousarray(np.asarray(items, dtype=np.int32).reshape(-1))
+            rc = self.lib.ctcext_greedy_stream_reset(self.handle, arr.ctypes.data, int(arr.size))
+        if rc != _lib.CTCEXT_OK:
+            _raise(self.lib, rc)
+
+    def push_ms(self):
+        """Diagnostics: the kernel's time in ms of the last push of a stream made with ``flags=CTCEXT_FLAG_PROFILE``."""
+        self._check_open()
+        ms = ctypes.c_double()
+        rc = self.lib.ctcext_greedy_stream_push_ms(self.handle, ctypes.byref(ms))
         if rc != _lib.CTCEXT_OK:
             _raise(self.lib, rc)
         return ms.value

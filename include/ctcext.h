@@ -1315,8 +1315,9 @@ int ctcext_dense_path_alignments_ms(ctcext_decoder* dec, double* ms);
  * CTCEXT_KERNEL_LAUNCHED, counters 0; with CTCEXT_FLAG_PROFILE norm_kernel_ms
  * is the per-row kernel's time and decode_kernel_ms the collapse's.
  *
- * Not covered: streams; skip_blank; host inputs and a synchronous form;
- * handles of more than one device (CTCEXT_UNIMPLEMENTED); the bigram scorer. */
+ * Not covered: skip_blank; host inputs and a synchronous form; handles of more
+ * than one device (CTCEXT_UNIMPLEMENTED); the bigram scorer.  Chunks of frames
+ * are "Streaming: greedy", below. */
 #define CTCEXT_HAS_GREEDY 1
 
 /* Host only: ctcext_dense_validate's checks, then: top_paths must be 1, scorer
@@ -1343,6 +1344,116 @@ int ctcext_greedy_row(const void* x, const void* norm, int32_t f64, int64_t fram
 /* Diagnostics: with CTCEXT_FLAG_PROFILE in the call's flags, the times in ms of
  * the last greedy call's per-row kernel and collapse (ms[2]).  Waits for them. */
 int ctcext_greedy_ms(ctcext_decoder* dec, double* ms);
+
+/* ---------------------------------------------------------------------------
+ * Streaming: greedy.  The greedy decode over chunks of frames: a stream object
+ * of its own, which holds no beam state, keeps per item the few words a best
+ * path needs between pushes, and one kernel per push appends to rows the
+ * stream owns.  A push costs O(chunk), not O(frames so far): nothing of a
+ * greedy hypothesis ever changes except the last token's end.  New entry points
+ * and structs only (CTCEXT_ABI_VERSION is unchanged; detect them by
+ * CTCEXT_HAS_GREEDY_STREAM at build time or by symbol at run time).
+ *
+ * Definition.  After every push, each item's decoded, alignment, lengths and
+ * log_probability are ctcext_greedy_row's over all frames it has taken since
+ * its last reset, its times are ctcext_token_times_row's of those rows and its
+ * scores ctcext_token_scores_row's of them -- all bit for bit, a NaN that an
+ * operation creates excepted in its sign; there is no new host definition.
+ * An item without frames has empty rows and log_probability 0.
+ *
+ * The rows are the stream's: allocated and padded at open, max_frames wide,
+ * forward and append-only.  A push writes O(chunk) elements per item and nothing
+ * past them; decoded and alignment are padded with pad_value, start and end with
+ * -1, logp_sum and logp_min with NaN.  ctcext_greedy_stream_push hands out the
+ * same device pointers every time.
+ *
+ * Status, decided on the device (chunk_length NULL: chunk_time for all; a
+ * negative length reads as 0; reset[b] != 0 is applied first: the item's frames
+ * become 0, its state is cleared and its rows are padded again up to their old
+ * lengths, and a status bit of the same push does not undo it):
+ *   length > chunk_time                 CTCEXT_ITEM_LENGTH
+ *   frames[b] + length > max_frames     CTCEXT_ITEM_CAPACITY
+ * An item with a bit takes no frame from this push, and status[b] carries the
+ * bit for this push only.  Unlike ctcext_stream_push_dense, which empties such
+ * an item's rows of that push, its rows STAY as they were: here the rows are
+ * the state, and they still hold the hypothesis of the frames taken so far.
+ *
+ * Two row evaluators stand behind the one collapse, chosen at open: a lane per
+ * chunk row (the one-shot kernel's arithmetic), and for rows of 64 classes and
+ * more a wave per row, whose max pass is a reduction over (value, index) and
+ * whose sum is the same class-order chain of rounded adds fed 64 terms at a
+ * time.  Both give the same bits.  Diagnostics: the environment variable
+ * CTCEXT_GREEDY_ROWS=lane / =wide, read at open, forces one.
+ *
+ * Not covered: skip_blank; host chunks and a synchronous push; the bigram
+ * scorer; ctcext_*_path_scores / _path_alignments over a greedy stream (it
+ * keeps neither the logits nor the normaliser); handles of more than one
+ * device (CTCEXT_UNIMPLEMENTED). */
+#define CTCEXT_HAS_GREEDY_STREAM 1
+
+typedef struct ctcext_greedy_stream ctcext_greedy_stream;
+
+typedef struct {            /* fixed for the stream's life */
+  int32_t token_times;      /* keep start / end / trailing_blank */
+  int32_t token_scores;     /* keep logp_sum / logp_min */
+  int64_t pad_value;        /* written past each decoded / alignment row's length */
+} ctcext_greedy_stream_want;
+
+/* Device pointers, the stream's own; rows are max_frames wide, top_paths is 1. */
+typedef struct {
+  int64_t* decoded;           /* [batch][1][max_frames] */
+  int32_t* decoded_length;    /* [batch][1] */
+  int64_t* alignment;         /* [batch][1][max_frames] */
+  int32_t* alignment_length;  /* [batch][1] */
+  void*    log_probability;   /* [batch][1] of dtype */
+  int32_t* status;            /* [batch] CTCEXT_ITEM_* bits of the last push, 0 = good */
+  int32_t* frames;            /* [batch] frames per item after the last push */
+  int32_t* start;             /* [batch][1][max_frames] } NULL without token_times */
+  int32_t* end;               /* [batch][1][max_frames] } */
+  int32_t* trailing_blank;    /* [batch][1]             } */
+  void*    logp_sum;          /* [batch][1][max_frames] of dtype } NULL without token_scores */
+  void*    logp_min;          /* [batch][1][max_frames] of dtype } */
+} ctcext_greedy_stream_outputs;
+
+/* Host only, no HIP call: ctcext_stream_validate, then (CTCEXT_INVALID_ARGUMENT)
+ *   "a greedy stream returns one path per item: top_paths must be 1"
+ *   "a greedy stream takes no beam scorer: scorer must be CTCEXT_SCORER_BASE"
+ *   "a greedy stream's flags may hold only CTCEXT_FLAG_PROFILE"
+ *   "ctcext_greedy_stream_push needs device chunks"      (on_device == 0)
+ * and with token_times or token_scores the blank_label rule of
+ * ctcext_token_times_validate, with its message.  beam_width is validated as
+ * always and not read. */
+int ctcext_greedy_stream_validate(const ctcext_stream_args* args, const ctcext_greedy_stream_want* want);
+/* Validates, then allocates and pads the state and the rows.  May block. */
+int ctcext_greedy_stream_open(ctcext_decoder* dec, const ctcext_stream_args* args,
+                              const ctcext_greedy_stream_want* want, ctcext_greedy_stream** out);
+/* Checks the chunk on the host (the checks of ctcext_stream_dense_validate that
+ * need no data; chunk flags: CTCEXT_FLAG_PROFILE and _DENSE_NULL_STREAM only),
+ * then enqueues one kernel on chunk->stream (NULL: the decoder's own, or the
+ * null stream with CTCEXT_FLAG_DENSE_NULL_STREAM in chunk->flags).  No
+ * allocation, no free, no host-blocking HIP call, no device-to-host copy: a
+ * push is a single kernel node of a captured graph.  reset is device [batch] or
+ * NULL.  out (may be NULL) receives the stream's pointers. */
+int ctcext_greedy_stream_push(ctcext_greedy_stream* s, const ctcext_chunk* chunk, const int32_t* reset,
+                              ctcext_greedy_stream_outputs* out);
+/* Waits for the stream of the last push and reports over all pushes since the
+ * previous check, with ctcext_stream_check's codes and messages for _LENGTH and
+ * _CAPACITY (the first match wins, then the record is cleared). */
+int ctcext_greedy_stream_check(ctcext_greedy_stream* s);
+/* frames[batch]: frames taken so far per item.  Waits. */
+int ctcext_greedy_stream_frames(ctcext_greedy_stream* s, int64_t* frames);
+/* Synchronous: puts the n named items (host list; items == NULL: all) back to
+ * no frames, as reset[b] does; the others' state and rows are untouched.  It
+ * runs the push kernel without a chunk behind the pushes so far, so status[]
+ * reads 0 for every item afterwards (the last push's bits are gone from the
+ * tensor, not from the record ctcext_greedy_stream_check reports) and frames[]
+ * the counts. */
+int ctcext_greedy_stream_reset(ctcext_greedy_stream* s, const int32_t* items, int64_t n);
+/* Close every greedy stream before ctcext_destroy of its decoder. */
+void ctcext_greedy_stream_close(ctcext_greedy_stream* s);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the stream's or the chunk's flags,
+ * the time of the last push's kernel in ms.  Waits for it. */
+int ctcext_greedy_stream_push_ms(ctcext_greedy_stream* s, double* ms);
 
 #ifdef __cplusplus
 }

@@ -42,12 +42,24 @@ kernel's time over the store after the last push beside the one-shot
 dense_token_scores over the caller's tensor for the same rows.  --score-store
 chooses the store's element type (the chunks are converted to it beforehand).
 
-    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense [--times] [--scores [--score-store bfloat16]]] [--input gaussian|peaky|twohot] [--out FILE]
+With --greedy nothing above runs: the report is the greedy stream's
+(GreedyStream, one kernel per push).  Per dtype (float32, bfloat16), in
+alternating rounds of one session: 150 pushes of 10 frames through the greedy
+stream, through one-shot decode_greedy on each [10, 256, 29] chunk (the least
+the one-shot kernels can do for a chunk: three launches) and through
+StreamDecoder.push_dense(results=False) -- the wall time per push from the
+first call to the last result, and from CTCEXT_FLAG_PROFILE runs of their own
+the kernels' time per push; one 1500-frame push against one-shot decode_greedy
+of the whole tensor; and the push kernel's time for 10-frame pushes under each
+row evaluator, alternating (C = 64 .. 5000 at B = 256 and 16).
+
+    python tools/stream_bench.py [--runs 5] [--chunks 1500,100,10] [--stable] [--dense [--times] [--scores [--score-store bfloat16]]] [--input gaussian|peaky|twohot] [--greedy] [--out FILE]
 
 Prints one table and one JSON line.  It is a report, not a check, and it does
 not touch bench.py.
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -288,6 +300,116 @@ def dense_rows(x, sl, chunks, runs):
     return rows
 
 
+def _greedy_walls(x, runs):
+    """Alternating rounds over the 10-frame schedule: wall ms per push of the three forms, and their kernel ms."""
+    sl = torch.full((B,), 10, dtype=torch.int32, device="cuda:0")
+    n = T // 10
+    wall = {"greedy stream": [], "one-shot decode_greedy per chunk": [], "push_dense(results=False)": []}
+    kern = {"greedy stream": [], "one-shot decode_greedy per chunk": []}
+    out = None
+    for r in range(runs + 1):   # (round 0 warms up)
+        for flags in (0, _lib.CTCEXT_FLAG_PROFILE):
+            with ctcext_amd.GreedyStream(B, C, T, device="cuda:0", token_scores=True, flags=flags, **KW) as g:
+                g.push(x[:0], batch_first=False)   # opens the stream: its allocations are not timed
+                torch.cuda.synchronize()
+                t0, k = time.perf_counter(), 0.0
+                for f in range(0, T, 10):
+                    g.push(x[f:f + 10], batch_first=False)
+                    if flags:
+                        k += g.push_ms()
+                torch.cuda.synchronize()
+                (kern if flags else wall)["greedy stream"].append((k if flags else (time.perf_counter() - t0) * 1e3) / n)
+                g.check()
+            torch.cuda.synchronize()
+            t0, k = time.perf_counter(), 0.0
+            for f in range(0, T, 10):
+                out = ctcext_amd.decode_greedy(x[f:f + 10], sl, batch_first=False, flags=flags, out=out, **KW)
+                if flags:
+                    ms = (ctypes.c_double * 2)()
+                    ctcext_amd.get_decoder(0).lib.ctcext_greedy_ms(ctcext_amd.get_decoder(0).handle, ms)
+                    k += ms[0] + ms[1]
+            torch.cuda.synchronize()
+            (kern if flags else wall)["one-shot decode_greedy per chunk"].append(
+                (k if flags else (time.perf_counter() - t0) * 1e3) / n)
+        with ctcext_amd.StreamDecoder(B, C, W, P, T, device="cuda:0", **KW) as s:
+            s.reserve(10)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(0, T, 10):
+                s.push_dense(x[f:f + 10], batch_first=False, results=False)
+            torch.cuda.synchronize()
+            wall["push_dense(results=False)"].append((time.perf_counter() - t0) * 1e3 / n)
+            s.check()
+    return {k: v[1:] for k, v in wall.items()}, {k: v[1:] for k, v in kern.items()}
+
+
+def _greedy_long(x, runs):
+    """One 1500-frame push against one-shot decode_greedy of the tensor, alternating: wall ms."""
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    rows = {"greedy stream, one 1500-frame push": [], "one-shot decode_greedy": []}
+    out = None
+    for r in range(runs + 1):
+        with ctcext_amd.GreedyStream(B, C, T, device="cuda:0", token_scores=True, **KW) as g:
+            g.push(x[:0], batch_first=False)
+            rows["greedy stream, one 1500-frame push"].append(_timed(lambda: g.push(x, batch_first=False))[0])
+        ms, out = _timed(lambda: ctcext_amd.decode_greedy(x, sl, batch_first=False, out=out, **KW))
+        rows["one-shot decode_greedy"].append(ms)
+    return {k: v[1:] for k, v in rows.items()}
+
+
+def _greedy_wide(runs):
+    """The push kernel's ms for one 10-frame push of rows of C classes under each row evaluator (forced through
+    CTCEXT_GREEDY_ROWS, which a stream reads when it opens), the two alternating push by push."""
+    rows = {}
+    for c in (64, 128, 256, 512, 1000, 5000):
+        for b in (256, 16):
+            x = torch.randn((b, 10, c), device="cuda:0")
+            streams = {}
+            for ev in ("lane", "wide"):
+                os.environ["CTCEXT_GREEDY_ROWS"] = ev
+                streams[ev] = ctcext_amd.GreedyStream(b, c, 10 * (runs + 1), device="cuda:0",
+                                                      flags=_lib.CTCEXT_FLAG_PROFILE, **KW)
+                streams[ev].push(x[:, :0])   # opens it
+            del os.environ["CTCEXT_GREEDY_ROWS"]
+            v = {"lane": [], "wide": []}
+            for r in range(runs + 1):
+                for ev, g in streams.items():
+                    g.push(x)
+                    v[ev].append(g.push_ms())
+            for ev, g in streams.items():
+                rows["C=%d B=%d %s" % (c, b, ev)] = v[ev][1:]
+                g.close()
+    return rows
+
+
+def greedy_report(runs, out_path):
+    def stat(v):
+        return {"median_ms": round(statistics.median(v), 5), "min_ms": round(min(v), 5), "max_ms": round(max(v), 5)}
+    res = {"shape": [B, T, C], "runs": runs, "rows": {}}
+    lines = []
+    for dt in (torch.float32, torch.bfloat16):
+        x = make_input("gaussian").to(dt)
+        name = str(dt).replace("torch.", "")
+        wall, kern = _greedy_walls(x, runs)
+        res["rows"][name] = {"wall_ms_per_push": {k: stat(v) for k, v in wall.items()},
+                             "kernel_ms_per_push": {k: stat(v) for k, v in kern.items()},
+                             "long": {k: stat(v) for k, v in _greedy_long(x, runs).items()}}
+        lines.append("B=256 C=29 %s, 150 pushes of 10 frames, %d alternating rounds: median (min .. max) ms per push" % (name, runs))
+        for part in ("wall_ms_per_push", "kernel_ms_per_push", "long"):
+            for k, v in res["rows"][name][part].items():
+                lines.append("  %-20s %-40s %9.4f (%.4f .. %.4f)" % (part, k, v["median_ms"], v["min_ms"], v["max_ms"]))
+    res["wide"] = {k: stat(v) for k, v in _greedy_wide(runs).items()}
+    lines.append("push kernel, one 10-frame push of float32 rows, lane per row and wide rows alternating: median (min .. max) ms")
+    for k, v in res["wide"].items():
+        lines.append("  %-20s %9.4f (%.4f .. %.4f)" % (k, v["median_ms"], v["min_ms"], v["max_ms"]))
+    text = "\n".join(lines) + "\n" + json.dumps(res)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 def make_input(kind):
     rng = np.random.default_rng(20251015)
     x = rng.standard_normal((T, B, C), dtype=np.float32)
@@ -325,8 +447,11 @@ def main():
     ap.add_argument("--scores", action="store_true",
                     help="with --dense: each multi-push schedule with and without a score store, and its kernels' times")
     ap.add_argument("--score-store", default=None, help="with --scores: bfloat16 or float16 (default: the compute dtype)")
+    ap.add_argument("--greedy", action="store_true", help="the greedy stream's report alone (see above)")
     ap.add_argument("--out", default=None, help="also write the table and the JSON line here")
     args = ap.parse_args()
+    if args.greedy:
+        return greedy_report(args.runs, args.out)
     chunks = [int(c) for c in args.chunks.split(",")]
     if args.scores and not args.dense:
         raise SystemExit("--scores needs --dense: a stream with a score store has the enqueue-only push alone")
