@@ -30,6 +30,7 @@
 #include "ctcx_stable.h"
 #include "ctcx_stream_dense.h"
 #include "ctcx_stream_store.h"
+#include "ctcx_targets.h"
 #include "ctcx_times.h"
 
 namespace ctcx {
@@ -167,9 +168,9 @@ struct Dev {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t s = nullptr;   // stream of the current call
-  hipEvent_t ev[11] = {};    // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
+  hipEvent_t ev[13] = {};    // CTCEXT_FLAG_PROFILE: around the pre-pass, decode, traceback; [4] after the dense pack;
                              // [5], [6] around the token-times kernel of a dense call, [7], [8] the token-scores kernel,
-                             // [9], [10] the path-scores kernels
+                             // [9], [10] the path-scores kernels, [11], [12] the target-scores kernels
   hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
   hipEvent_t al[6] = {};     // ... of a dense call's path alignments: around the forward, walk back, emit, times, scores
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
@@ -227,6 +228,8 @@ struct ctcext_decoder {
     int64_t pad_value = -1;     // what ctcext_dense_path_alignments pads its rows with
     int align_timed = 0;        // events al[0 .. align_timed) were recorded
     bool greedy = false;        // it was a ctcext_decode_greedy (events [0] .. [2] around its two kernels)
+    int targets_route = -1;     // the route of the last ctcext_dense_target_scores behind it (-1: none)
+    bool targets_timed = false; // events [11], [12] were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -1421,6 +1424,8 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   d->dense.sc = ScoreSrc{};
   d->dense.scores_timed = false;
   d->dense.paths_timed = false;
+  d->dense.targets_route = -1;
+  d->dense.targets_timed = false;
   d->dense.pad_value = o ? o->pad_value : -1;
   d->dense.align_timed = 0;
   d->dense.greedy = false;
@@ -1659,6 +1664,8 @@ extern "C" int ctcext_decode_greedy(ctcext_decoder* d, const ctcext_decode_args*
   d->dense.sc = ScoreSrc{};
   d->dense.scores_timed = false;
   d->dense.paths_timed = false;
+  d->dense.targets_route = -1;
+  d->dense.targets_timed = false;
   d->dense.pad_value = o ? o->pad_value : -1;
   d->dense.align_timed = 0;
   d->dense.greedy = true;
@@ -3564,6 +3571,119 @@ extern "C" int ctcext_stream_path_scores(ctcext_stream* st, void* path_logp) {
   if (rc != CTCEXT_OK) return rc;
   HIP_OR_FAIL(ctcx_launch_path_scores(p, n.s));
   g_err.clear();
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Target scores (ctcext.h, "Target scores"): the path scores' recursion over
+// rows the caller supplies, from the same sources (ScoreSrc, the sanitised
+// lengths, the final status word).  Short lists run in ctcx_targets.hip's packed
+// kernel, lists of whole transcripts in ctcx_paths.hip's per-row kernels, which
+// read the targets in place (CtcxPathsParams' row source).
+
+extern "C" int ctcext_targets_validate(const ctcext_targets* t) {
+  if (!t) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (t->n_targets < 0) return fail(CTCEXT_INVALID_ARGUMENT, "target scores: n_targets must not be negative");
+  if (t->max_target < 0) return fail(CTCEXT_INVALID_ARGUMENT, "target scores: max_target must not be negative");
+  if (t->n_targets > 0 && !t->target_length)
+    return fail(CTCEXT_INVALID_ARGUMENT, "target scores: target_length is null");
+  if (t->n_targets > 0 && t->max_target > 0 && !t->targets)
+    return fail(CTCEXT_INVALID_ARGUMENT, "target scores: targets is null");
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int32_t ctcext_target_scores_tile(int64_t num_classes, int32_t f64) {
+  return ctcx_targets_tile(num_classes, f64);
+}
+
+// CTCEXT_TARGETS=rows|staged|gathered (diagnostics; read at every call) forces
+// a route where the shape allows it: 0 per-row kernels, 1 packed and staged,
+// 2 packed and gathered
+static int targets_route(int64_t C, int64_t L, bool f64) {
+  const char* v = getenv("CTCEXT_TARGETS");
+  const std::string want = v ? v : "";
+  if (L > kTargetsMaxPacked || want == "rows") return 0;
+  if (want == "gathered" || !ctcx_targets_tile(C, f64 ? 1 : 0)) return 2;
+  return 1;
+}
+
+extern "C" int ctcext_dense_target_scores(ctcext_decoder* d, const ctcext_targets* t, void* target_logp) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_targets_validate(t);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_target_scores without a ctcext_decode_dense");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "target scores need a one-device decoder handle");
+  d->dense.targets_route = -1;
+  if (d->dense.B == 0 || t->n_targets == 0) return CTCEXT_OK;
+  if (!target_logp) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.sc.have) return fail(CTCEXT_INTERNAL, "target scores: the inputs of the last call are missing");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  const ScoreSrc& q = d->dense.sc;
+  const int route = targets_route(d->dense.C, t->max_target, q.f64);
+  const int32_t* const frames = (const int32_t*)root.dsl.p;
+  const int32_t* const status = (const int32_t*)root.dstat.p + B;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (route == 0) {
+    if (t->n_targets > 0x7fffffffLL) return fail(CTCEXT_UNIMPLEMENTED, "target scores: too many targets per item");
+    CtcxPathsParams p{};
+    paths_params(p, nullptr, nullptr, q, d->dense.T, B, d->dense.C, (int)t->n_targets, d->dense.blank_index);
+    p.frames = frames;
+    p.status = status;
+    p.path_logp = target_logp;
+    p.tgt = t->targets; p.tgt_len = t->target_length; p.tgt_L = t->max_target;
+    p.tgt_shared = t->shared ? 1 : 0; p.tgt_i64 = t->labels_i64 ? 1 : 0;
+    if (!ctcx_path_scores_fits(ctcx_paths_width(p), p.f64, p.force_lds))
+      return fail(CTCEXT_UNIMPLEMENTED, "target scores: rows this wide do not fit the LDS trellis");
+    if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[11], s));
+    HIP_OR_FAIL(ctcx_launch_path_scores(p, s));
+  } else {
+    CtcxTargetsParams p{};
+    p.targets = t->targets; p.target_length = t->target_length;
+    p.frames = frames; p.status = status;
+    p.x = q.x; p.norm = q.norm;
+    p.Tmax = d->dense.T; p.B = B; p.C = d->dense.C; p.xst_t = q.st_t; p.xst_b = q.st_b;
+    p.N = t->n_targets; p.L = t->max_target;
+    p.xfmt = q.xfmt; p.f64 = q.f64 ? 1 : 0; p.blank_index = d->dense.blank_index;
+    p.shared = t->shared ? 1 : 0; p.labels_i64 = t->labels_i64 ? 1 : 0;
+    p.staged = route == 1 ? 1 : 0;
+    p.out = target_logp;
+    if (prof) HIP_OR_FAIL(hipEventRecord(root.ev[11], s));
+    HIP_OR_FAIL(ctcx_launch_target_scores(p, s));
+  }
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.ev[12], s));
+    d->dense.targets_timed = true;
+  }
+  d->dense.targets_route = route;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_target_scores_route(ctcext_decoder* d, int32_t* route) {
+  if (!d || !route) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || d->dense.targets_route < 0)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no target scores were enqueued behind the last dense decode");
+  *route = d->dense.targets_route;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_target_scores_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.targets_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no target scores of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.ev[12]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[11], root.ev[12]));
+  *ms = f;
   return CTCEXT_OK;
 }
 

@@ -33,8 +33,22 @@ struct CtcxPathsParams {
   int32_t P, xfmt, f64, blank_index;
   int32_t force_lds, pad;   // force_lds: every row runs in the LDS instantiation (diagnostics)
   void* path_logp;          // [B][P] of the compute dtype
+  // Another source of the rows (ctcx_targets.h, the per-row route of the target
+  // scores); all zero: the walk buffers above.  With tgt set, row (b, p) is
+  // target p of item b, its labels in reading order; seq and len are not read.
+  // A length outside [0, tgt_L] makes the row NaN, one above the item's frames
+  // -inf; int64 labels are checked against [0, C) before they are narrowed.
+  const void* tgt;          // [B][P][tgt_L], or [P][tgt_L] with tgt_shared; int32, or int64 with tgt_i64
+  const int32_t* tgt_len;   // [B][P], or [P] with tgt_shared
+  int64_t tgt_L;
+  int32_t tgt_shared, tgt_i64;
 };
 
-// Whether rows of Tmax positions fit an instantiation (the LDS one holds kPathsMaxLdsT*); host only.
+// The widest row of a call: no row has more labels than frames.
+__host__ __device__ inline int64_t ctcx_paths_width(const CtcxPathsParams& p) {
+  return p.tgt_len && p.tgt_L < p.Tmax ? p.tgt_L : p.Tmax;
+}
+
+// Whether rows of Tmax positions (ctcx_paths_width) fit an instantiation (the LDS one holds kPathsMaxLdsT*); host only.
 bool ctcx_path_scores_fits(int64_t Tmax, int32_t f64, int32_t force_lds);
 hipError_t ctcx_launch_path_scores(const CtcxPathsParams& p, hipStream_t s);

@@ -47,10 +47,18 @@
 // the branch, in every lane).  A block that has fallen behind the band stays
 // behind it, and what its stale states feed lies behind it as well.
 //
+// Rows of the caller (CtcxPathsParams' tgt fields; the per-row route of the
+// target scores, ctcx_targets.h).  The same kernels read row (b, p) from the
+// caller's targets in place instead of the walk buffers: labels in reading
+// order, int32 or int64.  A length outside [0, tgt_L] makes the row NaN; a row
+// of more labels than frames is -inf without a recursion (its labels are
+// checked all the same), so every row that runs has m <= frames <= Tmax.
+//
 // Nothing is trusted: lengths are clamped to [0, Tmax] as the token-scores
 // kernel clamps them, a label outside [0, C) makes the row a NaN before any
 // logit is read, and every logit read is frame f < frames <= Tmax of item b.
 #include "ctcx_paths.h"
+#include "ctcx_lse.h"   // ninf, row_at, row_ptr, lse2, lse3, dpp_keep, from_prev_lane, finite_or_ninf
 
 #include <atomic>
 
@@ -58,66 +66,8 @@ namespace {
 
 constexpr int kR = kPathsRenorm;
 static_assert((kR & (kR - 1)) == 0, "the frame test below masks");
+static_assert(kPathsInNative == 0 && kPathsInF16 == 1 && kPathsInBF16 == 2, "ctcx_lse.h spells the formats out");
 
-template <typename T>
-__device__ __forceinline__ T ninf() { return (T)(-__builtin_inff()); }
-
-// element idx of the row at `row`, widened as the decode kernels' row stage
-// widens it (fp16: the hardware convert; bf16: the bits, 16 to the left)
-template <typename T, int Fmt>
-__device__ __forceinline__ T row_at(const void* row, uint32_t idx) {
-  if constexpr (Fmt == kPathsInF16)
-    return (T)(float)__builtin_bit_cast(_Float16, ((const uint16_t*)row)[idx]);
-  else if constexpr (Fmt == kPathsInBF16)
-    return (T)__uint_as_float((unsigned)((const uint16_t*)row)[idx] << 16);
-  else
-    return ((const T*)row)[idx];
-}
-template <int Fmt, typename T>
-__device__ __forceinline__ const void* row_ptr(const void* x, int64_t off) {
-  if constexpr (Fmt == kPathsInNative) return (const T*)x + off;
-  else return (const uint16_t*)x + off;
-}
-
-__device__ __forceinline__ float ex(float d) { return __builtin_amdgcn_exp2f(d * 1.44269504088896340736f); }
-__device__ __forceinline__ float lg(float s) { return __builtin_amdgcn_logf(s) * 0.69314718055994530942f; }
-__device__ __forceinline__ double ex(double d) { return exp(d); }
-__device__ __forceinline__ double lg(double s) { return log(s); }
-__device__ __forceinline__ float mx2(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double mx2(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ float ab(float a) { return fabsf(a); }
-__device__ __forceinline__ double ab(double a) { return fabs(a); }
-
-// log(exp(a) + exp(b)); all -inf (or NaN beside -inf): a + b.  A NaN argument
-// gives a NaN in both functions: the maximum drops it (fmax returns the other
-// argument), but every argument also goes through a subtraction of its own
-// (here a - b, below a - m, b - m, c - m), and the NaN comes back through that.
-template <typename T>
-__device__ __forceinline__ T lse2(T a, T b) {
-  const T m = mx2(a, b);
-  const T r = m + lg((T)1 + ex(-ab(a - b)));   // (min - max, as a free modifier)
-  return m > ninf<T>() ? r : a + b;
-}
-template <typename T>
-__device__ __forceinline__ T lse3(T a, T b, T c) {
-  const T m = mx2(mx2(a, b), c);
-  const T r = m + lg(ex(a - m) + ex(b - m) + ex(c - m));
-  return m > ninf<T>() ? r : a + b + c;
-}
-
-template <int Ctrl>
-__device__ __forceinline__ int dpp_keep(int old, int v) {
-  return __builtin_amdgcn_update_dpp(old, v, Ctrl, 0xf, 0xf, false);   // a lane without a source keeps `old`
-}
-// lane l receives lane l - 1's v, lane 0 -inf (wave_shr:1)
-__device__ __forceinline__ float from_prev_lane(float v) {
-  return __int_as_float(dpp_keep<0x138>(__float_as_int(ninf<float>()), __float_as_int(v)));
-}
-__device__ __forceinline__ double from_prev_lane(double v) {
-  const double o = ninf<double>();
-  return __hiloint2double(dpp_keep<0x138>(__double2hiint(o), __double2hiint(v)),
-                          dpp_keep<0x138>(__double2loint(o), __double2loint(v)));
-}
 // the wave's maximum of v (no NaN), uniform: row_shr 1, 2, 4, 8, row_bcast 15 and 31 gather it in lane 63
 __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, __int_as_float(dpp_keep<0x111>(__float_as_int(v), __float_as_int(v))));
@@ -128,7 +78,6 @@ __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, __int_as_float(dpp_keep<0x143>(__float_as_int(v), __float_as_int(v))));
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
-__device__ __forceinline__ float finite_or_ninf(float v) { return fabsf(v) < __builtin_inff() ? v : ninf<float>(); }
 
 // the largest register block of the compute dtype: 24 pairs of doubles with
 // their two sets of logits do not fit the register file, so float64 rows above
@@ -148,7 +97,10 @@ static_assert(kPathsBlocks[0] == 1 && kPathsBlocks[1] == 2 && kPathsBlocks[2] ==
 struct Row {
   int64_t bp, b;
   int m, frames;
-  bool empty;
+  bool empty;        // the row is NaN
+  bool infeasible;   // (a target) more labels than frames: the row is -inf (NaN with a bad label), and m reads 0
+  int tlen;          // (a target) its labels
+  int64_t t0;        // (a target) its first label's index in p.tgt
 };
 __device__ __forceinline__ Row read_row(const CtcxPathsParams& p) {
   Row r;
@@ -159,8 +111,42 @@ __device__ __forceinline__ Row read_row(const CtcxPathsParams& p) {
   auto clampT = [&](int v) { return v < 0 ? 0 : v > Tmax ? Tmax : v; };
   r.empty = p.status && p.status[r.b] != 0;
   r.frames = clampT(p.frames[r.b]);
+  r.infeasible = false;
+  r.t0 = 0;
+  r.tlen = 0;
+  if (p.tgt_len) {
+    const int64_t ti = p.tgt_shared ? pth : r.bp;
+    const int32_t len = p.tgt_len[ti];
+    r.empty |= len < 0 || len > p.tgt_L;
+    r.infeasible = !r.empty && len > r.frames;
+    r.m = r.empty || r.infeasible ? 0 : len;
+    r.t0 = ti * p.tgt_L;
+    r.tlen = r.empty ? 0 : len;
+    return r;
+  }
   r.m = r.empty ? 0 : clampT(p.len[((int64_t)pth * 2 + 0) * p.B + r.b]);
   return r;
+}
+// label j of the row: the walk's element m - 1 - j, or the target's j (-1: an int64 label outside [0, C))
+__device__ __forceinline__ int row_label(const CtcxPathsParams& p, const Row& r, const int32_t* d_rev, int j) {
+  if (!p.tgt_len) return d_rev[r.m - 1 - j];
+  if (!p.tgt_i64) return ((const int32_t*)p.tgt)[r.t0 + j];
+  const int64_t v = ((const int64_t*)p.tgt)[r.t0 + j];
+  return v < 0 || v >= p.C ? -1 : (int)v;
+}
+// the rows that need no recursion (uniform)
+template <typename T>
+__device__ __forceinline__ bool row_is_done(const CtcxPathsParams& p, const Row& r, T* out, int lane) {
+  if (!r.empty && !r.infeasible) return false;
+  bool bad = r.empty;
+  if (r.infeasible)   // its labels are checked all the same: a label outside [0, C) makes the row NaN
+    for (int j = lane; j < r.tlen; j += 64) {
+      const int v = row_label(p, r, nullptr, j);
+      bad |= v < 0 || v >= p.C;
+    }
+  bad = __any(bad);
+  if (lane == 0) *out = bad ? (T)__builtin_nanf("") : ninf<T>();
+  return true;
 }
 
 template <typename T, int Fmt, int K>
@@ -169,10 +155,7 @@ __global__ __launch_bounds__(64) void ctcx_path_scores_reg(CtcxPathsParams p) {
   if (p.force_lds || block_of<T>(r.m) != K) return;   // (uniform) another instantiation's row
   const int lane = threadIdx.x;
   T* const out = (T*)p.path_logp + r.bp;
-  if (r.empty) {
-    if (lane == 0) *out = (T)__builtin_nanf("");
-    return;
-  }
+  if (row_is_done(p, r, out, lane)) return;
   const int m = r.m, frames = r.frames;
   const int32_t* const d_rev = p.seq + (r.bp * 2 + 0) * p.Tmax;   // token j is element m - 1 - j
   const int j0 = lane * K;
@@ -180,12 +163,12 @@ __global__ __launch_bounds__(64) void ctcx_path_scores_reg(CtcxPathsParams p) {
   uint32_t lab[K];
   unsigned skipm = 0;   // bit i: the s - 2 step into label i is allowed
   bool bad = false;
-  int prev = (nl > 0 && j0 > 0) ? d_rev[m - j0] : -1;
+  int prev = (nl > 0 && j0 > 0) ? row_label(p, r, d_rev, j0 - 1) : -1;
 #pragma unroll
   for (int i = 0; i < K; ++i) {
     int v = 0;
     if (i < nl) {
-      v = d_rev[m - 1 - (j0 + i)];
+      v = row_label(p, r, d_rev, j0 + i);
       bad |= v < 0 || v >= p.C;
       if (j0 + i > 0 && v != prev) skipm |= 1u << i;
       prev = v;
@@ -291,12 +274,9 @@ __global__ __launch_bounds__(64) void ctcx_path_scores_lds(CtcxPathsParams p) {
   if (!p.force_lds && block_of<T>(r.m) != 0) return;   // (uniform) a register instantiation's row
   const int lane = threadIdx.x;
   T* const out = (T*)p.path_logp + r.bp;
-  if (r.empty) {
-    if (lane == 0) *out = (T)__builtin_nanf("");
-    return;
-  }
+  if (row_is_done(p, r, out, lane)) return;
   const int m = r.m, frames = r.frames;
-  const int W = (int)p.Tmax + 1;   // m <= Tmax
+  const int W = (int)ctcx_paths_width(p) + 1;   // m <= Tmax (and a target's <= tgt_L)
   T* const sB = (T*)s_mem;
   T* const sL = sB + W;
   int32_t* const sY = (int32_t*)(sL + W);
@@ -306,9 +286,9 @@ __global__ __launch_bounds__(64) void ctcx_path_scores_lds(CtcxPathsParams p) {
   for (int j = lane; j <= m; j += 64) {
     int v = 0;
     if (j < m) {
-      v = d_rev[m - 1 - j];
+      v = row_label(p, r, d_rev, j);
       bad |= v < 0 || v >= p.C;
-      if (j > 0 && v != d_rev[m - j]) v |= (int)0x80000000u;
+      if (j > 0 && v != row_label(p, r, d_rev, j - 1)) v |= (int)0x80000000u;
     }
     sY[j] = v;
     sB[j] = j == 0 ? (T)0 : NINF;
@@ -375,18 +355,19 @@ constexpr size_t lds_bytes(int64_t Tmax) { return (size_t)(Tmax + 1) * (2 * size
 template <typename T, int Fmt>
 hipError_t launch_all(const CtcxPathsParams& p, hipStream_t s) {
   const dim3 grid((unsigned)(p.B * p.P)), block(64);
+  const int64_t Wd = ctcx_paths_width(p);
   if (!p.force_lds) {
     // every register instantiation a row of at most Tmax labels can need
     hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 1>), grid, block, 0, s, p);
-    if (p.Tmax > 64 * 1) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 2>), grid, block, 0, s, p);
-    if (p.Tmax > 64 * 2) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 4>), grid, block, 0, s, p);
-    if (p.Tmax > 64 * 4) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 8>), grid, block, 0, s, p);
-    if (p.Tmax > 64 * 8) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 16>), grid, block, 0, s, p);
+    if (Wd > 64 * 1) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 2>), grid, block, 0, s, p);
+    if (Wd > 64 * 2) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 4>), grid, block, 0, s, p);
+    if (Wd > 64 * 4) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 8>), grid, block, 0, s, p);
+    if (Wd > 64 * 8) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 16>), grid, block, 0, s, p);
     if constexpr (kMaxBlock<T> >= 24)
-      if (p.Tmax > 64 * 16) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 24>), grid, block, 0, s, p);
-    if (p.Tmax <= 64 * kMaxBlock<T>) return hipGetLastError();
+      if (Wd > 64 * 16) hipLaunchKernelGGL((ctcx_path_scores_reg<T, Fmt, 24>), grid, block, 0, s, p);
+    if (Wd <= 64 * kMaxBlock<T>) return hipGetLastError();
   }
-  const size_t bytes = lds_bytes<T>(p.Tmax);
+  const size_t bytes = lds_bytes<T>(Wd);
   if (bytes > 64 * 1024) {
     // dynamic LDS above the default limit is allowed once per device and instantiation, for the widest row
     // (a host-side attribute of the function: no stream operation, nothing a capture sees)
@@ -421,9 +402,9 @@ bool ctcx_path_scores_fits(int64_t Tmax, int32_t f64, int32_t force_lds) {
 hipError_t ctcx_launch_path_scores(const CtcxPathsParams& p, hipStream_t s) {
   if (p.B <= 0 || p.P <= 0) return hipSuccess;
   if (p.B * p.P > 0x7fffffffLL || p.Tmax < 0 || p.C <= 0 || p.C > 0x7fffffffLL || p.blank_index < 0 ||
-      p.blank_index >= p.C || !p.seq || !p.len || !p.frames || !p.path_logp || (p.Tmax > 0 && (!p.x || !p.norm)) ||
+      p.blank_index >= p.C || (!p.tgt_len && (!p.seq || !p.len)) || (p.tgt_len && (p.tgt_L < 0 || (p.tgt_L > 0 && !p.tgt))) || !p.frames || !p.path_logp || (p.Tmax > 0 && (!p.x || !p.norm)) ||
       (p.xfmt != kPathsInNative && (p.f64 || (p.xfmt != kPathsInF16 && p.xfmt != kPathsInBF16))) ||
-      !ctcx_path_scores_fits(p.Tmax, p.f64, p.force_lds))
+      !ctcx_path_scores_fits(ctcx_paths_width(p), p.f64, p.force_lds))
     return hipErrorInvalidValue;
   if (p.f64) return launch_all<double, kPathsInNative>(p, s);
   if (p.xfmt == kPathsInF16) return launch_all<float, kPathsInF16>(p, s);

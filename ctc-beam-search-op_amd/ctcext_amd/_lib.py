@@ -92,6 +92,10 @@ GREEDY_STREAM_SYMBOLS = ("ctcext_greedy_stream_validate", "ctcext_greedy_stream_
                          "ctcext_greedy_stream_check", "ctcext_greedy_stream_frames", "ctcext_greedy_stream_reset",
                          "ctcext_greedy_stream_close", "ctcext_greedy_stream_push_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + GREEDY_STREAM_SYMBOLS
+# target scores (CTCEXT_HAS_TARGET_SCORES)
+TARGET_SCORES_SYMBOLS = ("ctcext_targets_validate", "ctcext_dense_target_scores", "ctcext_target_scores_tile",
+                         "ctcext_dense_target_scores_route", "ctcext_dense_target_scores_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TARGET_SCORES_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -180,6 +184,12 @@ class StreamDenseOutputs(ctypes.Structure):
                 ("frames", ctypes.c_void_p),
                 ("stable_length", ctypes.c_void_p), ("stable_frames", ctypes.c_void_p),
                 ("pad_value", ctypes.c_int64)]
+
+
+class Targets(ctypes.Structure):
+    """ctcext_targets: the label rows the target scores are asked about."""
+    _fields_ = [("targets", ctypes.c_void_p), ("target_length", ctypes.c_void_p), ("n_targets", ctypes.c_int64),
+                ("max_target", ctypes.c_int64), ("shared", ctypes.c_int32), ("labels_i64", ctypes.c_int32)]
 
 
 class GreedyStreamWant(ctypes.Structure):
@@ -481,6 +491,17 @@ def load():
         lib.ctcext_greedy_stream_close.restype = None
         lib.ctcext_greedy_stream_push_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_greedy_stream_push_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_target_scores"):   # (CTCEXT_HAS_TARGET_SCORES; older builds stay loadable for A/B runs)
+        lib.ctcext_targets_validate.argtypes = [ctypes.POINTER(Targets)]
+        lib.ctcext_targets_validate.restype = ctypes.c_int
+        lib.ctcext_dense_target_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(Targets), ctypes.c_void_p]
+        lib.ctcext_dense_target_scores.restype = ctypes.c_int
+        lib.ctcext_target_scores_tile.argtypes = [ctypes.c_int64, ctypes.c_int32]
+        lib.ctcext_target_scores_tile.restype = ctypes.c_int32
+        lib.ctcext_dense_target_scores_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+        lib.ctcext_dense_target_scores_route.restype = ctypes.c_int
+        lib.ctcext_dense_target_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_target_scores_ms.restype = ctypes.c_int
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

@@ -949,6 +949,75 @@ def path_scores(device=None):
     return out
 
 
+_NO_TARGETS = "target scores need a decode with token_scores=True"
+
+
+def dense_target_scores(targets, target_lengths, device=None):
+    """What the model thinks of label rows it did NOT return: the exact CTC
+    log-likelihood ``log p(y | x)`` of every supplied target under the logits
+    of the calling thread's last ``decode_dense(..., token_scores=True)`` or
+    ``decode_greedy(..., token_scores=True)`` on ``device`` (None: the current
+    one) -- a keyword list, another pass's N-best, an expected transcript.
+    Enqueued behind that decode on its stream without waiting for anything, so
+    it can be captured into the same ``torch.cuda.graph``.
+
+    ``targets`` is a CUDA int64 or int32 tensor ``[B, N, L]``, or ``[N, L]``
+    for one list shared by all items; ``target_lengths`` is a CUDA int32 tensor
+    ``[B, N]`` or ``[N]`` to match.  Returns a CUDA tensor ``[B, N]`` of the
+    compute dtype: the "Path scores" definition of ``include/ctcext.h`` applied
+    to each row.  An infeasible row is ``-inf``; a row with a label outside
+    ``[0, C)`` or a length outside ``[0, L]`` is NaN, as is every row of an
+    item with a status bit.  No ``blank_label`` is involved.  Lists with
+    ``L <= 63`` run in the packed kernel ("Target scores"), longer ones one
+    wave per target."""
+    what = "ctcext_dense_target_scores without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = dec.lib
+    if not hasattr(lib, "ctcext_dense_target_scores"):
+        raise UnimplementedError("this libctcext.so has no target scores (CTCEXT_HAS_TARGET_SCORES)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError(_NO_TARGETS, _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    import torch
+    if not (_is_torch(targets) and _is_torch(target_lengths) and targets.is_cuda and target_lengths.is_cuda):
+        raise TypeError("dense_target_scores: targets and target_lengths must be CUDA tensors")
+    if targets.dtype not in (torch.int64, torch.int32):
+        _type_error("targets", str(targets.dtype).replace("torch.", ""), "int32, int64")
+    if target_lengths.dtype != torch.int32:
+        _type_error("target_lengths", str(target_lengths.dtype).replace("torch.", ""), "int32")
+    if targets.device != dev or target_lengths.device != dev:
+        raise InvalidArgumentError("target scores: the targets must be on the decode's device", _lib.CTCEXT_INVALID_ARGUMENT)
+    shared = targets.dim() == 2
+    if targets.dim() not in (2, 3) or tuple(target_lengths.shape) != tuple(targets.shape[:-1]) or \
+            (not shared and targets.shape[0] != B):
+        raise InvalidArgumentError("target scores: targets must be [B, N, L] or [N, L], and target_lengths [B, N] or [N]",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    targets, target_lengths = targets.contiguous(), target_lengths.contiguous()
+    N, L = int(targets.shape[-2]), int(targets.shape[-1])
+    t = _lib.Targets(targets.data_ptr(), target_lengths.data_ptr(), N, L, 1 if shared else 0,
+                     1 if targets.dtype == torch.int64 else 0)
+    with torch.cuda.device(dev):
+        out = torch.empty((B, N), dtype=fdt, device=dev)
+    rc = lib.ctcext_dense_target_scores(dec.handle, ctypes.byref(t), out.data_ptr())
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def score_targets(logits, lengths, targets, target_lengths, *, blank_index=0, batch_first=True):
+    """``dense_target_scores`` for logits nothing has decoded yet:
+    ``decode_greedy(..., token_scores=True)`` supplies the normaliser (its two
+    small kernels), then the targets are scored behind it on the same stream.
+    Arguments as for ``decode_greedy`` and ``dense_target_scores``; returns the
+    CUDA tensor ``[B, N]``.  Nothing is waited for."""
+    decode_greedy(logits, lengths, batch_first=batch_first, blank_index=blank_index, token_scores=True)
+    return dense_target_scores(targets, target_lengths, device=logits.device)
+
+
 def path_score_row(x, norm, decoded, frames, blank_index, blank_label=-1):
     """The definition of the path score for one row, on the host (no GPU), in
     long double: ``x`` is one item's logits ``[frames, num_classes]`` (float32

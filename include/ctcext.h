@@ -1108,8 +1108,8 @@ int ctcext_stream_scores_ms(ctcext_stream* s, double* append_ms, double* scores_
  * unchanged.  Rows wider than the kernels hold (max_time above 13000, 8000
  * for float64): CTCEXT_UNIMPLEMENTED.
  *
- * Not covered: scoring transcripts the decode did not return; a Viterbi
- * re-alignment; handles of more than one device (CTCEXT_UNIMPLEMENTED);
+ * Not covered: scoring transcripts the decode did not return ("Target scores"
+ * below does that); a Viterbi re-alignment; handles of more than one device (CTCEXT_UNIMPLEMENTED);
  * scorer-table (bigram) terms -- the score is the acoustic CTC likelihood
  * only. */
 #define CTCEXT_HAS_PATH_SCORES 1
@@ -1454,6 +1454,83 @@ void ctcext_greedy_stream_close(ctcext_greedy_stream* s);
 /* Diagnostics: with CTCEXT_FLAG_PROFILE in the stream's or the chunk's flags,
  * the time of the last push's kernel in ms.  Waits for it. */
 int ctcext_greedy_stream_push_ms(ctcext_greedy_stream* s, double* ms);
+
+/* ---------------------------------------------------------------------------
+ * Target scores: the exact CTC log-likelihood log p(y | x) of label rows the
+ * CALLER supplies, on the device -- a hotword or keyword list scored against
+ * every utterance, the N-best of another pass rescored under the acoustic
+ * model, an expected transcript verified.  The path scores answer that only
+ * for the rows the decode returned.  New entry points and one new struct only
+ * (CTCEXT_ABI_VERSION is unchanged; detect them by CTCEXT_HAS_TARGET_SCORES at
+ * build time or by symbol at run time).
+ *
+ * Definition.  For item b and target n, y = targets[b][n][0 .. target_length
+ * [b][n]) (targets[n], target_length[n] with shared), and score[b][n] is the
+ * definition of "Path scores" applied to y: the same lp[f][c] = x[f][c] -
+ * norm[f] as one rounded subtraction in the compute dtype, the same frames,
+ * blank_index, 2m + 1 states and skip rule, and its conventions: an infeasible
+ * row is -inf, frames == 0 with m == 0 gives 0, every row of an item with a
+ * status bit is NaN, a label outside [0, C) makes the row NaN.  One more: a
+ * target_length outside [0, max_target] makes the row NaN; nothing in the two
+ * tensors is trusted.  No blank_label is involved, and the blank_label rule of
+ * the token times does not apply.  ctcext_path_score_row is the host
+ * definition.
+ *
+ * Routes.  Lists of short targets (max_target <= 63) run in a packed kernel:
+ * a target takes a segment of 8, 16, 32 or 64 lanes (the smallest with
+ * max_target + 1 slots), a workgroup of 256 threads holds 256 / segment
+ * targets of one item, and where the class count allows it (<= 512, <= 256 for
+ * float64: ctcext_target_scores_tile) the workgroup stages the item's rows
+ * through LDS once for all of them; wider alphabets are gathered lane by lane.
+ * Lists with max_target >= 64 (whole transcripts) run in the per-row kernels of
+ * the path scores, one wave per target, which read the targets in place; rows
+ * wider than those hold (min(max_target, max_time) above 13000, 8000 for
+ * float64): CTCEXT_UNIMPLEMENTED.  Every route evaluates the recursion in the
+ * compute dtype in the log domain (float32 renormalised every 16 frames), so
+ * the values agree with the definition to within the rounding of the
+ * recursion, and between routes likewise, not bit for bit.  Diagnostics: the
+ * environment variable CTCEXT_TARGETS=rows / =staged / =gathered, read at
+ * every call, forces a route where the shape allows it.
+ *
+ * Not covered: streams (ctcext_stream_* over the score store); a synchronous
+ * form after ctcext_decode; a forced Viterbi alignment of supplied targets;
+ * handles of more than one device (CTCEXT_UNIMPLEMENTED); scorer-table
+ * (bigram) terms; staging a compacted alphabet for wide vocabularies. */
+#define CTCEXT_HAS_TARGET_SCORES 1
+
+typedef struct {
+  const void*    targets;        /* device: [batch][n_targets][max_target], or [n_targets][max_target] with shared */
+  const int32_t* target_length;  /* device: [batch][n_targets], or [n_targets] with shared */
+  int64_t n_targets, max_target;
+  int32_t shared;                /* 1: one list for every item */
+  int32_t labels_i64;            /* 1: int64 labels (torch's default, the decoded rows' type); 0: int32 */
+} ctcext_targets;
+
+/* Host only, no HIP call (CTCEXT_INVALID_ARGUMENT):
+ *   "target scores: n_targets must not be negative"
+ *   "target scores: max_target must not be negative"
+ *   "target scores: target_length is null"     (n_targets > 0)
+ *   "target scores: targets is null"           (n_targets > 0 and max_target > 0) */
+int ctcext_targets_validate(const ctcext_targets* targets);
+/* Validates, then enqueues the kernels on the stream of the last
+ * ctcext_decode_dense / ctcext_decode_dense_skip / ctcext_decode_greedy,
+ * behind whatever that stream holds, over that call's logits (in place),
+ * normaliser, frames and final status word.  target_logp is a device pointer,
+ * [batch][n_targets] of the compute dtype.  No allocation, no host-blocking
+ * call, no device-to-host copy; capturable into the same graph as the decode.
+ * Without a preceding dense call: CTCEXT_FAILED_PRECONDITION.  n_targets == 0
+ * or batch == 0: CTCEXT_OK with nothing launched. */
+int ctcext_dense_target_scores(ctcext_decoder* dec, const ctcext_targets* targets, void* target_logp);
+/* For tests: the frames per LDS tile of the staged route for this class count,
+ * or 0 where the class count takes the gathered route. */
+int32_t ctcext_target_scores_tile(int64_t num_classes, int32_t f64);
+/* Which route the last ctcext_dense_target_scores behind the last dense call
+ * took: 0 the per-row kernels, 1 packed and staged, 2 packed and gathered.
+ * CTCEXT_FAILED_PRECONDITION where none launched anything. */
+int ctcext_dense_target_scores_route(ctcext_decoder* dec, int32_t* route);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
+ * last target-scores kernels of a dense call in ms.  Waits for them. */
+int ctcext_dense_target_scores_ms(ctcext_decoder* dec, double* ms);
 
 #ifdef __cplusplus
 }

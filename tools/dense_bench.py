@@ -354,6 +354,63 @@ def greedy_report(args):
     return lines, res
 
 
+def targets_report(args):
+    """--targets: the packed route against the per-row route (CTCEXT_TARGETS=rows) of the same targets at cfg3,
+    alternating pairs; the kernels' own time by device events (ctcext_dense_target_scores_ms)."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    x = times_inputs("gaussian", T, B, C)
+    rng = np.random.default_rng(20261126)
+    lines = ["%-22s %6s %10s %10s %8s %12s %12s %9s   (median of %d alternating pairs, ms; cfg3 B=%d T=%d C=%d)"
+             % ("targets", "route", "packed", "per-row", "gain", "greedy call", "whole call", "share", args.runs, B, T, C)]
+    res = {"runs": args.runs, "shape": [B, T, C], "targets": {}}
+
+    def once(y, n, rows):
+        if rows:
+            os.environ["CTCEXT_TARGETS"] = "rows"
+        else:
+            os.environ.pop("CTCEXT_TARGETS", None)
+        torch.cuda.synchronize()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True, **KW)
+        e[1].record()
+        out = ctcext_amd.dense_target_scores(y, n)
+        e[2].record()
+        e[2].synchronize()
+        ms, route = ctypes.c_double(), ctypes.c_int32()
+        if dec.lib.ctcext_dense_target_scores_ms(dec.handle, ctypes.byref(ms)) != _lib.CTCEXT_OK or \
+                dec.lib.ctcext_dense_target_scores_route(dec.handle, ctypes.byref(route)) != _lib.CTCEXT_OK:
+            raise SystemExit(dec.lib.ctcext_last_error().decode())
+        return ms.value, route.value, e[0].elapsed_time(e[1]), e[0].elapsed_time(e[2]), out
+
+    for name, N, lo, hi, shared in (("64 x 4..15", 64, 4, 15, False), ("64 x 4..15 shared", 64, 4, 15, True),
+                                    ("8 x 200", 8, 200, 200, False)):
+        shape = (N, hi) if shared else (B, N, hi)
+        y = torch.as_tensor(rng.integers(1, C, size=shape), device="cuda:0")
+        n = torch.as_tensor(rng.integers(lo, hi + 1, size=shape[:-1]).astype(np.int32), device="cuda:0")
+        for rows in (False, True):   # warm-up: kernels
+            once(y, n, rows)
+        packed, per_row, gains, greedy, call = [], [], [], [], []
+        for _ in range(args.runs):   # alternating pairs
+            a, route, g, c, out_a = once(y, n, False)
+            b, _, _, _, out_b = once(y, n, True)
+            packed.append(a); per_row.append(b); gains.append(1 - a / b); greedy.append(g); call.append(c)
+        os.environ.pop("CTCEXT_TARGETS", None)
+        diff = float((out_a.double() - out_b.double()).abs().max())
+        share = statistics.median(packed) / statistics.median(call)
+        lines.append("%-22s %6d %10.4f %10.4f %7.1f%% %12.4f %12.4f %9.4f   gain per pair: %s; max |packed - per-row| %.3g"
+                     % (name, route, statistics.median(packed), statistics.median(per_row), 100 * statistics.median(gains),
+                        statistics.median(greedy), statistics.median(call), share,
+                        " ".join("%.1f%%" % (100 * v) for v in gains), diff))
+        res["targets"][name] = {"route": route, "packed": stat(packed), "per_row": stat(per_row),
+                                "gain_per_pair": [round(v, 4) for v in gains], "greedy_call": stat(greedy),
+                                "call": stat(call), "kernel_share_of_call": round(share, 4), "max_abs_diff": diff,
+                                "finite": int(torch.isfinite(out_a).sum()), "rows": B * N}
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -372,9 +429,11 @@ def main():
                     help="the greedy decode's two kernels at cfg3, beside the beam call's normaliser kernel of the same run")
     ap.add_argument("--align", action="store_true",
                     help="the path-alignment kernels' cost at cfg3, beside the path-scores kernels' of the same run")
+    ap.add_argument("--targets", action="store_true",
+                    help="the target-scores kernel at cfg3: the packed route against the per-row route of the same targets")
     args = ap.parse_args()
-    if args.times or args.scores or args.paths or args.align or args.greedy:
-        lines, res = greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.times or args.scores or args.paths or args.align or args.greedy or args.targets:
+        lines, res = targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
