@@ -8,7 +8,8 @@ from .ops import (CTCExtBeamSearchDecoder, Decoder, DenseDecode, FailedPrecondit
                   dense_path_scores, dense_token_scores, dense_token_times, get_decoder, kept_frames, path_score_row,
                   path_scores, token_scores, token_scores_row, token_times, token_times_row,
                   PathAlignments, dense_path_alignments, path_alignments, path_alignment_row,
-                  decode_greedy, greedy_row, GreedyPush, GreedyStream, dense_target_scores, score_targets)
+                  decode_greedy, greedy_row, GreedyPush, GreedyStream, dense_target_scores, score_targets,
+                  TargetAlignments, dense_target_alignments, forced_align)
 
 __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "StablePrefix", "StreamDense",
@@ -19,5 +20,6 @@ __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDeco
            "dense_path_alignments", "path_alignments", "path_alignment_row", "PathAlignments",
            "decode_greedy", "greedy_row", "GreedyStream", "GreedyPush",
            "dense_target_scores", "score_targets",
+           "dense_target_alignments", "forced_align", "TargetAlignments",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

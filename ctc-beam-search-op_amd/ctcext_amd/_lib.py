@@ -96,6 +96,11 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + GREEDY_STREAM_SYMBOLS
 TARGET_SCORES_SYMBOLS = ("ctcext_targets_validate", "ctcext_dense_target_scores", "ctcext_target_scores_tile",
                          "ctcext_dense_target_scores_route", "ctcext_dense_target_scores_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TARGET_SCORES_SYMBOLS
+# target alignments (CTCEXT_HAS_TARGET_ALIGNMENTS)
+TARGET_ALIGNMENTS_SYMBOLS = ("ctcext_dense_target_alignments", "ctcext_target_alignments_bytes",
+                             "ctcext_target_alignments_word_frames", "ctcext_dense_target_alignments_route",
+                             "ctcext_dense_target_alignments_ms")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TARGET_ALIGNMENTS_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -190,6 +195,13 @@ class Targets(ctypes.Structure):
     """ctcext_targets: the label rows the target scores are asked about."""
     _fields_ = [("targets", ctypes.c_void_p), ("target_length", ctypes.c_void_p), ("n_targets", ctypes.c_int64),
                 ("max_target", ctypes.c_int64), ("shared", ctypes.c_int32), ("labels_i64", ctypes.c_int32)]
+
+
+class TargetAlignmentsOut(ctypes.Structure):
+    """ctcext_target_alignments_out: the outputs of ctcext_dense_target_alignments."""
+    _fields_ = [("logp", ctypes.c_void_p), ("start", ctypes.c_void_p), ("end", ctypes.c_void_p),
+                ("trailing_blank", ctypes.c_void_p), ("logp_sum", ctypes.c_void_p), ("logp_min", ctypes.c_void_p),
+                ("alignment", ctypes.c_void_p)]
 
 
 class GreedyStreamWant(ctypes.Structure):
@@ -502,6 +514,18 @@ def load():
         lib.ctcext_dense_target_scores_route.restype = ctypes.c_int
         lib.ctcext_dense_target_scores_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_target_scores_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_target_alignments"):   # (CTCEXT_HAS_TARGET_ALIGNMENTS)
+        lib.ctcext_dense_target_alignments.argtypes = [ctypes.c_void_p, ctypes.POINTER(Targets),
+                                                       ctypes.POINTER(TargetAlignmentsOut)]
+        lib.ctcext_dense_target_alignments.restype = ctypes.c_int
+        lib.ctcext_target_alignments_bytes.argtypes = [ctypes.c_int64] * 4
+        lib.ctcext_target_alignments_bytes.restype = ctypes.c_int64
+        lib.ctcext_target_alignments_word_frames.argtypes = []
+        lib.ctcext_target_alignments_word_frames.restype = ctypes.c_int32
+        lib.ctcext_dense_target_alignments_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+        lib.ctcext_dense_target_alignments_route.restype = ctypes.c_int
+        lib.ctcext_dense_target_alignments_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_target_alignments_ms.restype = ctypes.c_int
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

@@ -1018,6 +1018,90 @@ def score_targets(logits, lengths, targets, target_lengths, *, blank_index=0, ba
     return dense_target_scores(targets, target_lengths, device=logits.device)
 
 
+TargetAlignments = collections.namedtuple("TargetAlignments", ["logp", "times", "scores", "alignment"])
+
+
+def dense_target_alignments(targets, target_lengths, scores=False, alignment=False, device=None):
+    """Where in the audio each label of a supplied row lies: the forced Viterbi
+    alignment of every target under the logits of the calling thread's last
+    ``decode_dense(..., token_scores=True)`` or ``decode_greedy(...,
+    token_scores=True)`` on ``device`` (None: the current one) -- subtitle
+    timing, corpus segmentation, word timings for another pass's N-best.
+    Enqueued behind that decode on its stream without waiting for anything.
+    The first call of a shape sizes a workspace (``include/ctcext.h``, "Target
+    alignments") and may block; inside a ``torch.cuda.graph`` capture a call
+    that would have to grow it raises ``FailedPreconditionError``: call once
+    with the shape before capturing.
+
+    ``targets`` and ``target_lengths`` are as for ``dense_target_scores``.
+    Returns ``TargetAlignments(logp, times, scores, alignment)``: ``logp``
+    ``[B, N]`` of the compute dtype (the best alignment's log-probability),
+    ``times`` a ``TokenTimes`` of int32 ``[B, N, L]`` start and end frames and
+    ``[B, N]`` trailing blanks, ``scores`` a ``TokenScores`` ``[B, N, L]``
+    (``scores=True``, else None) and ``alignment`` int32 ``[B, N, T]``
+    (``alignment=True``, else None): per frame the class index, ``blank_index``
+    at a blank frame, -1 past the item's frames.  A row whose ``logp`` is
+    ``-inf`` (infeasible) or NaN (a label outside ``[0, C)``, a length outside
+    ``[0, L]``, an item with a status bit) is unaligned: times -1, scores NaN,
+    alignment -1.  Lists with ``L >= 64`` raise ``UnimplementedError``."""
+    what = "ctcext_dense_target_alignments without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = dec.lib
+    if not hasattr(lib, "ctcext_dense_target_alignments"):
+        raise UnimplementedError("this libctcext.so has no target alignments (CTCEXT_HAS_TARGET_ALIGNMENTS)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError("target alignments need a decode with token_scores=True",
+                                      _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    import torch
+    if not (_is_torch(targets) and _is_torch(target_lengths) and targets.is_cuda and target_lengths.is_cuda):
+        raise TypeError("dense_target_alignments: targets and target_lengths must be CUDA tensors")
+    if targets.dtype not in (torch.int64, torch.int32):
+        _type_error("targets", str(targets.dtype).replace("torch.", ""), "int32, int64")
+    if target_lengths.dtype != torch.int32:
+        _type_error("target_lengths", str(target_lengths.dtype).replace("torch.", ""), "int32")
+    if targets.device != dev or target_lengths.device != dev:
+        raise InvalidArgumentError("target alignments: the targets must be on the decode's device",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    shared = targets.dim() == 2
+    if targets.dim() not in (2, 3) or tuple(target_lengths.shape) != tuple(targets.shape[:-1]) or \
+            (not shared and targets.shape[0] != B):
+        raise InvalidArgumentError("target alignments: targets must be [B, N, L] or [N, L], and target_lengths [B, N] "
+                                   "or [N]", _lib.CTCEXT_INVALID_ARGUMENT)
+    targets, target_lengths = targets.contiguous(), target_lengths.contiguous()
+    N, L = int(targets.shape[-2]), int(targets.shape[-1])
+    t = _lib.Targets(targets.data_ptr(), target_lengths.data_ptr(), N, L, 1 if shared else 0,
+                     1 if targets.dtype == torch.int64 else 0)
+    with torch.cuda.device(dev):
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        logp = new((B, N), fdt)
+        tt = TokenTimes(new((B, N, L), torch.int32), new((B, N, L), torch.int32), new((B, N), torch.int32))
+        sc = TokenScores(new((B, N, L), fdt), new((B, N, L), fdt)) if scores else None
+        ali = new((B, N, T), torch.int32) if alignment else None
+    o = _lib.TargetAlignmentsOut(logp.data_ptr(), tt.start.data_ptr(), tt.end.data_ptr(), tt.trailing_blank.data_ptr(),
+                                 sc.logp_sum.data_ptr() if scores else None, sc.logp_min.data_ptr() if scores else None,
+                                 ali.data_ptr() if alignment else None)
+    rc = lib.ctcext_dense_target_alignments(dec.handle, ctypes.byref(t), ctypes.byref(o))
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return TargetAlignments(logp, tt, sc, ali)
+
+
+def forced_align(logits, lengths, targets, target_lengths, *, blank_index=0, batch_first=True, scores=False,
+                 alignment=False):
+    """``dense_target_alignments`` for logits nothing has decoded yet:
+    ``decode_greedy(..., token_scores=True)`` supplies the normaliser (its two
+    small kernels), then the targets are aligned behind it on the same stream.
+    Arguments as for ``decode_greedy`` and ``dense_target_alignments``; returns
+    the ``TargetAlignments``.  Nothing is waited for."""
+    decode_greedy(logits, lengths, batch_first=batch_first, blank_index=blank_index, token_scores=True)
+    return dense_target_alignments(targets, target_lengths, scores=scores, alignment=alignment, device=logits.device)
+
+
 def path_score_row(x, norm, decoded, frames, blank_index, blank_label=-1):
     """The definition of the path score for one row, on the host (no GPU), in
     long double: ``x`` is one item's logits ``[frames, num_classes]`` (float32

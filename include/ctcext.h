@@ -1213,8 +1213,9 @@ int ctcext_dense_path_scores_ms(ctcext_decoder* dec, double* ms);
  * The logits contract of "Token scores" applies unchanged.
  *
  * Not covered: streams; handles of more than one device
- * (CTCEXT_UNIMPLEMENTED); scorer-table terms; aligning transcripts the decode
- * did not return; checkpointing the back-pointers to shrink the workspace. */
+ * (CTCEXT_UNIMPLEMENTED); scorer-table terms; checkpointing the back-pointers
+ * to shrink the workspace.  (Aligning transcripts the decode did not return:
+ * "Target alignments".) */
 #define CTCEXT_HAS_PATH_ALIGNMENTS 1
 
 /* Device pointers (host pointers for ctcext_fetch_path_alignments without
@@ -1493,9 +1494,10 @@ int ctcext_greedy_stream_push_ms(ctcext_greedy_stream* s, double* ms);
  * every call, forces a route where the shape allows it.
  *
  * Not covered: streams (ctcext_stream_* over the score store); a synchronous
- * form after ctcext_decode; a forced Viterbi alignment of supplied targets;
- * handles of more than one device (CTCEXT_UNIMPLEMENTED); scorer-table
- * (bigram) terms; staging a compacted alphabet for wide vocabularies. */
+ * form after ctcext_decode; handles of more than one device
+ * (CTCEXT_UNIMPLEMENTED); scorer-table (bigram) terms; staging a compacted
+ * alphabet for wide vocabularies.  (Where each label of a target lies:
+ * "Target alignments".) */
 #define CTCEXT_HAS_TARGET_SCORES 1
 
 typedef struct {
@@ -1531,6 +1533,98 @@ int ctcext_dense_target_scores_route(ctcext_decoder* dec, int32_t* route);
 /* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
  * last target-scores kernels of a dense call in ms.  Waits for them. */
 int ctcext_dense_target_scores_ms(ctcext_decoder* dec, double* ms);
+
+/* ---------------------------------------------------------------------------
+ * Target alignments: the forced Viterbi alignment of label rows the CALLER
+ * supplies, on the device -- where in the audio each label of a reference
+ * transcript, a subtitle line or another pass's N-best entry lies, and how
+ * sure the model is of it.  The target scores say how likely such a row is;
+ * the path alignments time only the rows the decode returned.  New entry
+ * points and one new struct only (CTCEXT_ABI_VERSION is unchanged; detect them
+ * by CTCEXT_HAS_TARGET_ALIGNMENTS at build time or by symbol at run time).
+ *
+ * Definition (no new mathematics).  For item b and target n, y = targets[b][n]
+ * [0 .. target_length[b][n]) (ctcext_targets, as in "Target scores"), and the
+ * result is the definition of "Path alignments" applied to y, with the
+ * conventions of "Target scores": a target_length outside [0, max_target], a
+ * label outside [0, C) or an item with a status bit makes logp NaN; no
+ * blank_label is involved, and the blank_label rule does not apply.  Token
+ * times and token scores are the existing definitions applied to that
+ * alignment with merge = 0.  Outputs (device pointers):
+ *
+ *   logp            [batch][n_targets], compute dtype
+ *   start, end      int32 [batch][n_targets][max_target]
+ *   trailing_blank  int32 [batch][n_targets]
+ *   logp_sum, logp_min   [batch][n_targets][max_target], compute dtype; either
+ *                   or both may be NULL
+ *   alignment       int32 [batch][n_targets][max_time], or NULL: per frame the
+ *                   class index, blank_index at a blank frame, -1 at and past
+ *                   the item's frames
+ *
+ * An unaligned row (logp -inf or NaN) has times -1, trailing_blank 0, scores
+ * NaN and an alignment row of -1.  Cells at or past the target's length are
+ * -1 / NaN.  No exp or log is involved, so the kernel is held to the
+ * definition bit for bit, logp included (ctcext_path_alignment_row,
+ * ctcext_token_times_row, ctcext_token_scores_row).
+ *
+ * Route.  Lists of short targets (max_target <= 63) run in ONE kernel with the
+ * packed layout of the target scores: a segment of 8, 16, 32 or 64 lanes per
+ * target, 256 / segment targets of one item per workgroup, the staged LDS tile
+ * where ctcext_target_scores_tile allows it and gathered logits above.  The
+ * forward stores three decision bits per lane and frame, one 32-bit word per
+ * ctcext_target_alignments_word_frames() = 10 frames; the same kernel walks
+ * back over the words each lane stored itself, keeps every label's span in
+ * its lane and sums the span's log-posteriors.  Lists with max_target >= 64,
+ * and CTCEXT_TARGETS=rows: CTCEXT_UNIMPLEMENTED (the per-row kernels of the
+ * path alignments are not yet composed over supplied targets).
+ * CTCEXT_TARGETS=gathered forces the gathered route.
+ *
+ * Workspace.  batch * ceil(n_targets / (256 / segment)) * ceil(max_time / 10)
+ * * 1024 bytes of decision words (ctcext_target_alignments_bytes), grow-only.
+ * The first call of a shape may block (it allocates); a call that would have
+ * to grow it while the stream is capturing returns
+ * CTCEXT_FAILED_PRECONDITION and allocates nothing.
+ *
+ * The logits contract of "Token scores" applies unchanged.
+ *
+ * Not covered: max_target >= 64 (above); streams; handles of more than one
+ * device (CTCEXT_UNIMPLEMENTED); scorer-table terms; keeping the decision
+ * words in LDS for short max_time; a synchronous form. */
+#define CTCEXT_HAS_TARGET_ALIGNMENTS 1
+
+typedef struct {
+  void* logp;
+  void* start;
+  void* end;
+  void* trailing_blank;
+  void* logp_sum;   /* or NULL */
+  void* logp_min;   /* or NULL */
+  void* alignment;  /* or NULL */
+} ctcext_target_alignments_out;
+
+/* Host only: the frames one decision word holds (10). */
+int32_t ctcext_target_alignments_word_frames(void);
+/* Host only: bytes of the decision workspace of a call of this shape (the
+ * formula above); -1 for a negative argument or max_target > 63. */
+int64_t ctcext_target_alignments_bytes(int64_t batch, int64_t n_targets, int64_t max_target, int64_t max_time);
+/* Validates (ctcext_targets_validate; logp, trailing_blank and, with
+ * max_target > 0, start and end are required: CTCEXT_INVALID_ARGUMENT), then
+ * enqueues the kernel on the stream of the last ctcext_decode_dense /
+ * ctcext_decode_dense_skip / ctcext_decode_greedy, behind whatever that stream
+ * holds, over that call's logits (in place), normaliser, frames and final
+ * status word.  Waits for nothing; capturable into the same graph as the
+ * decode once the workspace holds the shape.  Without a preceding dense call:
+ * CTCEXT_FAILED_PRECONDITION.  n_targets == 0 or batch == 0: CTCEXT_OK with
+ * nothing launched. */
+int ctcext_dense_target_alignments(ctcext_decoder* dec, const ctcext_targets* targets,
+                                   const ctcext_target_alignments_out* out);
+/* Which route the last ctcext_dense_target_alignments behind the last dense
+ * call took: 1 packed and staged, 2 packed and gathered.
+ * CTCEXT_FAILED_PRECONDITION where none launched anything. */
+int ctcext_dense_target_alignments_route(ctcext_decoder* dec, int32_t* route);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
+ * last target-alignments kernel of a dense call in ms.  Waits for it. */
+int ctcext_dense_target_alignments_ms(ctcext_decoder* dec, double* ms);
 
 #ifdef __cplusplus
 }

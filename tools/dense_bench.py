@@ -39,6 +39,11 @@ whole call (events around it), beside the beam call of the same run
 (decode_dense, W and P of cfg3): its normaliser kernel -- the same read and the
 same class-order chain as the per-row kernel -- and its whole call.
 
+With --talign, instead: the target-alignments kernel (dense_target_alignments)
+at cfg3 on Gaussian and peaky logits, with the times alone and with scores and
+alignment rows, beside the target-scores kernel on the same targets and its own
+gathered route, in alternating rounds.
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -411,6 +416,64 @@ def targets_report(args):
     return lines, res
 
 
+def talign_report(args):
+    """--talign: the target-alignments kernel at cfg3 (times alone, and with scores and alignment rows) beside the
+    target-scores kernel on the same targets, and against its own gathered route (CTCEXT_TARGETS=gathered), in
+    alternating pairs; the kernels' own time by device events (ctcext_dense_target_*_ms).  The per-row route of the
+    issue's pairs does not exist yet, so those pairs are not timed."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    rng = np.random.default_rng(20261126)
+    lines = ["%-10s %-12s %10s %10s %10s %10s %9s %9s   (median of %d alternating pairs, ms; cfg3 B=%d T=%d C=%d)"
+             % ("inputs", "targets", "times", "all", "gathered", "scores-k", "t/scores", "t/gath", args.runs, B, T, C)]
+    res = {"runs": args.runs, "shape": [B, T, C], "talign": {}}
+
+    def once(x, y, n, what):
+        os.environ.pop("CTCEXT_TARGETS", None)
+        if what == "gathered":
+            os.environ["CTCEXT_TARGETS"] = "gathered"
+        torch.cuda.synchronize()
+        ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True, **KW)
+        ms = ctypes.c_double()
+        if what == "scores-k":
+            out = ctcext_amd.dense_target_scores(y, n)
+            rc = dec.lib.ctcext_dense_target_scores_ms(dec.handle, ctypes.byref(ms))
+        else:
+            out = ctcext_amd.dense_target_alignments(y, n, scores=what == "all", alignment=what == "all")
+            rc = dec.lib.ctcext_dense_target_alignments_ms(dec.handle, ctypes.byref(ms))
+        os.environ.pop("CTCEXT_TARGETS", None)
+        if rc != _lib.CTCEXT_OK:
+            raise SystemExit(dec.lib.ctcext_last_error().decode())
+        return ms.value, out
+
+    kinds = ("times", "all", "gathered", "scores-k")
+    for inputs in ("gaussian", "peaky"):
+        x = times_inputs(inputs, T, B, C)
+        for name, N, lo, hi in (("16 x 4..15", 16, 4, 15), ("4 x 40..60", 4, 40, 60), ("64 x 4..15", 64, 4, 15)):
+            y = torch.as_tensor(rng.integers(1, C, size=(B, N, hi)), device="cuda:0")
+            n = torch.as_tensor(rng.integers(lo, hi + 1, size=(B, N)).astype(np.int32), device="cuda:0")
+            for k in kinds:   # warm-up: kernels, the decision words
+                once(x, y, n, k)
+            t = {k: [] for k in kinds}
+            outs = {}
+            for _ in range(args.runs):   # alternating
+                for k in kinds:
+                    v, outs[k] = once(x, y, n, k)
+                    t[k].append(v)
+            a, g = outs["times"], outs["gathered"]
+            same = bool(torch.equal(a.logp, g.logp) and torch.equal(a.times.start, g.times.start) and
+                        torch.equal(a.times.end, g.times.end))
+            med = {k: statistics.median(v) for k, v in t.items()}
+            lines.append("%-10s %-12s %10.4f %10.4f %10.4f %10.4f %9.2f %9.2f   staged == gathered: %s; aligned %d of %d"
+                         % (inputs, name, med["times"], med["all"], med["gathered"], med["scores-k"],
+                            med["times"] / med["scores-k"], med["times"] / med["gathered"], same,
+                            int((a.logp > -np.inf).sum()), B * N))
+            res["talign"]["%s %s" % (inputs, name)] = dict({k: stat(v) for k, v in t.items()}, routes_identical=same,
+                                                          workspace_bytes=int(dec.lib.ctcext_target_alignments_bytes(B, N, hi, T)))
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -431,9 +494,11 @@ def main():
                     help="the path-alignment kernels' cost at cfg3, beside the path-scores kernels' of the same run")
     ap.add_argument("--targets", action="store_true",
                     help="the target-scores kernel at cfg3: the packed route against the per-row route of the same targets")
+    ap.add_argument("--talign", action="store_true",
+                    help="the target-alignments kernel at cfg3 beside the target-scores kernel and its own gathered route")
     args = ap.parse_args()
-    if args.times or args.scores or args.paths or args.align or args.greedy or args.targets:
-        lines, res = targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.times or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign:
+        lines, res = talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
