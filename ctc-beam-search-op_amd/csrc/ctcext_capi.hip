@@ -31,6 +31,7 @@
 #include "ctcx_stream_dense.h"
 #include "ctcx_stream_store.h"
 #include "ctcx_talign.h"
+#include "ctcx_transcripts.h"
 #include "ctcx_targets.h"
 #include "ctcx_times.h"
 
@@ -175,6 +176,7 @@ struct Dev {
   hipEvent_t sk[2] = {};     // ... of a skipping dense call: before the plan's normaliser, after the expansion
   hipEvent_t al[6] = {};     // ... of a dense call's path alignments: around the forward, walk back, emit, times, scores
   hipEvent_t ta[2] = {};     // ... of a dense call's target alignments: around the kernel
+  hipEvent_t tr[2] = {};     // ... of a dense call's transcript alignments: around the kernel
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf gk, glp;            // the greedy decode: the rows' arg-max [T][B] and max - norm [T][B]
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
@@ -234,6 +236,7 @@ struct ctcext_decoder {
     bool targets_timed = false; // events [11], [12] were recorded
     int talign_route = -1;      // the route of the last ctcext_dense_target_alignments behind it (-1: none)
     bool talign_timed = false;  // events ta[0], ta[1] were recorded
+    bool transcripts_timed = false;   // events tr[0], tr[1] were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -253,6 +256,7 @@ struct ctcext_decoder {
   // outputs of ctcext_fetch_path_alignments for host callers
   DevBuf al_bp, al_fin, al_vseq, al_vlen, al_out;
   DevBuf ta_bp;   // the target alignments' grow-only decision words (ctcx_talign.h)
+  DevBuf tr_bp;   // the transcript alignments' grow-only decision words (ctcx_transcripts.h)
   // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
   // the plan, and what the call that is running reads of it
   struct {
@@ -275,6 +279,8 @@ static void release_dev(Dev& d) {
   for (auto& ev : d.sk)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.ta)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : d.tr)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.al)
     if (ev) (void)hipEventDestroy(ev);
@@ -323,6 +329,7 @@ extern "C" int ctcext_create_sharded(const int* devices, int n_devices, ctcext_d
     for (auto& ev : v.sk) (void)hipEventCreate(&ev);
     for (auto& ev : v.al) (void)hipEventCreate(&ev);
     for (auto& ev : v.ta) (void)hipEventCreate(&ev);
+    for (auto& ev : v.tr) (void)hipEventCreate(&ev);
     // the shard inputs and the gathered walks move between the root and this
     // device by peer copies (xGMI); "already enabled" is fine
     if (v.device != devices[0]) {
@@ -348,7 +355,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out, &d->ta_bp,
+                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out, &d->ta_bp, &d->tr_bp,
                     &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
@@ -1436,6 +1443,7 @@ static int decode_dense(ctcext_decoder* d, const ctcext_decode_args* a, const ct
   d->dense.targets_timed = false;
   d->dense.talign_route = -1;
   d->dense.talign_timed = false;
+  d->dense.transcripts_timed = false;
   d->dense.pad_value = o ? o->pad_value : -1;
   d->dense.align_timed = 0;
   d->dense.greedy = false;
@@ -1678,6 +1686,7 @@ extern "C" int ctcext_decode_greedy(ctcext_decoder* d, const ctcext_decode_args*
   d->dense.targets_timed = false;
   d->dense.talign_route = -1;
   d->dense.talign_timed = false;
+  d->dense.transcripts_timed = false;
   d->dense.pad_value = o ? o->pad_value : -1;
   d->dense.align_timed = 0;
   d->dense.greedy = true;
@@ -3730,7 +3739,8 @@ extern "C" int ctcext_dense_target_alignments(ctcext_decoder* d, const ctcext_ta
   const int route = targets_route(d->dense.C, t->max_target, q.f64);
   if (route == 0)
     return fail(CTCEXT_UNIMPLEMENTED,
-                "target alignments: targets of more than 63 labels (and CTCEXT_TARGETS=rows) have no route yet");
+                "target alignments: targets of more than 63 labels (and CTCEXT_TARGETS=rows) run in "
+                "ctcext_dense_transcript_alignments");
   DeviceGuard guard;
   Dev& root = d->devs[0];
   HIP_OR_FAIL(hipSetDevice(root.device));
@@ -3790,6 +3800,99 @@ extern "C" int ctcext_dense_target_alignments_ms(ctcext_decoder* d, double* ms) 
   HIP_OR_FAIL(hipEventSynchronize(root.ta[1]));
   float f = 0;
   HIP_OR_FAIL(hipEventElapsedTime(&f, root.ta[0], root.ta[1]));
+  *ms = f;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Transcript alignments (ctcext.h, "Transcript alignments"): the target
+// alignments' definition and sources for rows of up to 2047 labels, in
+// ctcx_transcripts.hip's one kernel (a workgroup per target: the skewed forward,
+// the walk back, times and scores).
+
+extern "C" int32_t ctcext_transcript_alignments_block_frames(void) { return kTranscriptBlockFrames; }
+
+extern "C" int32_t ctcext_transcript_alignments_word_frames(int64_t max_target) {
+  return ctcx_transcript_word_frames(max_target);
+}
+
+extern "C" int64_t ctcext_transcript_alignments_bytes(int64_t batch, int64_t n_targets, int64_t max_target,
+                                                      int64_t max_time) {
+  return ctcx_transcript_bytes(batch, n_targets, max_target, max_time);
+}
+
+extern "C" int ctcext_dense_transcript_alignments(ctcext_decoder* d, const ctcext_targets* t,
+                                                  const ctcext_target_alignments_out* o) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_targets_validate(t);
+  if (rc != CTCEXT_OK) return rc;
+  if (!o) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_transcript_alignments without a ctcext_decode_dense");
+  if (d->devs.size() != 1)
+    return fail(CTCEXT_UNIMPLEMENTED, "transcript alignments need a one-device decoder handle");
+  d->dense.transcripts_timed = false;
+  if (d->dense.B == 0 || t->n_targets == 0) return CTCEXT_OK;
+  if (!o->logp || !o->trailing_blank || (t->max_target > 0 && (!o->start || !o->end)))
+    return fail(CTCEXT_INVALID_ARGUMENT, "transcript alignments need logp, start, end and trailing_blank");
+  if (!d->dense.sc.have)
+    return fail(CTCEXT_INTERNAL, "transcript alignments: the inputs of the last call are missing");
+  if (t->max_target > kTranscriptMaxTarget)
+    return fail(CTCEXT_UNIMPLEMENTED, "transcript alignments: targets of more than 2047 labels have no route");
+  if (d->dense.T > kTranscriptMaxTime)
+    return fail(CTCEXT_UNIMPLEMENTED, "transcript alignments: max_time above 13000 has no route");
+  const int64_t B = d->dense.B;
+  if (B * t->n_targets > 0x7fffffffLL)
+    return fail(CTCEXT_UNIMPLEMENTED, "transcript alignments: too many targets for one launch");
+  const ScoreSrc& q = d->dense.sc;
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  // the decision words: grow-only; a call that has to grow them may block, and is refused while the stream is capturing
+  const size_t want = (size_t)ctcx_transcript_bytes(B, t->n_targets, t->max_target, d->dense.T);
+  if (want > d->tr_bp.cap) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &st) != hipSuccess) (void)hipGetLastError();
+    if (st != hipStreamCaptureStatusNone)
+      return fail(CTCEXT_FAILED_PRECONDITION,
+                  "transcript alignments: the workspace must grow and the stream is capturing; call once with this "
+                  "shape before the capture");
+    HIP_OR_FAIL(d->tr_bp.ensure(want));
+  }
+  CtcxTalignParams p{};
+  p.t.targets = t->targets; p.t.target_length = t->target_length;
+  p.t.frames = (const int32_t*)root.dsl.p; p.t.status = (const int32_t*)root.dstat.p + B;
+  p.t.x = q.x; p.t.norm = q.norm;
+  p.t.Tmax = d->dense.T; p.t.B = B; p.t.C = d->dense.C; p.t.xst_t = q.st_t; p.t.xst_b = q.st_b;
+  p.t.N = t->n_targets; p.t.L = t->max_target;
+  p.t.xfmt = q.xfmt; p.t.f64 = q.f64 ? 1 : 0; p.t.blank_index = d->dense.blank_index;
+  p.t.shared = t->shared ? 1 : 0; p.t.labels_i64 = t->labels_i64 ? 1 : 0;
+  p.t.out = o->logp;
+  p.bp = (uint32_t*)d->tr_bp.p;
+  p.start = (int32_t*)o->start; p.end = (int32_t*)o->end; p.trailing_blank = (int32_t*)o->trailing_blank;
+  p.logp_sum = o->logp_sum; p.logp_min = o->logp_min; p.alignment = (int32_t*)o->alignment;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.tr[0], s));
+  HIP_OR_FAIL(ctcx_launch_transcript_align(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.tr[1], s));
+    d->dense.transcripts_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_transcript_alignments_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.transcripts_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no transcript alignments of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.tr[1]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.tr[0], root.tr[1]));
   *ms = f;
   return CTCEXT_OK;
 }

@@ -9,7 +9,8 @@ from .ops import (CTCExtBeamSearchDecoder, Decoder, DenseDecode, FailedPrecondit
                   path_scores, token_scores, token_scores_row, token_times, token_times_row,
                   PathAlignments, dense_path_alignments, path_alignments, path_alignment_row,
                   decode_greedy, greedy_row, GreedyPush, GreedyStream, dense_target_scores, score_targets,
-                  TargetAlignments, dense_target_alignments, forced_align)
+                  TargetAlignments, dense_target_alignments, forced_align, dense_transcript_alignments,
+                  align_transcripts)
 
 __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "StablePrefix", "StreamDense",
@@ -21,5 +22,6 @@ __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDeco
            "decode_greedy", "greedy_row", "GreedyStream", "GreedyPush",
            "dense_target_scores", "score_targets",
            "dense_target_alignments", "forced_align", "TargetAlignments",
+           "dense_transcript_alignments", "align_transcripts",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

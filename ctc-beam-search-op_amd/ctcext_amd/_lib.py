@@ -101,6 +101,11 @@ TARGET_ALIGNMENTS_SYMBOLS = ("ctcext_dense_target_alignments", "ctcext_target_al
                              "ctcext_target_alignments_word_frames", "ctcext_dense_target_alignments_route",
                              "ctcext_dense_target_alignments_ms")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TARGET_ALIGNMENTS_SYMBOLS
+# transcript alignments (CTCEXT_HAS_TRANSCRIPT_ALIGNMENTS)
+TRANSCRIPT_ALIGNMENTS_SYMBOLS = ("ctcext_dense_transcript_alignments", "ctcext_dense_transcript_alignments_ms",
+                                 "ctcext_transcript_alignments_bytes", "ctcext_transcript_alignments_block_frames",
+                                 "ctcext_transcript_alignments_word_frames")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TRANSCRIPT_ALIGNMENTS_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -526,6 +531,18 @@ def load():
         lib.ctcext_dense_target_alignments_route.restype = ctypes.c_int
         lib.ctcext_dense_target_alignments_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         lib.ctcext_dense_target_alignments_ms.restype = ctypes.c_int
+    if hasattr(lib, "ctcext_dense_transcript_alignments"):   # (CTCEXT_HAS_TRANSCRIPT_ALIGNMENTS)
+        lib.ctcext_dense_transcript_alignments.argtypes = [ctypes.c_void_p, ctypes.POINTER(Targets),
+                                                           ctypes.POINTER(TargetAlignmentsOut)]
+        lib.ctcext_dense_transcript_alignments.restype = ctypes.c_int
+        lib.ctcext_dense_transcript_alignments_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_transcript_alignments_ms.restype = ctypes.c_int
+        lib.ctcext_transcript_alignments_bytes.argtypes = [ctypes.c_int64] * 4
+        lib.ctcext_transcript_alignments_bytes.restype = ctypes.c_int64
+        lib.ctcext_transcript_alignments_block_frames.argtypes = []
+        lib.ctcext_transcript_alignments_block_frames.restype = ctypes.c_int32
+        lib.ctcext_transcript_alignments_word_frames.argtypes = [ctypes.c_int64]
+        lib.ctcext_transcript_alignments_word_frames.restype = ctypes.c_int32
     if hasattr(lib, "ctcext_stream_open_scores"):   # (CTCEXT_HAS_STREAM_SCORES; older builds stay loadable for A/B runs)
         lib.ctcext_stream_scores_validate.argtypes = [ctypes.POINTER(StreamArgs), ctypes.POINTER(StreamScoresArgs)]
         lib.ctcext_stream_scores_validate.restype = ctypes.c_int

@@ -1043,35 +1043,39 @@ def dense_target_alignments(targets, target_lengths, scores=False, alignment=Fal
     at a blank frame, -1 past the item's frames.  A row whose ``logp`` is
     ``-inf`` (infeasible) or NaN (a label outside ``[0, C)``, a length outside
     ``[0, L]``, an item with a status bit) is unaligned: times -1, scores NaN,
-    alignment -1.  Lists with ``L >= 64`` raise ``UnimplementedError``."""
-    what = "ctcext_dense_target_alignments without a ctcext_decode_dense"
+    alignment -1.  Lists with ``L >= 64`` raise ``UnimplementedError``: whole
+    transcripts go to ``dense_transcript_alignments``."""
+    return _target_alignments("ctcext_dense_target_alignments", "target alignments", "CTCEXT_HAS_TARGET_ALIGNMENTS",
+                              targets, target_lengths, scores, alignment, device)
+
+
+def _target_alignments(entry, name, macro, targets, target_lengths, scores, alignment, device):
+    """The body ``dense_target_alignments`` and ``dense_transcript_alignments`` share: the C entry point differs."""
+    what = entry + " without a ctcext_decode_dense"
     dec = _thread_decoder(device, what)
     lib = dec.lib
-    if not hasattr(lib, "ctcext_dense_target_alignments"):
-        raise UnimplementedError("this libctcext.so has no target alignments (CTCEXT_HAS_TARGET_ALIGNMENTS)",
-                                 _lib.CTCEXT_UNIMPLEMENTED)
+    if not hasattr(lib, entry):
+        raise UnimplementedError("this libctcext.so has no %s (%s)" % (name, macro), _lib.CTCEXT_UNIMPLEMENTED)
     if getattr(dec, "_times_dense", None) is None:
         raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
     shape = getattr(dec, "_scores_dense", None)
     if shape is None:
-        raise FailedPreconditionError("target alignments need a decode with token_scores=True",
-                                      _lib.CTCEXT_FAILED_PRECONDITION)
+        raise FailedPreconditionError(name + " need a decode with token_scores=True", _lib.CTCEXT_FAILED_PRECONDITION)
     B, P, T, dev, fdt = shape
     import torch
     if not (_is_torch(targets) and _is_torch(target_lengths) and targets.is_cuda and target_lengths.is_cuda):
-        raise TypeError("dense_target_alignments: targets and target_lengths must be CUDA tensors")
+        raise TypeError("dense_%s: targets and target_lengths must be CUDA tensors" % name.replace(" ", "_"))
     if targets.dtype not in (torch.int64, torch.int32):
         _type_error("targets", str(targets.dtype).replace("torch.", ""), "int32, int64")
     if target_lengths.dtype != torch.int32:
         _type_error("target_lengths", str(target_lengths.dtype).replace("torch.", ""), "int32")
     if targets.device != dev or target_lengths.device != dev:
-        raise InvalidArgumentError("target alignments: the targets must be on the decode's device",
-                                   _lib.CTCEXT_INVALID_ARGUMENT)
+        raise InvalidArgumentError(name + ": the targets must be on the decode's device", _lib.CTCEXT_INVALID_ARGUMENT)
     shared = targets.dim() == 2
     if targets.dim() not in (2, 3) or tuple(target_lengths.shape) != tuple(targets.shape[:-1]) or \
             (not shared and targets.shape[0] != B):
-        raise InvalidArgumentError("target alignments: targets must be [B, N, L] or [N, L], and target_lengths [B, N] "
-                                   "or [N]", _lib.CTCEXT_INVALID_ARGUMENT)
+        raise InvalidArgumentError(name + ": targets must be [B, N, L] or [N, L], and target_lengths [B, N] or [N]",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
     targets, target_lengths = targets.contiguous(), target_lengths.contiguous()
     N, L = int(targets.shape[-2]), int(targets.shape[-1])
     t = _lib.Targets(targets.data_ptr(), target_lengths.data_ptr(), N, L, 1 if shared else 0,
@@ -1085,7 +1089,7 @@ def dense_target_alignments(targets, target_lengths, scores=False, alignment=Fal
     o = _lib.TargetAlignmentsOut(logp.data_ptr(), tt.start.data_ptr(), tt.end.data_ptr(), tt.trailing_blank.data_ptr(),
                                  sc.logp_sum.data_ptr() if scores else None, sc.logp_min.data_ptr() if scores else None,
                                  ali.data_ptr() if alignment else None)
-    rc = lib.ctcext_dense_target_alignments(dec.handle, ctypes.byref(t), ctypes.byref(o))
+    rc = getattr(lib, entry)(dec.handle, ctypes.byref(t), ctypes.byref(o))
     if rc != _lib.CTCEXT_OK:
         _raise(lib, rc)
     return TargetAlignments(logp, tt, sc, ali)
@@ -1100,6 +1104,32 @@ def forced_align(logits, lengths, targets, target_lengths, *, blank_index=0, bat
     the ``TargetAlignments``.  Nothing is waited for."""
     decode_greedy(logits, lengths, batch_first=batch_first, blank_index=blank_index, token_scores=True)
     return dense_target_alignments(targets, target_lengths, scores=scores, alignment=alignment, device=logits.device)
+
+
+def dense_transcript_alignments(targets, target_lengths, scores=False, alignment=False, device=None):
+    """``dense_target_alignments`` for whole transcripts: the same arguments,
+    preconditions, definition and ``TargetAlignments`` result for targets of up
+    to 2047 labels, in a kernel of its own that gives every target a workgroup
+    (``include/ctcext.h``, "Transcript alignments").  Any ``L`` from 0 to 2047
+    runs there; for ``L <= 63`` the results equal ``dense_target_alignments``
+    bit for bit, which packs many short targets into a workgroup and is the
+    better choice for lists of them.  ``L > 2047`` or a decode with
+    ``max_time > 13000`` raises ``UnimplementedError``.  The workspace rule
+    under a ``torch.cuda.graph`` capture is that of
+    ``dense_target_alignments``, with a buffer of its own."""
+    return _target_alignments("ctcext_dense_transcript_alignments", "transcript alignments",
+                              "CTCEXT_HAS_TRANSCRIPT_ALIGNMENTS", targets, target_lengths, scores, alignment, device)
+
+
+def align_transcripts(logits, lengths, targets, target_lengths, *, blank_index=0, batch_first=True, scores=False,
+                      alignment=False):
+    """``dense_transcript_alignments`` for logits nothing has decoded yet, as
+    ``forced_align`` is to ``dense_target_alignments``: ``decode_greedy(...,
+    token_scores=True)`` supplies the normaliser, then the transcripts are
+    aligned behind it on the same stream.  Nothing is waited for."""
+    decode_greedy(logits, lengths, batch_first=batch_first, blank_index=blank_index, token_scores=True)
+    return dense_transcript_alignments(targets, target_lengths, scores=scores, alignment=alignment,
+                                       device=logits.device)
 
 
 def path_score_row(x, norm, decoded, frames, blank_index, blank_label=-1):

@@ -1575,8 +1575,8 @@ int ctcext_dense_target_scores_ms(ctcext_decoder* dec, double* ms);
  * ctcext_target_alignments_word_frames() = 10 frames; the same kernel walks
  * back over the words each lane stored itself, keeps every label's span in
  * its lane and sums the span's log-posteriors.  Lists with max_target >= 64,
- * and CTCEXT_TARGETS=rows: CTCEXT_UNIMPLEMENTED (the per-row kernels of the
- * path alignments are not yet composed over supplied targets).
+ * and CTCEXT_TARGETS=rows: CTCEXT_UNIMPLEMENTED here; whole transcripts run in
+ * ctcext_dense_transcript_alignments ("Transcript alignments", below).
  * CTCEXT_TARGETS=gathered forces the gathered route.
  *
  * Workspace.  batch * ceil(n_targets / (256 / segment)) * ceil(max_time / 10)
@@ -1625,6 +1625,74 @@ int ctcext_dense_target_alignments_route(ctcext_decoder* dec, int32_t* route);
 /* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
  * last target-alignments kernel of a dense call in ms.  Waits for it. */
 int ctcext_dense_target_alignments_ms(ctcext_decoder* dec, double* ms);
+
+/* ---------------------------------------------------------------------------
+ * Transcript alignments: "Target alignments" for whole transcripts -- a label
+ * row of up to 2047 labels against its utterance, for subtitle timing, corpus
+ * segmentation, or the word timings and confidences of another system's
+ * output.  New entry points only; the structs are ctcext_targets and
+ * ctcext_target_alignments_out (CTCEXT_ABI_VERSION is unchanged; detect them by
+ * CTCEXT_HAS_TRANSCRIPT_ALIGNMENTS at build time or by symbol at run time).
+ *
+ * Definition: that of "Target alignments", word for word -- "Path alignments"
+ * applied to targets[b][n][0 .. target_length[b][n]); a label outside [0, C) or
+ * a length outside [0, max_target] makes the row NaN before any logit is read
+ * with it; a row with more labels than the frames allow is -inf; every row of
+ * an item with a status bit is NaN; an unaligned row has times -1,
+ * trailing_blank 0, scores NaN and an alignment row of -1; blank frames of the
+ * alignment row read blank_index; no blank_label is involved.  No exp or log
+ * is involved, so the results equal the definition bit for bit, and for
+ * max_target <= 63 they equal ctcext_dense_target_alignments on the same
+ * inputs bit for bit.
+ *
+ * Route.  Any max_target from 0 to 2047 runs in ONE kernel, one launch: a
+ * workgroup of 256 threads (four waves) per target, grid batch * n_targets.
+ * Thread t holds K label pairs in registers, K the smallest of 1, 2, 4, 8 with
+ * 256 K > max_target.  The forward is skewed in time across the waves: frames
+ * are cut into blocks of ctcext_transcript_alignments_block_frames() = 20, wave
+ * w runs block p - w in phase p, and the one value a wave needs from the wave
+ * below crosses through LDS, one barrier per block.  A thread packs
+ * ctcext_transcript_alignments_word_frames(max_target) = 10, 5, 2 or 1 frames
+ * of decisions into a 32-bit word.  The same launch walks back (wave 0) and
+ * writes times, scores and the alignment row (all threads).  Lists of many
+ * short targets are served better by ctcext_dense_target_alignments, which
+ * packs several targets into a workgroup.
+ *
+ * Workspace.  batch * n_targets * ceil(max_time / word_frames) * 1024 bytes of
+ * decision words (ctcext_transcript_alignments_bytes), grow-only, in a buffer
+ * of its own.  The first call of a shape may block (it allocates); a call that
+ * would have to grow it while the stream is capturing returns
+ * CTCEXT_FAILED_PRECONDITION and allocates nothing.
+ *
+ * The logits contract of "Token scores" applies unchanged.
+ *
+ * Not covered: max_target > 2047 or max_time > 13000 (CTCEXT_UNIMPLEMENTED);
+ * streams; handles of more than one device (CTCEXT_UNIMPLEMENTED); K chosen
+ * per target instead of per call; LDS staging of the logits rows; scorer-table
+ * terms; a synchronous form. */
+#define CTCEXT_HAS_TRANSCRIPT_ALIGNMENTS 1
+
+/* Host only: the frames of one forward block (20). */
+int32_t ctcext_transcript_alignments_block_frames(void);
+/* Host only: the frames one decision word holds for this max_target (10 up to
+ * 255 labels, 5 up to 511, 2 up to 1023, 1 up to 2047); 0 where no K holds it. */
+int32_t ctcext_transcript_alignments_word_frames(int64_t max_target);
+/* Host only: bytes of the decision workspace of a call of this shape (the
+ * formula above); -1 for a negative argument or max_target > 2047. */
+int64_t ctcext_transcript_alignments_bytes(int64_t batch, int64_t n_targets, int64_t max_target, int64_t max_time);
+/* As ctcext_dense_target_alignments: validates (ctcext_targets_validate; logp,
+ * trailing_blank and, with max_target > 0, start and end are required:
+ * CTCEXT_INVALID_ARGUMENT), then enqueues the kernel on the stream of the last
+ * ctcext_decode_dense / ctcext_decode_dense_skip / ctcext_decode_greedy, over
+ * that call's logits (in place), normaliser, frames and final status word.
+ * Waits for nothing; capturable once the workspace holds the shape.  Without a
+ * preceding dense call: CTCEXT_FAILED_PRECONDITION.  n_targets == 0 or
+ * batch == 0: CTCEXT_OK with nothing launched. */
+int ctcext_dense_transcript_alignments(ctcext_decoder* dec, const ctcext_targets* targets,
+                                       const ctcext_target_alignments_out* out);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
+ * last transcript-alignments kernel of a dense call in ms.  Waits for it. */
+int ctcext_dense_transcript_alignments_ms(ctcext_decoder* dec, double* ms);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,13 @@ at cfg3 on Gaussian and peaky logits, with the times alone and with scores and
 alignment rows, beside the target-scores kernel on the same targets and its own
 gathered route, in alternating rounds.
 
+With --transcripts, instead: the transcript-alignments kernel
+(dense_transcript_alignments) at cfg3 on Gaussian and peaky logits, each item's
+target its own greedy-decoded row, with the times alone and with scores and
+alignment rows, beside dense_path_alignments(times=True, scores=True) on the
+same rows (its five launches together), in alternating rounds; then the
+Gaussian rows cut to 255, 511 and 1023 labels, so that every K is timed.
+
 Prints one table per shape and one JSON line.  It is a report, not a check
 (it does stop if the dense outputs differ from the synchronous ones), and it
 does not touch bench.py.
@@ -474,6 +481,68 @@ def talign_report(args):
     return lines, res
 
 
+def transcripts_report(args):
+    """--transcripts: the transcript-alignments kernel at cfg3, one target per item (its own greedy row), beside the
+    path-alignment kernels on the same rows, in alternating rounds; the kernels' own time by device events
+    (ctcext_dense_transcript_alignments_ms, ctcext_dense_path_alignments_ms).  Rows cut short have no yardstick:
+    the path alignments take only the rows the decode returned."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    lines = ["%-10s %-12s %3s %10s %10s %10s %8s %8s   (median of %d alternating rounds, ms; cfg3 B=%d T=%d C=%d, N=1)"
+             % ("inputs", "labels", "K", "times", "all", "path-align", "t/path", "all/path", args.runs, B, T, C)]
+    res = {"runs": args.runs, "shape": [B, T, C], "transcripts": {}}
+
+    def once(x, y, n, what):
+        torch.cuda.synchronize()
+        ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True)
+        ms, five = ctypes.c_double(), (ctypes.c_double * 5)()
+        if what == "path-align":
+            out = ctcext_amd.dense_path_alignments(times=True, scores=True)
+            rc = dec.lib.ctcext_dense_path_alignments_ms(dec.handle, five)
+            ms.value = sum(five)
+        else:
+            out = ctcext_amd.dense_transcript_alignments(y, n, scores=what == "all", alignment=what == "all")
+            rc = dec.lib.ctcext_dense_transcript_alignments_ms(dec.handle, ctypes.byref(ms))
+        if rc != _lib.CTCEXT_OK:
+            raise SystemExit(dec.lib.ctcext_last_error().decode())
+        return ms.value, out
+
+    for inputs, caps in (("gaussian", (None, 255, 511, 1023)), ("peaky", (None,))):
+        x = times_inputs(inputs, T, B, C)
+        g = ctcext_amd.decode_greedy(x, sl, batch_first=False, token_scores=True)
+        torch.cuda.synchronize()
+        for cap in caps:
+            L = min(int(g.decoded_lengths.max()), cap or T)
+            y, n = g.decoded[:, :, :L].contiguous(), g.decoded_lengths.clamp(max=L)
+            kinds = ("times", "all") + (() if cap else ("path-align",))
+            for k in kinds:   # warm-up: kernels, the decision words
+                once(x, y, n, k)
+            t, outs = {k: [] for k in kinds}, {}
+            for _ in range(args.runs):   # alternating
+                for k in kinds:
+                    v, outs[k] = once(x, y, n, k)
+                    t[k].append(v)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            a, pa = outs["all"], outs.get("path-align")
+            eq = lambda u, v: bool(torch.equal(u.isnan(), v.isnan()) and torch.equal(u.nan_to_num(), v.nan_to_num()))
+            same = pa is None or (eq(a.logp, pa.logp) and torch.equal(a.times.start, pa.times.start[..., :L]) and
+                                  torch.equal(a.times.end, pa.times.end[..., :L]) and
+                                  eq(a.scores.logp_sum, pa.scores.logp_sum[..., :L]) and
+                                  eq(a.scores.logp_min, pa.scores.logp_min[..., :L]))   # (cells past a row's labels are NaN)
+            K = next(k for k in (1, 2, 4, 8) if 256 * k > L)
+            yard = ("%10.4f %8.2f %8.2f" % (med["path-align"], med["times"] / med["path-align"], med["all"] / med["path-align"])
+                    if pa is not None else "%10s %8s %8s" % ("-", "-", "-"))
+            lines.append("%-10s %4d..%-6d %3d %10.4f %10.4f %s   equal to the path alignments: %s; aligned %d of %d"
+                         % (inputs, int(n.min()), int(n.max()), K, med["times"], med["all"], yard,
+                            same if pa is not None else "-", int((a.logp > -np.inf).sum()), B))
+            res["transcripts"]["%s L=%d" % (inputs, L)] = dict(
+                {k: stat(v) for k, v in t.items()}, K=K, equal=same,
+                workspace_bytes=int(dec.lib.ctcext_transcript_alignments_bytes(B, 1, L, T)),
+                path_alignments_workspace_bytes=int(dec.lib.ctcext_path_alignments_row_bytes(T)) * B)
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -496,9 +565,11 @@ def main():
                     help="the target-scores kernel at cfg3: the packed route against the per-row route of the same targets")
     ap.add_argument("--talign", action="store_true",
                     help="the target-alignments kernel at cfg3 beside the target-scores kernel and its own gathered route")
+    ap.add_argument("--transcripts", action="store_true",
+                    help="the transcript-alignments kernel at cfg3 beside the path-alignment kernels on the same rows")
     args = ap.parse_args()
-    if args.times or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign:
-        lines, res = talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.times or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign or args.transcripts:
+        lines, res = transcripts_report(args) if args.transcripts else talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
