@@ -103,17 +103,58 @@ def case(name):
     return c
 
 
-def _check(got, want, what=""):
+def _check(got, want, what="", E=E_T):
     torch.cuda.synchronize()
     got = got.cpu().numpy()
     for mask in (np.isnan, np.isneginf, np.isposinf):
         np.testing.assert_array_equal(mask(got), mask(want), err_msg="%s: %s cells" % (what, mask.__name__))
     fin = np.isfinite(want)
     err = np.abs(got[fin].astype(np.longdouble) - want[fin])
-    tol = 4 * E_T[got.dtype.type]
+    tol = 4 * E[got.dtype.type]
     print(what, "largest error %.3g of %.3g" % (err.max() if err.size else 0, tol))
     assert (err <= tol).all(), (what, err.max())
     return got
+
+
+# The inputs of tie_inputs and a blank_index other than 0.  E_NEW is E_T's measurement over the finite expected cells of
+# NEW_CASES alone, so that no case above gets a wider bound (float32 1.9647e-5 and float64 3.1787e-14, both on the
+# blank5-sticky inputs); test_cpu_alignment_inputs holds each constant to its measured figure from both sides.
+E_NEW = {np.float32: 1.965e-5, np.float64: 3.18e-14}
+ROUTES = {"staged": dict(route=1), "gathered": dict(route=2, env="gathered"), "rows": dict(route=0, env="rows")}
+
+
+def _planted(name, kind, dtype, edges=False):
+    import tie_inputs
+    return tie_inputs.planted_case("target scores " + name, kind, 15, 12, dtype=dtype, edges=edges)
+
+
+def _blank_case(blank, kind, dtype):
+    c = _case(22, [22, 17, 0], 15, kind="sticky", dtype=dtype, blank=blank)
+    if kind == "flat":
+        c["x"] = np.zeros_like(c["x"])
+    return c
+
+
+NEW_CASES = {}
+for _dt in (np.float32, np.float64):
+    for _r, _kw in ROUTES.items():
+        _tag = "%s-%s" % (_r, _dt.__name__)
+        NEW_CASES["masked-" + _tag] = (functools.partial(_planted, "masked-" + _dt.__name__, "masked", _dt), _kw)
+        NEW_CASES["nonfinite-" + _tag] = (functools.partial(_planted, "nonfinite-" + _dt.__name__, "nonfinite", _dt), _kw)
+        NEW_CASES["nonfinite-edges-" + _tag] = (
+            functools.partial(_planted, "nonfinite-edges-" + _dt.__name__, "nonfinite", _dt, edges=True), _kw)
+        for _b in (5, 2):
+            for _k in ("sticky", "flat"):
+                NEW_CASES["blank%d-%s-%s" % (_b, _k, _tag)] = (functools.partial(_blank_case, _b, _k, _dt), _kw)
+
+
+@functools.lru_cache(maxsize=None)
+def new_case(name):
+    build, kw = NEW_CASES[name]
+    c = dict(build(), **kw)
+    c["want"] = expected(c["x"], c["sl"], c["y"], c["n"], blank=c["blank"])
+    assert np.isfinite(c["want"]).any() and np.isnan(c["want"]).any(), name
+    return c
 
 
 def _route():
@@ -144,6 +185,20 @@ def test_matches_definition(name, monkeypatch):
     got = _score(x, c["sl"], c["y"], c["n"], **kw)
     assert got.is_cuda and tuple(got.shape) == c["n"].shape and got.dtype == getattr(torch, c["x"].dtype.name)
     _check(got, c["want"], name)
+    assert _route() == c["route"]
+
+
+@pytest.mark.parametrize("name", list(NEW_CASES))
+def test_matches_definition_on_masked_nonfinite_and_other_blanks(name, monkeypatch):
+    """-inf logits under a feasible target (and rows whose every alignment passes one: -inf, never NaN), an item
+    with a NaN, a +inf or a frame of -inf (NaN, as the normaliser is), and blank_index 5 and 2 of 6 classes."""
+    c = new_case(name)
+    monkeypatch.delenv("CTCEXT_TARGETS", raising=False)
+    if "env" in c:
+        monkeypatch.setenv("CTCEXT_TARGETS", c["env"])
+    got = _score(np.array(c["x"]), c["sl"], c["y"], c["n"], blank_index=c["blank"])
+    assert tuple(got.shape) == c["n"].shape and got.dtype == getattr(torch, c["x"].dtype.name)
+    _check(got, c["want"], name, E_NEW)
     assert _route() == c["route"]
 
 
