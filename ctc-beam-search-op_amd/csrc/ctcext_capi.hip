@@ -32,6 +32,7 @@
 #include "ctcx_stream_store.h"
 #include "ctcx_talign.h"
 #include "ctcx_transcripts.h"
+#include "ctcx_prefix.h"
 #include "ctcx_targets.h"
 #include "ctcx_times.h"
 
@@ -177,6 +178,7 @@ struct Dev {
   hipEvent_t al[6] = {};     // ... of a dense call's path alignments: around the forward, walk back, emit, times, scores
   hipEvent_t ta[2] = {};     // ... of a dense call's target alignments: around the kernel
   hipEvent_t tr[2] = {};     // ... of a dense call's transcript alignments: around the kernel
+  hipEvent_t px[3] = {};     // ... of a dense call's prefix scores: before Kernel A, between the two, after Kernel B
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf gk, glp;            // the greedy decode: the rows' arg-max [T][B] and max - norm [T][B]
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
@@ -237,6 +239,7 @@ struct ctcext_decoder {
     int talign_route = -1;      // the route of the last ctcext_dense_target_alignments behind it (-1: none)
     bool talign_timed = false;  // events ta[0], ta[1] were recorded
     bool transcripts_timed = false;   // events tr[0], tr[1] were recorded
+    bool prefix_timed = false;        // events px[0 .. 3) were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -257,6 +260,7 @@ struct ctcext_decoder {
   DevBuf al_bp, al_fin, al_vseq, al_vlen, al_out;
   DevBuf ta_bp;   // the target alignments' grow-only decision words (ctcx_talign.h)
   DevBuf tr_bp;   // the transcript alignments' grow-only decision words (ctcx_transcripts.h)
+  DevBuf px_ws;   // the prefix scores' grow-only tails workspace (ctcx_prefix.h)
   // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
   // the plan, and what the call that is running reads of it
   struct {
@@ -281,6 +285,8 @@ static void release_dev(Dev& d) {
   for (auto& ev : d.ta)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.tr)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : d.px)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.al)
     if (ev) (void)hipEventDestroy(ev);
@@ -330,6 +336,7 @@ extern "C" int ctcext_create_sharded(const int* devices, int n_devices, ctcext_d
     for (auto& ev : v.al) (void)hipEventCreate(&ev);
     for (auto& ev : v.ta) (void)hipEventCreate(&ev);
     for (auto& ev : v.tr) (void)hipEventCreate(&ev);
+    for (auto& ev : v.px) (void)hipEventCreate(&ev);
     // the shard inputs and the gathered walks move between the root and this
     // device by peer copies (xGMI); "already enabled" is fine
     if (v.device != devices[0]) {
@@ -355,7 +362,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out, &d->ta_bp, &d->tr_bp,
+                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out, &d->ta_bp, &d->tr_bp, &d->px_ws,
                     &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
@@ -3705,6 +3712,96 @@ extern "C" int ctcext_dense_target_scores_ms(ctcext_decoder* d, double* ms) {
   float f = 0;
   HIP_OR_FAIL(hipEventElapsedTime(&f, root.ev[11], root.ev[12]));
   *ms = f;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Prefix scores (ctcext.h, "Prefix scores"): the target scores' sources and
+// packed trellis, in ctcx_prefix.hip's two kernels (the forward with tails, the
+// extension reduce) over a grow-only tails workspace.
+
+static_assert(CTCEXT_PREFIX_TIME_TILE == kPrefixTile && CTCEXT_PREFIX_NARROW_SLICES == kPrefixNarrowSlices,
+              "ctcext.h states the reduce kernel's tile and slices");
+
+extern "C" int32_t ctcext_prefix_scores_layout(int64_t num_classes, int32_t f64) {
+  return ctcx_prefix_layout(num_classes, f64);
+}
+
+extern "C" int ctcext_dense_prefix_scores(ctcext_decoder* d, const ctcext_targets* t, void* ext_logp) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_targets_validate(t);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_prefix_scores without a ctcext_decode_dense");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "prefix scores need a one-device decoder handle");
+  d->dense.prefix_timed = false;
+  if (!d->dense.sc.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "prefix scores need a dense call that kept its logits and normaliser");
+  if (d->dense.B == 0 || t->n_targets == 0) return CTCEXT_OK;
+  if (!ext_logp) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ScoreSrc& q = d->dense.sc;
+  const int route = targets_route(d->dense.C, t->max_target, q.f64);   // (CTCEXT_TARGETS forces Kernel A's route)
+  if (route == 0 && !ctcx_prefix_rows_fit(t->max_target, d->dense.T, q.f64 ? 1 : 0))
+    return fail(CTCEXT_UNIMPLEMENTED, "prefix scores: rows this wide do not fit the LDS trellis");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  // the tails: grow-only; a call that has to grow them may block, and is refused while the stream is capturing
+  const size_t want = (size_t)ctcx_prefix_bytes(B, t->n_targets, d->dense.T, q.f64 ? 1 : 0);
+  if (want > d->px_ws.cap) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &st) != hipSuccess) (void)hipGetLastError();
+    if (st != hipStreamCaptureStatusNone)
+      return fail(CTCEXT_FAILED_PRECONDITION,
+                  "prefix scores: the workspace must grow and the stream is capturing; call once with this shape "
+                  "before the capture");
+    HIP_OR_FAIL(d->px_ws.ensure(want));
+  }
+  CtcxPrefixParams p{};
+  p.t.targets = t->targets; p.t.target_length = t->target_length;
+  p.t.frames = (const int32_t*)root.dsl.p; p.t.status = (const int32_t*)root.dstat.p + B;
+  p.t.x = q.x; p.t.norm = q.norm;
+  p.t.Tmax = d->dense.T; p.t.B = B; p.t.C = d->dense.C; p.t.xst_t = q.st_t; p.t.xst_b = q.st_b;
+  p.t.N = t->n_targets; p.t.L = t->max_target;
+  p.t.xfmt = q.xfmt; p.t.f64 = q.f64 ? 1 : 0; p.t.blank_index = d->dense.blank_index;
+  p.t.shared = t->shared ? 1 : 0; p.t.labels_i64 = t->labels_i64 ? 1 : 0;
+  p.t.staged = route == 1 ? 1 : 0;
+  p.rows = route == 0 ? 1 : 0;
+  p.tails = d->px_ws.p;
+  p.info = (int32_t*)((char*)d->px_ws.p + ctcx_prefix_tails_bytes(B, t->n_targets, d->dense.T, p.t.f64));
+  p.ext = ext_logp;
+  // CTCEXT_PREFIX=narrow|wide (diagnostics; read at every call)
+  const char* v = getenv("CTCEXT_PREFIX");
+  const std::string want_layout = v ? v : "";
+  p.layout = want_layout == "narrow" ? 0 : want_layout == "wide" ? 1 : ctcx_prefix_layout(p.t.C, p.t.f64);
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.px[0], s));
+  HIP_OR_FAIL(ctcx_launch_prefix_tails(p, s));
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.px[1], s));
+  HIP_OR_FAIL(ctcx_launch_prefix_reduce(p, s));
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.px[2], s));
+    d->dense.prefix_timed = true;
+  }
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_prefix_scores_ms(ctcext_decoder* d, double* tails_ms, double* reduce_ms) {
+  if (!d || !tails_ms || !reduce_ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.prefix_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no prefix scores of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.px[2]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.px[0], root.px[1]));
+  *tails_ms = f;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.px[1], root.px[2]));
+  *reduce_ms = f;
   return CTCEXT_OK;
 }
 

@@ -249,3 +249,6 @@ hipError_t ctcx_launch_target_scores(const CtcxTargetsParams& p, hipStream_t s) 
   if (p.xfmt == kPathsInBF16) return launch_all<float, kPathsInBF16>(p, s);
   return launch_all<float, kPathsInNative>(p, s);
 }
+
+// (ctcx_prefix.hip's ctcx_prefix_tails is this kernel's twin: the same segments, exchange, staging and
+// renormalisation, with two stores a frame.  A change of the recursion above belongs there as well.)

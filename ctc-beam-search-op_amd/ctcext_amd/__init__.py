@@ -10,7 +10,7 @@ from .ops import (CTCExtBeamSearchDecoder, Decoder, DenseDecode, FailedPrecondit
                   PathAlignments, dense_path_alignments, path_alignments, path_alignment_row,
                   decode_greedy, greedy_row, GreedyPush, GreedyStream, dense_target_scores, score_targets,
                   TargetAlignments, dense_target_alignments, forced_align, dense_transcript_alignments,
-                  align_transcripts)
+                  align_transcripts, dense_prefix_scores, score_prefixes, prefix_score_row)
 
 __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "StablePrefix", "StreamDense",
@@ -23,5 +23,6 @@ __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDeco
            "dense_target_scores", "score_targets",
            "dense_target_alignments", "forced_align", "TargetAlignments",
            "dense_transcript_alignments", "align_transcripts",
+           "dense_prefix_scores", "score_prefixes", "prefix_score_row",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

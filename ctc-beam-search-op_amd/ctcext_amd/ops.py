@@ -1018,6 +1018,104 @@ def score_targets(logits, lengths, targets, target_lengths, *, blank_index=0, ba
     return dense_target_scores(targets, target_lengths, device=logits.device)
 
 
+def _prefix_lib(lib):
+    if not hasattr(lib, "ctcext_dense_prefix_scores"):
+        raise UnimplementedError("this libctcext.so has no prefix scores (CTCEXT_HAS_PREFIX_SCORES)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+def dense_prefix_scores(prefixes, prefix_lengths, device=None):
+    """What an external beam search asks at every step: for every partial
+    hypothesis ``g`` supplied and every class ``c`` at once, the CTC prefix
+    score ``log p(transcript begins with g, c | x)`` under the logits of the
+    calling thread's last ``decode_dense(..., token_scores=True)`` or
+    ``decode_greedy(..., token_scores=True)`` on ``device`` (None: the current
+    one).  Enqueued behind that decode on its stream; after one call of a
+    shape nothing is allocated or waited for, so it can be captured into the
+    same ``torch.cuda.graph``.
+
+    ``prefixes`` is a CUDA int64 or int32 tensor ``[B, N, L]``, or ``[N, L]``
+    for one list shared by all items; ``prefix_lengths`` is a
+    CUDA int32 tensor ``[B, N]`` or ``[N]`` to match.  Returns a CUDA tensor
+    ``[B, N, C]`` of the compute dtype: the "Prefix scores" definition of
+    ``include/ctcext.h``.  The blank column holds the end score, the path score
+    of ``g`` itself.  An infeasible prefix gives a row of ``-inf``; a label
+    outside ``[0, C)``, a length outside ``[0, L]`` or an item with a status
+    bit a row of NaN.  Acoustic scores only."""
+    what = "ctcext_dense_prefix_scores without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = _prefix_lib(dec.lib)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError("prefix scores need a decode with token_scores=True",
+                                      _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    import torch
+    if not (_is_torch(prefixes) and _is_torch(prefix_lengths) and prefixes.is_cuda and prefix_lengths.is_cuda):
+        raise TypeError("dense_prefix_scores: prefixes and prefix_lengths must be CUDA tensors")
+    if prefixes.dtype not in (torch.int64, torch.int32):
+        _type_error("prefixes", str(prefixes.dtype).replace("torch.", ""), "int32, int64")
+    if prefix_lengths.dtype != torch.int32:
+        _type_error("prefix_lengths", str(prefix_lengths.dtype).replace("torch.", ""), "int32")
+    if prefixes.device != dev or prefix_lengths.device != dev:
+        raise InvalidArgumentError("prefix scores: the prefixes must be on the decode's device",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    shared = prefixes.dim() == 2
+    if prefixes.dim() not in (2, 3) or tuple(prefix_lengths.shape) != tuple(prefixes.shape[:-1]) or \
+            (not shared and prefixes.shape[0] != B):
+        raise InvalidArgumentError("prefix scores: prefixes must be [B, N, L] or [N, L], and prefix_lengths [B, N] or [N]",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    prefixes, prefix_lengths = prefixes.contiguous(), prefix_lengths.contiguous()
+    N, L = int(prefixes.shape[-2]), int(prefixes.shape[-1])
+    t = _lib.Targets(prefixes.data_ptr(), prefix_lengths.data_ptr(), N, L, 1 if shared else 0,
+                     1 if prefixes.dtype == torch.int64 else 0)
+    with torch.cuda.device(dev):
+        out = torch.empty((B, N, int(dec._scores_keep.shape[-1])), dtype=fdt, device=dev)   # (the kept logits: classes last)
+    rc = lib.ctcext_dense_prefix_scores(dec.handle, ctypes.byref(t), out.data_ptr())
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return out
+
+
+def score_prefixes(logits, lengths, prefixes, prefix_lengths, *, blank_index=0, batch_first=True):
+    """``dense_prefix_scores`` for logits nothing has decoded yet:
+    ``decode_greedy(..., token_scores=True)`` supplies the normaliser, then the
+    prefixes are scored behind it on the same stream.  Arguments as for
+    ``decode_greedy`` and ``dense_prefix_scores``; returns the CUDA tensor
+    ``[B, N, C]``."""
+    decode_greedy(logits, lengths, batch_first=batch_first, blank_index=blank_index, token_scores=True)
+    return dense_prefix_scores(prefixes, prefix_lengths, device=logits.device)
+
+
+def prefix_score_row(x, norm, prefix, frames, blank_index):
+    """The definition of the prefix scores for one prefix, on the host (no
+    GPU), in long double: ``x`` is one item's logits ``[frames, num_classes]``
+    (float32 or float64, the compute dtype), ``norm`` its rows' normaliser
+    ``[frames]``, ``prefix`` the label row (without padding).  Returns a numpy
+    array ``[num_classes]`` of ``x``'s dtype."""
+    lib = _prefix_lib(_lib.load())
+    x = np.asarray(x)
+    dt = np.float64 if x.dtype == np.float64 else np.float32
+    frames = int(frames)
+    if x.ndim != 2:
+        raise ValueError("prefix_score_row: x must be [frames, num_classes]")
+    C = int(x.shape[1])
+    x = np.ascontiguousarray(x[:frames], dtype=dt)
+    nm = np.ascontiguousarray(np.asarray(norm).reshape(-1)[:frames], dtype=dt)
+    if x.shape[0] != frames or nm.size != frames:
+        raise ValueError("prefix_score_row: x and norm must hold the item's frames")
+    g = np.ascontiguousarray(np.asarray(prefix, dtype=np.int64).reshape(-1))
+    out = np.empty((max(C, 1),), dt)
+    rc = lib.ctcext_prefix_score_row(x.ctypes.data, nm.ctypes.data, 1 if dt == np.float64 else 0, frames, C,
+                                     _ptr(g, ctypes.c_int64), int(g.size), int(blank_index), out.ctypes.data)
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_prefix_score_row: bad arguments", rc)
+    return out[:C]
+
+
 TargetAlignments = collections.namedtuple("TargetAlignments", ["logp", "times", "scores", "alignment"])
 
 

@@ -1535,6 +1535,95 @@ int ctcext_dense_target_scores_route(ctcext_decoder* dec, int32_t* route);
 int ctcext_dense_target_scores_ms(ctcext_decoder* dec, double* ms);
 
 /* ---------------------------------------------------------------------------
+ * Prefix scores: the CTC prefix score of every one-label extension of partial
+ * hypotheses the CALLER supplies, on the device -- what an external beam
+ * search (joint CTC/attention decoding, shallow fusion over a BPE alphabet)
+ * asks of the acoustic model at every step: how likely is it that the
+ * transcript BEGINS with g followed by class c, for every c at once.  The
+ * target scores answer a different question (g.c as a whole transcript).  New
+ * entry points only (CTCEXT_ABI_VERSION is unchanged; detect them by
+ * CTCEXT_HAS_PREFIX_SCORES at build time or by symbol at run time);
+ * ctcext_targets and ctcext_targets_validate are reused as they are.
+ *
+ * Definition.  For item b and prefix n, g = prefixes[b][n][0 ..
+ * prefix_length[b][n]) with m labels.  The recursion is that of "Path scores"
+ * applied to g: lp[f][c] = x[f][c] - norm[f] as one rounded subtraction in the
+ * compute dtype, the same frames, blank = blank_index, S = 2m + 1 states,
+ * start, alpha_f[s] and skip rule.  Two tail values a frame:
+ *   bl_f = alpha_f[2m];   nb_f = alpha_f[2m - 1] for m > 0, else -inf.
+ * For every class c != blank:
+ *   phi_f(c)  = bl_f if m > 0 and c == g[m - 1], else LSE(bl_f, nb_f)
+ *   term_0(c) = lp[0][c] if m == 0, else -inf
+ *   term_f(c) = phi_{f-1}(c) + lp[f][c]          for 1 <= f < frames
+ *   ext[b][n][c] = LSE over f in [0, frames) of term_f(c),
+ * the log of the total probability of all label sequences that start with g
+ * followed by c.  The blank column holds the end score, ext[b][n][blank] =
+ * LSE(bl_{frames-1}, nb_{frames-1}): the path score of g itself, which a
+ * search needs to close a hypothesis (a blank is never an extension).  For
+ * m == 0 the LSE over all C columns is 0, up to the normaliser's rounding.
+ *
+ * Conventions, as in "Target scores": LSE of all -inf is -inf, never NaN;
+ * frames == 0 gives -inf everywhere except the blank column of an empty
+ * prefix, which is 0; an infeasible g gives a row of -inf; a label outside
+ * [0, C), a length outside [0, max_target] or an item with a status bit makes
+ * the whole row of C values NaN.  No blank_label is involved.  The values are
+ * acoustic only (no scorer-table terms); after a skipping decode they run over
+ * the caller's rows on the original time axis, as the path scores do.
+ *
+ * Kernels.  Kernel A is the forward of g in the packed trellis of the target
+ * scores (max_target <= 63: segments of 8, 16, 32 or 64 lanes, rows staged
+ * through LDS up to ctcext_target_scores_tile's class counts and gathered
+ * above); it stores bl_f and nb_f of every frame f < frames, as absolute log
+ * values, into a tails workspace [batch][n_targets][max_time][2] of the compute
+ * dtype (followed by one int32 a prefix), grow-only on the handle.  Lists with
+ * max_target >= 64 run one wave per prefix with the states in LDS, up to the
+ * path scores' row limits (min(max_target, max_time) above 13000, 8000 for
+ * float64: CTCEXT_UNIMPLEMENTED); CTCEXT_TARGETS=rows / =gathered forces
+ * Kernel A's route as it forces the target scores'.  Kernel B reduces the tails against
+ * every class column: work split over (item, group of G prefixes, class tile),
+ * the logits read in place and once a group, the tails through LDS in tiles of
+ * CTCEXT_PREFIX_TIME_TILE frames, an online LSE of one exp a term in registers.
+ * Its wide layout gives a workgroup 256 classes; its narrow layout (small
+ * alphabets: ctcext_prefix_scores_layout) 32 classes times
+ * CTCEXT_PREFIX_NARROW_SLICES interleaved time slices, merged through LDS in
+ * slice order.  Both evaluate in the compute dtype in the log domain and agree
+ * with the definition to the rounding of the recursion and of the reduction,
+ * not bit for bit.  Diagnostics: the environment variable CTCEXT_PREFIX=narrow
+ * / =wide, read at every call, forces a layout (both hold every class count).
+ *
+ * Not covered: streams over the score store; a stateful step-by-step form that
+ * carries the tails between calls; scorer-table terms; a synchronous form
+ * after ctcext_decode; handles of more than one device (CTCEXT_UNIMPLEMENTED). */
+#define CTCEXT_HAS_PREFIX_SCORES 1
+#define CTCEXT_PREFIX_TIME_TILE 64
+#define CTCEXT_PREFIX_NARROW_SLICES 8
+
+/* Validates (ctcext_targets_validate), then enqueues the two kernels on the
+ * stream of the last ctcext_decode_dense / ctcext_decode_dense_skip /
+ * ctcext_decode_greedy (with the score opt-in), behind whatever that stream
+ * holds, over that call's logits (in place), normaliser, frames and final
+ * status word.  ext_logp is a device pointer, [batch][n_targets][num_classes]
+ * of the compute dtype.  The first call of a shape grows the tails workspace
+ * and may block; once it has its size: no allocation, no host-blocking call,
+ * capturable into the same graph as the decode.  A call that would have to
+ * grow it while the stream is capturing: CTCEXT_FAILED_PRECONDITION, as is a
+ * call without such a preceding dense call.  n_targets == 0 or batch == 0:
+ * CTCEXT_OK with nothing launched. */
+int ctcext_dense_prefix_scores(ctcext_decoder* dec, const ctcext_targets* prefixes, void* ext_logp);
+/* Kernel B's layout for this class count: 0 narrow, 1 wide. */
+int32_t ctcext_prefix_scores_layout(int64_t num_classes, int32_t f64);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the times of
+ * the last prefix scores' two kernels in ms.  Waits for them. */
+int ctcext_dense_prefix_scores_ms(ctcext_decoder* dec, double* tails_ms, double* reduce_ms);
+/* The definition for one prefix, on the host, in long double (no HIP call):
+ * x [frames][num_classes] and norm [frames] of the compute dtype (float32, or
+ * float64 with f64), prefix m labels; ext [num_classes] of the same type.
+ * CTCEXT_INVALID_ARGUMENT for a negative size, a blank_index outside [0, C) or
+ * a null pointer that is needed. */
+int ctcext_prefix_score_row(const void* x, const void* norm, int32_t f64, int64_t frames, int64_t num_classes,
+                            const int64_t* prefix, int64_t m, int32_t blank_index, void* ext /* [num_classes] */);
+
+/* ---------------------------------------------------------------------------
  * Target alignments: the forced Viterbi alignment of label rows the CALLER
  * supplies, on the device -- where in the audio each label of a reference
  * transcript, a subtitle line or another pass's N-best entry lies, and how

@@ -543,6 +543,80 @@ def transcripts_report(args):
     return lines, res
 
 
+def prefixes_report(args):
+    """--prefixes: the prefix scores' two kernels (device events: ctcext_dense_prefix_scores_ms) beside the whole
+    score_prefixes call, 16 prefixes of 20 to 60 labels an item, at cfg3 and at B=32 T=750 C=5000, for both layouts
+    (CTCEXT_PREFIX) and with the per-row forward (CTCEXT_TARGETS=rows); a sweep of class counts for the layouts' switch; and what a
+    caller had before: dense_target_scores over the N * (C - 1) extended rows at the cfg3 shape."""
+    dec = ctcext_amd.get_decoder(0)
+    rng = np.random.default_rng(20261126)
+    N, lo, hi = 16, 20, 60
+    res = {"runs": args.runs, "prefixes": [N, lo, hi], "shapes": {}}
+    lines = ["%-26s %7s %7s %10s %10s %12s   (median of %d runs, ms; %d prefixes of %d..%d labels an item)"
+             % ("shape", "layout", "forward", "tails", "reduce", "whole call", args.runs, N, lo, hi)]
+
+    def once(x, sl, y, n, layout=None, forward=None):
+        for k, v in (("CTCEXT_PREFIX", layout), ("CTCEXT_TARGETS", forward)):
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = str(v)
+        torch.cuda.synchronize()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record()
+        ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True, **KW)
+        out = ctcext_amd.dense_prefix_scores(y, n)
+        e[1].record()
+        e[1].synchronize()
+        a, b = ctypes.c_double(), ctypes.c_double()
+        if dec.lib.ctcext_dense_prefix_scores_ms(dec.handle, ctypes.byref(a), ctypes.byref(b)) != _lib.CTCEXT_OK:
+            raise SystemExit(dec.lib.ctcext_last_error().decode())
+        return a.value, b.value, e[0].elapsed_time(e[1]), out
+
+    def inputs(B, T, C):
+        x = times_inputs("gaussian", T, B, C)
+        sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+        y = torch.as_tensor(rng.integers(1, C, size=(B, N, hi)), device="cuda:0")
+        n = torch.as_tensor(rng.integers(lo, hi + 1, size=(B, N)).astype(np.int32), device="cuda:0")
+        return x, sl, y, n
+
+    def row(name, data, layout, forward=None):
+        once(*data, layout, forward)   # warm-up
+        runs = [once(*data, layout, forward)[:3] for _ in range(args.runs)]
+        t, r, c = (statistics.median(v) for v in zip(*runs))
+        lines.append("%-26s %7s %7s %10.4f %10.4f %12.4f" % (name, layout or "default", forward or "packed", t, r, c))
+        return {"tails": stat([v[0] for v in runs]), "reduce": stat([v[1] for v in runs]), "call": stat([v[2] for v in runs])}
+
+    B3, T3, C3 = SHAPES["cfg3"][:3]
+    for name, (B, T, C) in (("cfg3", (B3, T3, C3)), ("B32-T750-C5000", (32, 750, 5000))):
+        data = inputs(B, T, C)
+        tag = "%s B=%d T=%d C=%d" % (name, B, T, C)
+        res["shapes"][name] = {"default": row(tag, data, None), "rows": row(tag, data, None, "rows")}
+        for layout in ("narrow", "wide"):
+            res["shapes"][name][layout] = row(tag, data, layout)
+        if name == "cfg3":   # the nearest thing before: every g.c as a whole transcript, N * (C - 1) rows of up to 61 labels
+            x, sl, y, n = data
+            ext = torch.zeros((B, N, C - 1, hi + 1), dtype=torch.int64, device="cuda:0")
+            ext[:, :, :, :hi] = y[:, :, None, :]
+            ext.scatter_(3, n.long()[:, :, None, None].expand(B, N, C - 1, 1),
+                         torch.arange(1, C, device="cuda:0")[None, None, :, None].expand(B, N, C - 1, 1))
+            ye, ne = ext.reshape(B, N * (C - 1), hi + 1), (n + 1)[:, :, None].expand(B, N, C - 1).reshape(B, -1).contiguous()
+            ms, v = [], ctypes.c_double()
+            for _ in range(args.runs + 1):
+                ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True, **KW)
+                ctcext_amd.dense_target_scores(ye, ne)
+                if dec.lib.ctcext_dense_target_scores_ms(dec.handle, ctypes.byref(v)) != _lib.CTCEXT_OK:
+                    raise SystemExit(dec.lib.ctcext_last_error().decode())
+                ms.append(v.value)
+            lines.append("%-26s dense_target_scores over %d extended rows an item: %.4f ms" % (tag, N * (C - 1), statistics.median(ms[1:])))
+            res["shapes"][name]["target_scores_extended"] = stat(ms[1:])
+    for C in (29, 64, 96, 128, 192, 256, 512):   # the layouts' switch, at cfg3's batch and frames
+        data = inputs(B3, T3, C)
+        res["shapes"]["switch-C%d" % C] = {k: row("switch B=%d T=%d C=%d" % (B3, T3, C), data, k) for k in ("narrow", "wide")}
+    for k in ("CTCEXT_PREFIX", "CTCEXT_TARGETS"):
+        os.environ.pop(k, None)
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -567,9 +641,11 @@ def main():
                     help="the target-alignments kernel at cfg3 beside the target-scores kernel and its own gathered route")
     ap.add_argument("--transcripts", action="store_true",
                     help="the transcript-alignments kernel at cfg3 beside the path-alignment kernels on the same rows")
+    ap.add_argument("--prefixes", action="store_true",
+                    help="the prefix-scores kernels at cfg3 and at B=32 T=750 C=5000: layouts, G, and the target scores of the extended rows")
     args = ap.parse_args()
-    if args.times or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign or args.transcripts:
-        lines, res = transcripts_report(args) if args.transcripts else talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.times or args.prefixes or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign or args.transcripts:
+        lines, res = prefixes_report(args) if args.prefixes else transcripts_report(args) if args.transcripts else talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
