@@ -33,6 +33,7 @@
 #include "ctcx_talign.h"
 #include "ctcx_transcripts.h"
 #include "ctcx_prefix.h"
+#include "ctcx_tgrad.h"
 #include "ctcx_targets.h"
 #include "ctcx_times.h"
 
@@ -179,6 +180,7 @@ struct Dev {
   hipEvent_t ta[2] = {};     // ... of a dense call's target alignments: around the kernel
   hipEvent_t tr[2] = {};     // ... of a dense call's transcript alignments: around the kernel
   hipEvent_t px[3] = {};     // ... of a dense call's prefix scores: before Kernel A, between the two, after Kernel B
+  hipEvent_t tg[2] = {};     // ... of a dense call's target gradients: around the launches
   DevBuf x, xw, sl, norm, prep, rec, foff, item, top_pos, top_kind, logp, seq, len, phase, sctab, gstate;
   DevBuf gk, glp;            // the greedy decode: the rows' arg-max [T][B] and max - norm [T][B]
   DevBuf dsl, dstat;         // the dense path: sanitised lengths [B]; status before [B] and after [B] the decode, table flag
@@ -240,6 +242,8 @@ struct ctcext_decoder {
     bool talign_timed = false;  // events ta[0], ta[1] were recorded
     bool transcripts_timed = false;   // events tr[0], tr[1] were recorded
     bool prefix_timed = false;        // events px[0 .. 3) were recorded
+    int tgrad_route = -1;             // the route of the last ctcext_dense_target_grads behind it (-1: none)
+    bool tgrad_timed = false;         // events tg[0], tg[1] were recorded
   } dense;
   // what ctcext_fetch_token_times needs of the last synchronous decode or
   // push beside the walks: the items' frames (host) and the labels' rule
@@ -261,6 +265,7 @@ struct ctcext_decoder {
   DevBuf ta_bp;   // the target alignments' grow-only decision words (ctcx_talign.h)
   DevBuf tr_bp;   // the transcript alignments' grow-only decision words (ctcx_transcripts.h)
   DevBuf px_ws;   // the prefix scores' grow-only tails workspace (ctcx_prefix.h)
+  DevBuf tg_ws;   // the target gradients' grow-only checkpoints (ctcx_tgrad.h)
   // blank-frame skipping (ctcext.h, "Blank-frame skipping"): the workspace of
   // the plan, and what the call that is running reads of it
   struct {
@@ -287,6 +292,8 @@ static void release_dev(Dev& d) {
   for (auto& ev : d.tr)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.px)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& ev : d.tg)
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : d.al)
     if (ev) (void)hipEventDestroy(ev);
@@ -337,6 +344,7 @@ extern "C" int ctcext_create_sharded(const int* devices, int n_devices, ctcext_d
     for (auto& ev : v.ta) (void)hipEventCreate(&ev);
     for (auto& ev : v.tr) (void)hipEventCreate(&ev);
     for (auto& ev : v.px) (void)hipEventCreate(&ev);
+    for (auto& ev : v.tg) (void)hipEventCreate(&ev);
     // the shard inputs and the gathered walks move between the root and this
     // device by peer copies (xGMI); "already enabled" is fine
     if (v.device != devices[0]) {
@@ -362,7 +370,7 @@ extern "C" void ctcext_destroy(ctcext_decoder* d) {
   DeviceGuard guard;
   (void)hipSetDevice(d->devs[0].device);
   DevBuf* bufs[] = {&d->off, &d->res, &d->ptrs, &d->out_idx, &d->out_val, &d->tt_frames, &d->tt_start, &d->tt_end,
-                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out, &d->ta_bp, &d->tr_bp, &d->px_ws,
+                    &d->tt_trail, &d->sc_sum, &d->sc_min, &d->ps_out, &d->al_bp, &d->al_fin, &d->al_vseq, &d->al_vlen, &d->al_out, &d->ta_bp, &d->tr_bp, &d->px_ws, &d->tg_ws,
                     &d->skip.norm, &d->skip.kmap, &d->skip.cidx, &d->skip.kept, &d->skip.xc};
   for (DevBuf* b : bufs) b->release();
   d->h_item.release();
@@ -3802,6 +3810,106 @@ extern "C" int ctcext_dense_prefix_scores_ms(ctcext_decoder* d, double* tails_ms
   *tails_ms = f;
   HIP_OR_FAIL(hipEventElapsedTime(&f, root.px[1], root.px[2]));
   *reduce_ms = f;
+  return CTCEXT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Target gradients (ctcext.h, "Target gradients"): the target scores' sources
+// and packed trellis, in ctcx_tgrad.hip's one kernel (forward with checkpoints,
+// backward by tiles, class-major reduce), one launch per group of targets.
+
+static_assert(CTCEXT_TARGET_GRADS_TILE_F32 == kTgradK32 && CTCEXT_TARGET_GRADS_TILE_F64 == kTgradK64,
+              "ctcext.h states the kernel's tile");
+
+extern "C" int ctcext_dense_target_grads(ctcext_decoder* d, const ctcext_targets* t, const void* weights, void* scores,
+                                         void* grad, int32_t batch_first) {
+  if (!d) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  int rc = ctcext_targets_validate(t);
+  if (rc != CTCEXT_OK) return rc;
+  if (!d->dense.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "ctcext_dense_target_grads without a ctcext_decode_dense");
+  if (d->devs.size() != 1) return fail(CTCEXT_UNIMPLEMENTED, "target gradients need a one-device decoder handle");
+  d->dense.tgrad_route = -1;
+  d->dense.tgrad_timed = false;
+  if (!d->dense.sc.have)
+    return fail(CTCEXT_FAILED_PRECONDITION, "target gradients need a dense call that kept its logits and normaliser");
+  if (t->max_target > kTargetsMaxPacked)
+    return fail(CTCEXT_UNIMPLEMENTED, "target gradients: max_target must be at most 63 (longer targets have no route yet)");
+  if (d->dense.B == 0) return CTCEXT_OK;
+  if (!grad || (t->n_targets > 0 && !scores)) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  const ScoreSrc& q = d->dense.sc;
+  const int route = targets_route(d->dense.C, t->max_target, q.f64) == 2 ? 2 : 1;   // (CTCEXT_TARGETS=gathered forces it)
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  hipStream_t s = d->dense.s;
+  const int64_t B = d->dense.B;
+  // the checkpoints: grow-only; a call that has to grow them may block, and is refused while the stream is capturing
+  // CTCEXT_TGRADS=forward (diagnostics; read at every call): the forward with its checkpoints alone;
+  // CTCEXT_TGRADS_TILE=n: a tile of n frames where n is a power of two below the default
+  const char* v = getenv("CTCEXT_TGRADS");
+  const char* vt = getenv("CTCEXT_TGRADS_TILE");
+  int tile = ctcx_tgrad_tile(d->dense.C, q.f64 ? 1 : 0, route == 1 ? 1 : 0);
+  const int asked = vt ? atoi(vt) : 0;
+  if (asked >= 1 && asked < tile && (asked & (asked - 1)) == 0) tile = asked;
+  const size_t want = (size_t)ctcx_tgrad_bytes(B, d->dense.T, tile, q.f64 ? 1 : 0);
+  if (want > d->tg_ws.cap) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &st) != hipSuccess) (void)hipGetLastError();
+    if (st != hipStreamCaptureStatusNone)
+      return fail(CTCEXT_FAILED_PRECONDITION,
+                  "target gradients: the workspace must grow and the stream is capturing; call once with this shape "
+                  "before the capture");
+    HIP_OR_FAIL(d->tg_ws.ensure(want));
+  }
+  CtcxTgradParams p{};
+  p.t.targets = t->targets; p.t.target_length = t->target_length;
+  p.t.frames = (const int32_t*)root.dsl.p; p.t.status = (const int32_t*)root.dstat.p + B;
+  p.t.x = q.x; p.t.norm = q.norm;
+  p.t.Tmax = d->dense.T; p.t.B = B; p.t.C = d->dense.C; p.t.xst_t = q.st_t; p.t.xst_b = q.st_b;
+  p.t.N = t->n_targets; p.t.L = t->max_target;
+  p.t.xfmt = q.xfmt; p.t.f64 = q.f64 ? 1 : 0; p.t.blank_index = d->dense.blank_index;
+  p.t.shared = t->shared ? 1 : 0; p.t.labels_i64 = t->labels_i64 ? 1 : 0;
+  p.t.staged = route == 1 ? 1 : 0;
+  p.t.out = scores;
+  p.weights = weights;
+  p.grad = grad;
+  p.ost_t = batch_first ? d->dense.C : B * d->dense.C;
+  p.ost_b = batch_first ? d->dense.T * d->dense.C : d->dense.C;
+  p.ws = d->tg_ws.p;
+  p.tile = tile;
+  p.forward_only = v && std::string(v) == "forward" ? 1 : 0;
+  const bool prof = (d->dense.flags & CTCEXT_FLAG_PROFILE) != 0;
+  if (prof) HIP_OR_FAIL(hipEventRecord(root.tg[0], s));
+  HIP_OR_FAIL(ctcx_launch_target_grads(p, s));   // (n_targets == 0: one launch that zero-fills the slab)
+  if (prof) {
+    HIP_OR_FAIL(hipEventRecord(root.tg[1], s));
+    d->dense.tgrad_timed = true;
+  }
+  d->dense.tgrad_route = route;
+  g_err.clear();
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_target_grads_route(ctcext_decoder* d, int32_t* route) {
+  if (!d || !route) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || d->dense.tgrad_route < 0)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no target gradients were enqueued behind the last dense decode");
+  *route = d->dense.tgrad_route;
+  return CTCEXT_OK;
+}
+
+extern "C" int ctcext_dense_target_grads_ms(ctcext_decoder* d, double* ms) {
+  if (!d || !ms) return fail(CTCEXT_INVALID_ARGUMENT, "null argument");
+  if (!d->dense.have || !d->dense.tgrad_timed)
+    return fail(CTCEXT_FAILED_PRECONDITION, "no target gradients of a CTCEXT_FLAG_PROFILE dense decode");
+  DeviceGuard guard;
+  Dev& root = d->devs[0];
+  HIP_OR_FAIL(hipSetDevice(root.device));
+  HIP_OR_FAIL(hipEventSynchronize(root.tg[1]));
+  float f = 0;
+  HIP_OR_FAIL(hipEventElapsedTime(&f, root.tg[0], root.tg[1]));
+  *ms = f;
   return CTCEXT_OK;
 }
 

@@ -10,7 +10,8 @@ from .ops import (CTCExtBeamSearchDecoder, Decoder, DenseDecode, FailedPrecondit
                   PathAlignments, dense_path_alignments, path_alignments, path_alignment_row,
                   decode_greedy, greedy_row, GreedyPush, GreedyStream, dense_target_scores, score_targets,
                   TargetAlignments, dense_target_alignments, forced_align, dense_transcript_alignments,
-                  align_transcripts, dense_prefix_scores, score_prefixes, prefix_score_row)
+                  align_transcripts, dense_prefix_scores, score_prefixes, prefix_score_row,
+                  TargetGrads, dense_target_grads, target_grads, score_targets_autograd, target_grad_row)
 
 __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDecoder", "Decoder", "get_decoder", "StreamDecoder",
            "StablePrefix", "StreamDense",
@@ -24,5 +25,6 @@ __all__ = ["ctc_ext_beam_search_decoder", "decode_logits", "CTCExtBeamSearchDeco
            "dense_target_alignments", "forced_align", "TargetAlignments",
            "dense_transcript_alignments", "align_transcripts",
            "dense_prefix_scores", "score_prefixes", "prefix_score_row",
+           "dense_target_grads", "target_grads", "score_targets_autograd", "target_grad_row", "TargetGrads",
            "OpError", "InvalidArgumentError", "FailedPreconditionError", "UnimplementedError",
            "InternalError"]

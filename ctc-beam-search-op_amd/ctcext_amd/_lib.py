@@ -110,6 +110,10 @@ EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TRANSCRIPT_ALIGNMENTS_SYMBOLS
 PREFIX_SCORES_SYMBOLS = ("ctcext_dense_prefix_scores", "ctcext_prefix_scores_layout", "ctcext_dense_prefix_scores_ms",
                          "ctcext_prefix_score_row")
 EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + PREFIX_SCORES_SYMBOLS
+# target gradients (CTCEXT_HAS_TARGET_GRADS)
+TARGET_GRADS_SYMBOLS = ("ctcext_dense_target_grads", "ctcext_dense_target_grads_route", "ctcext_dense_target_grads_ms",
+                        "ctcext_target_grad_row")
+EXPORTED_SYMBOLS = EXPORTED_SYMBOLS + TARGET_GRADS_SYMBOLS
 CTCEXT_ITEM_CAPACITY = 16        # status bit of a push: the chunk would take the item past max_frames
 CTCEXT_FLAG_DENSE_NULL_STREAM = 512   # ctcext_decode_dense: stream NULL is the null stream itself
 CTCEXT_ITEM_LENGTH = 1           # status bits: sequence_length(b) > max_time
@@ -547,6 +551,18 @@ def load():
         lib.ctcext_transcript_alignments_block_frames.restype = ctypes.c_int32
         lib.ctcext_transcript_alignments_word_frames.argtypes = [ctypes.c_int64]
         lib.ctcext_transcript_alignments_word_frames.restype = ctypes.c_int32
+    if hasattr(lib, "ctcext_dense_target_grads"):   # (CTCEXT_HAS_TARGET_GRADS)
+        lib.ctcext_dense_target_grads.argtypes = [ctypes.c_void_p, ctypes.POINTER(Targets), ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+        lib.ctcext_dense_target_grads.restype = ctypes.c_int
+        lib.ctcext_dense_target_grads_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+        lib.ctcext_dense_target_grads_route.restype = ctypes.c_int
+        lib.ctcext_dense_target_grads_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        lib.ctcext_dense_target_grads_ms.restype = ctypes.c_int
+        lib.ctcext_target_grad_row.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        lib.ctcext_target_grad_row.restype = ctypes.c_int
     if hasattr(lib, "ctcext_dense_prefix_scores"):   # (CTCEXT_HAS_PREFIX_SCORES)
         lib.ctcext_dense_prefix_scores.argtypes = [ctypes.c_void_p, ctypes.POINTER(Targets), ctypes.c_void_p]
         lib.ctcext_dense_prefix_scores.restype = ctypes.c_int

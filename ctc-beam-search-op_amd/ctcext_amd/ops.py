@@ -530,6 +530,7 @@ def decode_dense(logits, lengths, beam_width, top_paths, *, batch_first=True,
     if token_scores:   # (dense_token_scores' output shapes and dtype, and the rows its kernel reads)
         dec._scores_keep = x
         dec._scores_dense = (B, P, T, dev, fdt)
+        dec._scores_batch_first = bool(batch_first) and x.dim() == 3   # (dense_target_grads' slab follows it)
     # x, sl and tab may be temporaries: they were allocated on this stream, and
     # the caching allocator hands their memory out again in stream order
     del x, sl, tab
@@ -628,6 +629,7 @@ def decode_greedy(logits, lengths, *, batch_first=True, merge_repeated=False, bl
     if token_scores:
         dec._scores_keep = x
         dec._scores_dense = (B, 1, T, dev, fdt)
+        dec._scores_batch_first = bool(batch_first) and x.dim() == 3
     del x, sl
     return out
 
@@ -1114,6 +1116,148 @@ def prefix_score_row(x, norm, prefix, frames, blank_index):
     if rc != _lib.CTCEXT_OK:
         raise InvalidArgumentError("ctcext_prefix_score_row: bad arguments", rc)
     return out[:C]
+
+
+TargetGrads = collections.namedtuple("TargetGrads", ["scores", "grad"])
+
+
+def _tgrad_lib(lib):
+    if not hasattr(lib, "ctcext_dense_target_grads"):
+        raise UnimplementedError("this libctcext.so has no target gradients (CTCEXT_HAS_TARGET_GRADS)",
+                                 _lib.CTCEXT_UNIMPLEMENTED)
+    return lib
+
+
+def dense_target_grads(targets, target_lengths, weights=None, device=None):
+    """CTC forward-backward over supplied targets: ``dense_target_scores`` and,
+    with it, ``sum_n weights[b, n] * d log p(y_n | x) / d logits[b]`` under the
+    logits of the calling thread's last ``decode_dense(..., token_scores=True)``
+    or ``decode_greedy(..., token_scores=True)`` on ``device`` (None: the
+    current one) -- what minimum-risk training over a rescored N-best, a
+    keyword list trained against a list or a CTC loss on short utterances
+    needs.  Enqueued behind that decode on its stream; after one call of a
+    shape nothing is allocated or waited for, so it can be captured into the
+    same ``torch.cuda.graph``.
+
+    ``targets`` and ``target_lengths`` are ``dense_target_scores``'s;
+    ``weights`` is a CUDA tensor ``[B, N]`` of the compute dtype, or None for
+    ones.  Returns ``TargetGrads(scores, grad)``: ``scores`` is
+    ``dense_target_scores``'s ``[B, N]``, ``grad`` a contiguous CUDA tensor of
+    the compute dtype, ``[B, T, C]`` or ``[T, B, C]`` as the logits the decode
+    read were oriented, every cell written (zeros past an item's length).  Rows
+    without a finite score (``-inf`` or NaN) add nothing; the definition is in
+    ``include/ctcext.h``, "Target gradients".  Targets of more than 63 labels
+    raise ``UnimplementedError``."""
+    what = "ctcext_dense_target_grads without a ctcext_decode_dense"
+    dec = _thread_decoder(device, what)
+    lib = _tgrad_lib(dec.lib)
+    if getattr(dec, "_times_dense", None) is None:
+        raise FailedPreconditionError(what, _lib.CTCEXT_FAILED_PRECONDITION)
+    shape = getattr(dec, "_scores_dense", None)
+    if shape is None:
+        raise FailedPreconditionError("target gradients need a decode with token_scores=True",
+                                      _lib.CTCEXT_FAILED_PRECONDITION)
+    B, P, T, dev, fdt = shape
+    import torch
+    if not (_is_torch(targets) and _is_torch(target_lengths) and targets.is_cuda and target_lengths.is_cuda):
+        raise TypeError("dense_target_grads: targets and target_lengths must be CUDA tensors")
+    if targets.dtype not in (torch.int64, torch.int32):
+        _type_error("targets", str(targets.dtype).replace("torch.", ""), "int32, int64")
+    if target_lengths.dtype != torch.int32:
+        _type_error("target_lengths", str(target_lengths.dtype).replace("torch.", ""), "int32")
+    if targets.device != dev or target_lengths.device != dev:
+        raise InvalidArgumentError("target gradients: the targets must be on the decode's device",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    shared = targets.dim() == 2
+    if targets.dim() not in (2, 3) or tuple(target_lengths.shape) != tuple(targets.shape[:-1]) or \
+            (not shared and targets.shape[0] != B):
+        raise InvalidArgumentError("target gradients: targets must be [B, N, L] or [N, L], and target_lengths [B, N] or [N]",
+                                   _lib.CTCEXT_INVALID_ARGUMENT)
+    targets, target_lengths = targets.contiguous(), target_lengths.contiguous()
+    N, L = int(targets.shape[-2]), int(targets.shape[-1])
+    if weights is not None:
+        if not (_is_torch(weights) and weights.is_cuda and weights.device == dev):
+            raise TypeError("dense_target_grads: weights must be a CUDA tensor on the decode's device")
+        if weights.dtype != fdt:
+            _type_error("weights", str(weights.dtype).replace("torch.", ""), str(fdt).replace("torch.", ""))
+        if tuple(weights.shape) != (B, N):
+            raise InvalidArgumentError("target gradients: weights must be [B, N]", _lib.CTCEXT_INVALID_ARGUMENT)
+        weights = weights.detach().contiguous()
+    t = _lib.Targets(targets.data_ptr(), target_lengths.data_ptr(), N, L, 1 if shared else 0,
+                     1 if targets.dtype == torch.int64 else 0)
+    C = int(dec._scores_keep.shape[-1])   # (the kept logits: classes last)
+    bf = bool(getattr(dec, "_scores_batch_first", False))
+    with torch.cuda.device(dev):
+        scores = torch.empty((B, N), dtype=fdt, device=dev)
+        grad = torch.empty((B, T, C) if bf else (T, B, C), dtype=fdt, device=dev)
+    rc = lib.ctcext_dense_target_grads(dec.handle, ctypes.byref(t), None if weights is None else weights.data_ptr(),
+                                       scores.data_ptr(), grad.data_ptr(), 1 if bf else 0)
+    if rc != _lib.CTCEXT_OK:
+        _raise(lib, rc)
+    return TargetGrads(scores, grad)
+
+
+def target_grads(logits, lengths, targets, target_lengths, weights=None, *, blank_index=0, batch_first=True):
+    """``dense_target_grads`` for logits nothing has decoded yet:
+    ``decode_greedy(..., token_scores=True)`` supplies the normaliser, then the
+    forward-backward runs behind it on the same stream.  Arguments as for
+    ``decode_greedy`` and ``dense_target_grads``; returns ``TargetGrads``.
+    Nothing is waited for."""
+    decode_greedy(logits, lengths, batch_first=batch_first, blank_index=blank_index, token_scores=True)
+    return dense_target_grads(targets, target_lengths, weights, device=logits.device)
+
+
+def score_targets_autograd(logits, lengths, targets, target_lengths, *, blank_index=0, batch_first=True):
+    """``score_targets`` that ``torch.autograd`` can differentiate with respect
+    to ``logits``: the forward is ``score_targets``; the backward runs the
+    greedy pre-pass on the saved logits again (the handle may have moved on)
+    and ``dense_target_grads`` with the incoming gradient as the weights, and
+    returns the slab in the logits' dtype.  Rows without a finite score pass no
+    gradient."""
+    import torch
+
+    class _ScoreTargets(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            ctx.save_for_backward(x)
+            return score_targets(x, lengths, targets, target_lengths, blank_index=blank_index, batch_first=batch_first)
+
+        @staticmethod
+        def backward(ctx, v):
+            x, = ctx.saved_tensors
+            g = target_grads(x, lengths, targets, target_lengths, v.contiguous(), blank_index=blank_index,
+                             batch_first=batch_first).grad
+            return g.to(x.dtype)
+
+    return _ScoreTargets.apply(logits)
+
+
+def target_grad_row(x, norm, target, frames, blank_index):
+    """The definition of the target gradients for one target, on the host (no
+    GPU), in long double: ``x`` is one item's logits ``[frames, num_classes]``
+    (float32 or float64, the compute dtype), ``norm`` its rows' normaliser
+    ``[frames]``, ``target`` the label row (without padding).  Returns
+    ``(logp, g)``: a scalar and a numpy array ``[frames, num_classes]`` of
+    ``x``'s dtype; a row without a finite score has an all-zero ``g``."""
+    lib = _tgrad_lib(_lib.load())
+    x = np.asarray(x)
+    dt = np.float64 if x.dtype == np.float64 else np.float32
+    frames = int(frames)
+    if x.ndim != 2:
+        raise ValueError("target_grad_row: x must be [frames, num_classes]")
+    C = int(x.shape[1])
+    x = np.ascontiguousarray(x[:frames], dtype=dt)
+    nm = np.ascontiguousarray(np.asarray(norm).reshape(-1)[:frames], dtype=dt)
+    if x.shape[0] != frames or nm.size != frames:
+        raise ValueError("target_grad_row: x and norm must hold the item's frames")
+    y = np.ascontiguousarray(np.asarray(target, dtype=np.int64).reshape(-1))
+    logp, g = np.empty((1,), dt), np.empty((max(frames, 1), max(C, 1)), dt)
+    rc = lib.ctcext_target_grad_row(x.ctypes.data, nm.ctypes.data, 1 if dt == np.float64 else 0, frames, C,
+                                    _ptr(y, ctypes.c_int64), int(y.size), int(blank_index), logp.ctypes.data,
+                                    g.ctypes.data)
+    if rc != _lib.CTCEXT_OK:
+        raise InvalidArgumentError("ctcext_target_grad_row: bad arguments", rc)
+    return logp[0], g[:frames, :C]
 
 
 TargetAlignments = collections.namedtuple("TargetAlignments", ["logp", "times", "scores", "alignment"])

@@ -1624,6 +1624,98 @@ int ctcext_prefix_score_row(const void* x, const void* norm, int32_t f64, int64_
                             const int64_t* prefix, int64_t m, int32_t blank_index, void* ext /* [num_classes] */);
 
 /* ---------------------------------------------------------------------------
+ * Target gradients: CTC forward-backward over label rows the CALLER supplies,
+ * on the device -- the derivative of the target scores with respect to the
+ * logits, which minimum-risk (MWER) fine-tuning over a rescored N-best, a
+ * keyword list trained against a list and a CTC loss on short utterances need,
+ * and whose occupancies are per-frame posteriors.  New entry points only
+ * (CTCEXT_ABI_VERSION is unchanged; detect them by CTCEXT_HAS_TARGET_GRADS at
+ * build time or by symbol at run time); ctcext_targets and
+ * ctcext_targets_validate are reused as they are.
+ *
+ * Definition.  Notation of "Path scores": for an item, F its frames,
+ * lp[f][c] = x[f][c] - norm[f] as one rounded subtraction in the compute
+ * dtype; a target y of m labels has the 2m + 1 states z (blanks interleaved),
+ * the skip rule skip[s] and the recursion alpha_f(s) of the path scores.  beta
+ * is its mirror:
+ *   beta_{F-1}(s) = lp[F-1][z_s] for s in {2m, 2m - 1} (2m alone for m == 0),
+ *                   else -inf
+ *   beta_f(s) = LSE(beta_{f+1}(s), beta_{f+1}(s+1),
+ *                   skip[s+2] ? beta_{f+1}(s+2) : -inf) + lp[f][z_s]
+ * and with logp = LSE(alpha_{F-1}(2m), alpha_{F-1}(2m - 1))
+ *   occ_f(c)  = sum over s with z_s == c of
+ *               exp(alpha_f(s) + beta_f(s) - lp[f][c] - logp)
+ *               (a state whose alpha_f(s) + beta_f(s) is -inf adds exactly 0)
+ *   g_n[f][c] = occ_f(c) - exp(lp[f][c])   for f < F;   0 for f >= F,
+ * which is d log p(y_n | x) / d x[f][c].  The call returns the scores
+ * [batch][n_targets], with the values and conventions of "Target scores", and
+ * the slab G[b] = sum_n w[b][n] * g_n over the rows whose score is finite.  A
+ * row whose score is -inf (infeasible, or every alignment passes a masked
+ * logit) or NaN (a bad label or length, an item with a status bit or a NaN
+ * normaliser) adds nothing and is recognisable by its score; an item without a
+ * finite row has an all-zero slab.  w is used as given (weights == NULL:
+ * ones): a zero adds nothing, a NaN propagates.  Every cell of the slab is
+ * written, the frames past an item's length included.
+ *
+ * The kernel agrees with the long-double definition (ctcext_target_grad_row)
+ * cell by cell to the rounding of the recursions, not bit for bit; the bits
+ * are the same on every run of the same call: there is no atomic, and every
+ * sum has a fixed order.
+ *
+ * Kernel.  The packed trellis of the target scores (segments of 8, 16, 32 or
+ * 64 lanes, 256 / segment targets of one item a workgroup, rows staged through
+ * LDS up to ctcext_target_scores_tile's class counts and gathered above;
+ * CTCEXT_TARGETS=gathered forces that route).  One launch: the forward stores a
+ * checkpoint of all states every K frames (CTCEXT_TARGET_GRADS_TILE_F32 /
+ * _F64, fewer where K staged rows would not fit a tile) into a workspace that
+ * is grow-only on the handle; the backward recomputes one tile of alpha into
+ * LDS, runs beta down it and turns each alpha into a weighted occupancy; a
+ * class-major reduce over lists of lanes built once per workgroup sums them
+ * per (frame, class) in lane order and writes rows along the class axis.  An
+ * item with more than 256 / segment targets takes one launch per group, in
+ * order on the stream: the first stores, the later ones add.
+ *
+ * Not covered: targets of 64 labels and more (CTCEXT_UNIMPLEMENTED: they need
+ * a workgroup per target); streams; a synchronous host form; handles of more
+ * than one device (CTCEXT_UNIMPLEMENTED); scorer-table terms. */
+#define CTCEXT_HAS_TARGET_GRADS 1
+#define CTCEXT_TARGET_GRADS_TILE_F32 16
+#define CTCEXT_TARGET_GRADS_TILE_F64 8
+
+/* Validates (ctcext_targets_validate), then enqueues the launches on the
+ * stream of the last ctcext_decode_dense / ctcext_decode_dense_skip /
+ * ctcext_decode_greedy (with the score opt-in), as ctcext_dense_target_scores
+ * does.  weights is a device pointer [batch][n_targets] of the compute dtype,
+ * or NULL; scores a device pointer [batch][n_targets] and grad one of
+ * [batch][max_time][num_classes] (batch_first != 0) or
+ * [max_time][batch][num_classes], dense, of the compute dtype.
+ * max_target >= 64: CTCEXT_UNIMPLEMENTED ("... max_target must be at most
+ * 63 ...").  The first call of a shape grows the workspace and may block; once
+ * it has its size: no allocation, no host-blocking call, capturable into the
+ * same graph as the decode.  A call that would have to grow it while the
+ * stream is capturing: CTCEXT_FAILED_PRECONDITION, as is a call without such a
+ * preceding dense call.  n_targets == 0: the slab is zero-filled. */
+int ctcext_dense_target_grads(ctcext_decoder* dec, const ctcext_targets* targets, const void* weights_or_null,
+                              void* scores_out, void* grad_out, int32_t batch_first);
+/* Which route the last ctcext_dense_target_grads behind the last dense call
+ * took: 1 staged, 2 gathered.  CTCEXT_FAILED_PRECONDITION where there is none. */
+int ctcext_dense_target_grads_route(ctcext_decoder* dec, int32_t* route);
+/* Diagnostics: with CTCEXT_FLAG_PROFILE in the decode's flags, the time of the
+ * last target gradients' launches in ms.  Waits for them.  (The environment
+ * variable CTCEXT_TGRADS=forward, read at every call, stops every launch
+ * behind its forward: the scores are written, the slab is not;
+ * CTCEXT_TGRADS_TILE=8 or 4 shortens the tile, for measurements.) */
+int ctcext_dense_target_grads_ms(ctcext_decoder* dec, double* ms);
+/* The definition for one target, on the host, in long double (no HIP call):
+ * x [frames][num_classes] and norm [frames] of the compute dtype (float32, or
+ * float64 with f64), target m labels; logp one value and grad
+ * [frames][num_classes] of the same type.  A row without a finite score has an
+ * all-zero grad.  CTCEXT_INVALID_ARGUMENT for a negative size, a blank_index
+ * outside [0, C) or a null pointer that is needed. */
+int ctcext_target_grad_row(const void* x, const void* norm, int32_t f64, int64_t frames, int64_t num_classes,
+                           const int64_t* target, int64_t m, int32_t blank_index, void* logp, void* grad);
+
+/* ---------------------------------------------------------------------------
  * Target alignments: the forced Viterbi alignment of label rows the CALLER
  * supplies, on the device -- where in the audio each label of a reference
  * transcript, a subtitle line or another pass's N-best entry lies, and how

@@ -617,6 +617,69 @@ def prefixes_report(args):
     return lines, res
 
 
+def tgrads_report(args):
+    """--tgrads: the target gradients at cfg3 over the --targets workload (64 targets of 4 to 15 labels an item):
+    the launches' time by device events (ctcext_dense_target_grads_ms), with smaller tiles (CTCEXT_TGRADS_TILE) and
+    the forward alone (CTCEXT_TGRADS=forward); dense_target_scores on the same rows in the same session; and
+    torch's own ctc_loss backward over the same (item, target) pairs flattened to a batch (another normaliser:
+    informative only)."""
+    B, T, C, W, P = SHAPES["cfg3"]
+    N, lo, hi = 64, 4, 15
+    dec = ctcext_amd.get_decoder(0)
+    sl = torch.full((B,), T, dtype=torch.int32, device="cuda:0")
+    x = times_inputs("gaussian", T, B, C)
+    rng = np.random.default_rng(20261126)
+    y = torch.as_tensor(rng.integers(1, C, size=(B, N, hi)), device="cuda:0")
+    n = torch.as_tensor(rng.integers(lo, hi + 1, size=(B, N)).astype(np.int32), device="cuda:0")
+    w = torch.as_tensor(rng.uniform(-1, 1, size=(B, N)).astype(np.float32), device="cuda:0")
+
+    def once(env, scores_only=False):
+        for k in ("CTCEXT_TGRADS", "CTCEXT_TGRADS_TILE"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        ctcext_amd.decode_greedy(x, sl, batch_first=False, flags=_lib.CTCEXT_FLAG_PROFILE, token_scores=True, **KW)
+        ms = ctypes.c_double()
+        if scores_only:
+            ctcext_amd.dense_target_scores(y, n)
+            rc = dec.lib.ctcext_dense_target_scores_ms(dec.handle, ctypes.byref(ms))
+        else:
+            ctcext_amd.dense_target_grads(y, n, w)
+            rc = dec.lib.ctcext_dense_target_grads_ms(dec.handle, ctypes.byref(ms))
+        if rc != _lib.CTCEXT_OK:
+            raise SystemExit(dec.lib.ctcext_last_error().decode())
+        return ms.value
+
+    lines = ["%-34s %10s   (median of %d runs after a warm-up, ms; cfg3 B=%d T=%d C=%d, %d targets of %d..%d labels an item)"
+             % ("what", "kernels", args.runs, B, T, C, N, lo, hi)]
+    res = {"runs": args.runs, "shape": [B, T, C], "targets": [N, lo, hi], "rows": {}}
+    for name, env, so in (("target gradients (tile 16)", {}, False), ("target gradients, tile 8", {"CTCEXT_TGRADS_TILE": "8"}, False),
+                          ("target gradients, tile 4", {"CTCEXT_TGRADS_TILE": "4"}, False),
+                          ("forward with checkpoints alone", {"CTCEXT_TGRADS": "forward"}, False),
+                          ("dense_target_scores, same rows", {}, True)):
+        once(env, so)
+        runs = [once(env, so) for _ in range(args.runs)]
+        lines.append("%-34s %10.4f" % (name, statistics.median(runs)))
+        res["rows"][name] = stat(runs)
+    for k in ("CTCEXT_TGRADS", "CTCEXT_TGRADS_TILE"):
+        os.environ.pop(k, None)
+    # what a caller had before: torch's loss over the B * N pairs as a batch, its backward timed by device events
+    lp = torch.log_softmax(x, 2).repeat_interleave(N, dim=1).requires_grad_()
+    runs = []
+    for _ in range(args.runs + 1):
+        loss = torch.nn.functional.ctc_loss(lp, y.reshape(B * N, hi), sl.long().repeat_interleave(N), n.reshape(-1).long(),
+                                            blank=0, reduction="sum")
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record()
+        loss.backward()
+        e[1].record()
+        e[1].synchronize()
+        runs.append(e[0].elapsed_time(e[1]))
+        lp.grad = None
+    lines.append("%-34s %10.4f" % ("torch ctc_loss backward, %d pairs" % (B * N), statistics.median(runs[1:])))
+    res["rows"]["torch_ctc_loss_backward"] = stat(runs[1:])
+    return lines, res
+
+
 def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
@@ -643,9 +706,11 @@ def main():
                     help="the transcript-alignments kernel at cfg3 beside the path-alignment kernels on the same rows")
     ap.add_argument("--prefixes", action="store_true",
                     help="the prefix-scores kernels at cfg3 and at B=32 T=750 C=5000: layouts, G, and the target scores of the extended rows")
+    ap.add_argument("--tgrads", action="store_true",
+                    help="the target-gradients kernel at cfg3 beside the target scores of the same rows and torch's ctc_loss backward")
     args = ap.parse_args()
-    if args.times or args.prefixes or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign or args.transcripts:
-        lines, res = prefixes_report(args) if args.prefixes else transcripts_report(args) if args.transcripts else talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
+    if args.tgrads or args.times or args.prefixes or args.scores or args.paths or args.align or args.greedy or args.targets or args.talign or args.transcripts:
+        lines, res = tgrads_report(args) if args.tgrads else prefixes_report(args) if args.prefixes else transcripts_report(args) if args.transcripts else talign_report(args) if args.talign else targets_report(args) if args.targets else greedy_report(args) if args.greedy else align_report(args) if args.align else paths_report(args) if args.paths else scores_report(args) if args.scores else times_report(args)
         text = "\n".join(lines) + "\n" + json.dumps(res)
         print(text)
         if args.out:
